@@ -332,6 +332,37 @@ def stream_copy_ceiling(device, n_bytes=1 << 30, reps=10):
     return 2.0 * n_bytes * reps / (a.elapsed_time(b) * 1e-3) / 1e9
 
 
+DUMP_USER_SAMPLE = 65536     # --dump-outputs: user rows written besides the last batch's (the item table goes out whole)
+
+
+def dump_outputs(eng, last_user, out_dir):
+    """--dump-outputs DIR: what the timed FOCF steps hand their caller after the last one, as .npy files (43 MB) --
+    the last step's loss slot, the engine's running loss total, the whole item table and the user rows of the last batch plus
+    a fixed seeded sample of the others.  Rows are read as of the last step (fr_table_gather: the lazy-Adam replay, nothing
+    in the tables is modified), so the timings taken after this see the same engine state."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    # the last fused step's loss is reduced, and the item runs of a pipelined item-complete step are applied, by the next
+    # launch or by finish(): the caller's check_device_errors() already ran it, this makes the dump independent of that
+    eng.finish()
+    torch.cuda.synchronize()
+    g = torch.Generator(device="cpu").manual_seed(SEED + 99991)
+    sample = torch.randperm(eng.U.n_rows, generator=g)[:DUMP_USER_SAMPLE]
+    user_ids = torch.unique(torch.cat([sample, last_user.cpu()]))        # sorted
+    item_ids = torch.arange(eng.I.n_rows, dtype=torch.int64)
+    out = {
+        "loss_last_step": eng.loss_ring[eng.loss_slot][:3],               # (loss, mse, fair) of the last timed step
+        "loss_running_total": eng.loss_acc[:5],                           # sums of loss, mse, fair; steps; first NaN step
+        "user_embedding_rows": eng.U.gather(eng.hyper, user_ids.to(eng.device), eng.err_flag),
+        "user_embedding_row_ids": user_ids.to(torch.float64),
+        "item_embedding": eng.I.gather(eng.hyper, item_ids.to(eng.device), eng.err_flag),
+    }
+    eng.check_device_errors()
+    for name, t in out.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def xavier_tables(n_users, n_items, dim, seed, device):
     g = torch.Generator(device="cpu").manual_seed(seed + 1)
     U = torch.randn(n_users, dim, generator=g) * math.sqrt(2.0 / (n_users + dim))
@@ -566,7 +597,12 @@ def main():
     ap.add_argument("--age", type=int, default=0,
                     help="optimizer steps run before the warm-up so that the lazy-Adam staleness is stationary "
                          "(default: one sweep period)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (last step's loss, loss total, item table, a fixed "
+                         "sample of user rows) as DIR/<name>.npy, so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "focf" or args.gpus != 1 or args.force_sharded):
+        raise SystemExit("--dump-outputs: the single-GPU FOCF run only (--workload focf --gpus 1, no --force-sharded)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -792,6 +828,8 @@ def main():
         dt = float(t.item())
     eng.check_device_errors()
     loss_last = float(eng.loss_ring[eng.loss_slot][0].item()) if not sharded else float("nan")
+    if args.dump_outputs:
+        dump_outputs(eng, u[W + K - 1], args.dump_outputs)
     launch = {"library": "library step loop (fr_focf_runs_many)" if (not sharded and eng.item_runs) else "library step loop (fr_focf_steps_many)",
               "graph": "hipGraph" if graph is not None else "eager", "eager": "eager"}[launch_mode]
     other = None

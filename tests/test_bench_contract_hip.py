@@ -78,6 +78,88 @@ def test_bench_json_contract(args):
         assert "other_workloads" not in d
 
 
+def _eager_reference(item_dist, age=8, W=2, K=12):
+    """bench.py's batches (same seeds, same counts) stepped by a fresh engine on the three-launch chain (fr_focf_forward +
+    fr_focf_backward_adam, no deferred loss, no look-ahead): an independent path to what `--dump-outputs` reports.  Returns the
+    (loss, mse, fair) of every step, the flushed tables and the user ids of the last timed batch."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    from fairrec.model.fair_recommender.focf import FocfEngine
+    from fairrec.optim import FusedLazyAdam
+    dev = torch.device("cuda")
+    pipe = FocfEngine.LOW_WATER + FocfEngine.GROUP + 4          # one GPU: bench.py draws K + W + PIPE batches
+    aged = bench.synth_batches(age, bench.BATCH, bench.N_USERS, bench.N_ITEMS, bench.SEED + 104729, item_dist)
+    timed = bench.synth_batches(K + W + pipe, bench.BATCH, bench.N_USERS, bench.N_ITEMS, bench.SEED, item_dist)
+    U, I = bench.xavier_tables(bench.N_USERS, bench.N_ITEMS, bench.DIM, bench.SEED, dev)
+    eng = FocfEngine(U, I, bench.OBJECTIVE, bench.FAIR_WEIGHT, 5.0)
+    FusedLazyAdam(eng, lr=bench.LR, weight_decay=bench.WD)
+    losses = []
+    for cols, n in ((aged, age), (timed, W + K)):
+        u, i, r, s = (t.to(dev) for t in cols)
+        for k in range(n):
+            loss, _ = eng.forward(u[k], i[k], r[k], s[k])
+            losses.append(loss[:3].clone())
+            eng.backward_adam()
+    eng.flush()
+    eng.check_device_errors()
+    return (torch.stack(losses).double().cpu().numpy(), eng.U.weight.cpu().numpy(), eng.I.weight.cpu().numpy(),
+            timed[0][W + K - 1].numpy())
+
+
+DUMP_FILES = ["item_embedding.npy", "loss_last_step.npy", "loss_running_total.npy", "user_embedding_row_ids.npy",
+              "user_embedding_rows.npy"]
+
+
+def _load_dump(path):
+    import numpy as np
+    files = sorted(os.listdir(path))
+    assert files == DUMP_FILES, files
+    assert sum(os.path.getsize(os.path.join(path, f)) for f in files) <= 64 << 20
+    z = {f[:-4]: np.load(os.path.join(path, f)) for f in files}
+    for name, a in z.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    return z
+
+
+@pytest.mark.parametrize("args", [("--launch", "graph"), ("--launch", "library"), ("--launch", "library", "--item-dist", "grouped")],
+                         ids=["graph", "library", "library_grouped"])
+def test_bench_dump_outputs(tmp_path, args):
+    """`--dump-outputs DIR`: what the timed steps computed up to and including the last one, as float32 / float64 .npy files
+    under 64 MB in all, checked against an eager re-run of the same batches on another launch path: the last step's loss
+    terms, the running total over all 8 + 2 + 12 steps, the whole item table and the dumped user rows (the last batch's
+    among them).  Two runs with the same arguments feed the same inputs, so their dumps agree."""
+    import numpy as np
+    import bench
+    d = _bench("--no-shapes", "--graph-only", "--dump-outputs", str(tmp_path / "a"), *args)
+    assert d["steps"] == 12 and d["ms_per_step"] > 0
+    z = _load_dump(tmp_path / "a")
+    ref_loss, ref_U, ref_I, last_users = _eager_reference("grouped" if "grouped" in args else "uniform")
+    assert ref_loss.shape == (22, 3)
+    tot = z["loss_running_total"]
+    assert tot[3] == 22 and tot[4] == 0, tot                         # every step counted, none NaN
+    last = z["loss_last_step"]
+    assert last.shape == (3,) and last[0] > 1.0 and last[1] > 1.0, last
+    np.testing.assert_allclose(last, ref_loss[-1], rtol=1e-4, atol=1e-6)
+    np.testing.assert_allclose(tot[:3], ref_loss.sum(0), rtol=1e-4, atol=1e-5)
+    assert abs(float(last[0]) - d["config"]["final_loss"]) <= 1e-6    # (the line rounds it to 6 places)
+    ids = z["user_embedding_row_ids"]
+    assert (np.diff(ids) > 0).all() and ids.size >= 65536 and z["user_embedding_rows"].shape == (ids.size, 64)
+    assert np.isin(last_users, ids).all()
+    # (rows no batch touches wobble around zero by Adam steps of ~1e-7: another launch path moves them by a fraction of one)
+    tol = 2e-3 * bench.LR
+    assert z["item_embedding"].shape == ref_I.shape
+    assert float(np.abs(z["item_embedding"] - ref_I).max()) <= tol
+    assert float(np.abs(z["user_embedding_rows"] - ref_U[ids.astype(np.int64)]).max()) <= tol
+    if args[1] == "graph":
+        _bench("--no-shapes", "--graph-only", "--dump-outputs", str(tmp_path / "b"), *args)
+        b = _load_dump(tmp_path / "b")
+        for name in z:
+            np.testing.assert_allclose(z[name], b[name], rtol=1e-4, atol=1e-6 * float(np.abs(b[name]).max()) + 1e-12,
+                                       err_msg=name)
+
+
 def test_bench_nfcf_workload_contract():
     """`--workload nfcf100m` (BASELINE.json configs[4]) at a reduced table size: same JSON contract, NFCF finetune step."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "nfcf100m", "--nfcf-users", "200001",
