@@ -743,7 +743,9 @@ FR_API int fr_nfcf_loss_tail(const float* label, const float* sst, int64_t B, fl
  *                  h2 [B, n2] = the dropped hidden activations, y [B] = the output after its ReLU.  With `label`: out =
  *                  sigmoid(y), dy = d mean(BCE) / dy, bce_part / mm_part [fr_scorer_blocks(B)] (see fr_nfcf_loss_tail);
  *                  `loss` != NULL (no fairness term follows: the pre-training stage): loss[3] = (mean BCE, mean BCE, 0),
- *                  written by the launch's last workgroup -- no fr_nfcf_loss_tail call then.
+ *                  written by the launch's last workgroup -- no fr_nfcf_loss_tail call then.  `ticket` (needed with `loss`)
+ *                  is that launch's arrival counter: one device word, 0 on entry, which the last workgroup returns to 0 --
+ *                  launches that may run at the same time (other streams, other host threads) each need their own.
  *   fr_scorer_bwd  from dy (times gscale[0] when given): dz3 [B], dz2 [B, n2], dz1 [B, n1] = the gradients at the three
  *                  pre-activations, dx0 / dx1 = the input blocks' gradients (either may be NULL: a frozen table), w3part
  *                  [fr_scorer_blocks(B), n2 + 1] = per-workgroup shares of (dW3 | db3), summed by fr_parts_sum.
@@ -760,7 +762,7 @@ FR_API int64_t fr_scorer_blocks(int64_t B);
 FR_API int fr_scorer_fwd(const fr_scorer* s, const float* x0, const float* x1, int64_t B, const int64_t* counter,
                          int64_t* used_out, int64_t* tick_state, float* x0d, float* x1d, float* h1, float* h2, float* y,
                          const float* label, const float* sst, float* out, float* dy, float* bce_part, float* mm_part,
-                         float* loss, void* stream);
+                         float* loss, uint32_t* ticket, void* stream);
 FR_API int fr_scorer_bwd(const fr_scorer* s, const float* dy, const float* gscale, const float* y, const float* h1,
                          const float* h2, int64_t B, const int64_t* used, float* dz1, float* dz2, float* dz3, float* dx0,
                          float* dx1, float* w3part, void* stream);

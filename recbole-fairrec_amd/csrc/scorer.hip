@@ -54,9 +54,8 @@ struct ScFwd {
     const float *label, *sst;
     float *out, *dy, *bce_part, *mm_part;
     float* loss;                 // no fairness term behind this launch: the last workgroup to finish writes loss[3]
+    unsigned* ticket;            // with `loss`: this launch's arrival counter (the caller's zeroed word; back to 0 when it ends)
 };
-
-__device__ unsigned int sc_ticket;   // arrivals of a forward launch that closes its own loss (back to 0 when it ends)
 
 struct ScBwd {
     ScShape s;
@@ -355,9 +354,9 @@ __global__ __launch_bounds__(SC_THREADS) void scorer_fwd_kernel(ScFwd a) {
         __shared__ bool last;
         if (tid == 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this workgroup's partial (a device-scope store) has landed
-            const unsigned t = __hip_atomic_fetch_add(&sc_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             last = t == gridDim.x - 1;
-            if (last) sc_ticket = 0u;
+            if (last) *a.ticket = 0u;
         }
         __syncthreads();
         if (last && tid < 64) {
@@ -604,7 +603,7 @@ extern "C" int64_t fr_scorer_blocks(int64_t B) { return B < 1 ? 0 : (B + SC_ROWS
 extern "C" int fr_scorer_fwd(const fr_scorer* s, const float* x0, const float* x1, int64_t B, const int64_t* counter,
                              int64_t* used_out, int64_t* tick_state, float* x0d, float* x1d, float* h1, float* h2, float* y,
                              const float* label, const float* sst, float* out, float* dy, float* bce_part, float* mm_part,
-                             float* loss, void* stream_) {
+                             float* loss, uint32_t* ticket, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     FR_CHECK_ARG(shape_ok(s), "fr_scorer_fwd: shape not supported (k0 == k1, multiples of 32, k0 + k1 <= 512; n1 <= 128, n2 <= 64, multiples of 32)");
     FR_CHECK_ARG(x0 && x1 && h1 && h2 && y && B >= 1 && B < (1ll << 31) && s->W1 && s->b1 && s->W2 && s->b2 && s->W3 && s->b3,
@@ -613,6 +612,7 @@ extern "C" int fr_scorer_fwd(const fr_scorer* s, const float* x0, const float* x
                                  s->off_h1 % 4 == 0 && s->off_h2 % 4 == 0),
                  "fr_scorer_fwd: dropout needs the counter, the `used` word, the dropped-input buffers and offsets that are multiples of 4");
     FR_CHECK_ARG(!label || (out && dy && bce_part && (!sst || mm_part)), "fr_scorer_fwd: the loss head needs out, dy and the partial buffers");
+    FR_CHECK_ARG(!label || !loss || ticket, "fr_scorer_fwd: closing the loss needs the launch's arrival counter");
     FR_CHECK_ARG((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)x0d | (uintptr_t)x1d |
                    (uintptr_t)s->W1 | (uintptr_t)s->W2 | (uintptr_t)s->W3) & 15) == 0, "fr_scorer_fwd: 16-byte alignment required");
     ScFwd a{};
@@ -623,6 +623,7 @@ extern "C" int fr_scorer_fwd(const fr_scorer* s, const float* x0, const float* x
     a.x0 = x0; a.x1 = x1; a.x0d = x0d; a.x1d = x1d; a.h1 = h1; a.h2 = h2; a.y = y;
     a.label = label; a.sst = label ? sst : nullptr; a.out = out; a.dy = dy; a.bce_part = bce_part; a.mm_part = mm_part;
     a.loss = label ? loss : nullptr;
+    a.ticket = (unsigned*)ticket;
     const int K0 = s->k0 + s->k1;
     const size_t ring = 3 * ((size_t)2 * SC_ROWS * 36 + (size_t)2 * s->n1 * 36);
     const size_t scratch = 4096 + (size_t)SC_ROWS * (s->n1 + 4) + (size_t)SC_ROWS * (s->n2 + 4) + 6 * 1024;

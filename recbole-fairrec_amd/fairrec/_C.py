@@ -213,7 +213,7 @@ _PROTOS = {
     "fr_scorer_blocks": (c_int64, [c_int64]),
     "fr_scorer_fwd": (c_int, [POINTER(FrScorer), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_void_p, c_void_p]),
+                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "fr_scorer_bwd": (c_int, [POINTER(FrScorer), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fr_parts_sum": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),

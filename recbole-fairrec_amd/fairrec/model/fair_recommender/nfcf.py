@@ -103,10 +103,12 @@ class _NfcfFused(torch.autograd.Function):
         y, out, dy = torch.empty(B, **f32), torch.empty(B, **f32), torch.empty(B, **f32)
         part = torch.empty(3 * nblk, **f32)        # bce_part | mm_part
         loss = torch.empty(3, **f32)
+        # closing the loss in the launch: its own arrival counter (a word shared by launches on other streams would mix them)
+        ticket = torch.zeros(1, dtype=torch.int32, device=dev) if item_table is None else None
         _C.check(lib.fr_scorer_fwd(ctypes.byref(d), x0.data_ptr(), x1.data_ptr(), B, _C.ptr(state), _C.ptr(used), _C.ptr(state),
                                    _C.ptr(x0d), _C.ptr(x1d), h1.data_ptr(), h2.data_ptr(), y.data_ptr(), label.data_ptr(),
                                    _C.ptr(sst), out.data_ptr(), dy.data_ptr(), part.data_ptr(), part[nblk:].data_ptr(),
-                                   loss.data_ptr() if item_table is None else None, st), "fr_scorer_fwd")
+                                   loss.data_ptr() if item_table is None else None, _C.ptr(ticket), st), "fr_scorer_fwd")
         iws = item_table._ws if item_table is not None else None
         if iws is not None:     # (without the fairness term the forward launch has closed the loss itself)
             ws = torch.empty(lib.fr_nfcf_loss_workspace_bytes(B), dtype=torch.uint8, device=dev)

@@ -23,7 +23,7 @@ for p in (0.0, 0.2):
     for it in range(5):
         _C.check(lib.fr_scorer_fwd(ctypes.byref(d), x0.data_ptr(), x1.data_ptr(), B, state.data_ptr(), used.data_ptr(), state.data_ptr(),
                                    x0d.data_ptr(), x1d.data_ptr(), h1.data_ptr(), h2.data_ptr(), y.data_ptr(), label.data_ptr(), sst.data_ptr(),
-                                   out.data_ptr(), dy.data_ptr(), part.data_ptr(), part[nblk:].data_ptr(), None, _C.current_stream()), "fwd")
+                                   out.data_ptr(), dy.data_ptr(), part.data_ptr(), part[nblk:].data_ptr(), None, None, _C.current_stream()), "fwd")
         torch.cuda.synchronize()
     buf = np.zeros(64, dtype=np.uint64)
     assert raw.fr_debug_scorer_trace(buf.ctypes.data_as(ctypes.c_void_p)) == 0

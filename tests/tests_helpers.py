@@ -16,3 +16,18 @@ def sort_segments(idx, n_rows):
                                        _C.current_stream()), "sort")
     torch.cuda.synchronize()
     return perm.cpu().numpy(), seg_start.cpu().numpy(), seg_row.cpu().numpy(), int(nseg), int(err)
+
+
+class NfcfDataset:
+    """The part of a dataset NFCF's constructor and reset_params read: row counts and the user feature table."""
+
+    def __init__(self, n_users, n_items, gender):
+        from fairrec.data.interaction import Interaction
+        self._n = {"user_id": n_users, "item_id": n_items}
+        self._uf = Interaction({"user_id": torch.arange(n_users), "gender": torch.from_numpy(gender)})
+
+    def num(self, f):
+        return self._n[f]
+
+    def get_user_feature(self):
+        return self._uf
