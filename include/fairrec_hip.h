@@ -962,6 +962,29 @@ FR_API int fr_prof_read(int kind, double* total_ms, int64_t* count);
  * work / total_ms is the rate bench.py holds against the MFMA / HBM peak. */
 FR_API int fr_prof_read_work(int kind, double* work);
 
+/*
+ * Dynamic negative sampling (`neg_sampling: {uniform: 1, dynamic: M}`): keep the highest-scoring of M candidates per slot.
+ * scores / cand are [M, cols] row-major; out[c] = cand[r*cols + c] with r = the first index of the maximum of
+ * scores[:, c] -- torch.max(dim=0) semantics: the lowest index among equal maxima, a NaN beats every number and the
+ * first NaN wins.
+ */
+FR_API int fr_dyn_neg_select(const float* scores, const int64_t* cand, int64_t cols, int32_t M, int64_t* out, void* stream);
+
+/* The same for a dot-product model (PFCN_PMF / PFCN_BiasedMF predict), scores computed in the kernel: candidate r of output
+ * column c = j*n + i (j < num) is cand[(r*num + j)*n + i], its score
+ *     sigmoid(((dot(user_rows[i,:], item row) + user_bias[i]) + item bias) + *global_bias)
+ * with the item (and item bias) rows read as of the tables' step, as fr_table_gather reads them; each bias term is
+ * skipped when its pointer is NULL.  An id outside the item table sets FR_DEV_ERR_INDEX_RANGE in *err_flag. */
+FR_API int fr_dyn_neg_dot_select(const fr_table* item_t, const fr_adam* item_adam, const fr_table* item_bias_t,
+                                 const fr_adam* item_bias_adam, const float* user_rows, const float* user_bias,
+                                 const float* global_bias, const int64_t* cand, int64_t n, int32_t num, int32_t M,
+                                 int64_t* out, uint32_t* err_flag, void* stream);
+/* The [num*M*n] scores fr_dyn_neg_dot_select picks from, in cand's order (for checking them). */
+FR_API int fr_dyn_neg_dot_scores(const fr_table* item_t, const fr_adam* item_adam, const fr_table* item_bias_t,
+                                 const fr_adam* item_bias_adam, const float* user_rows, const float* user_bias,
+                                 const float* global_bias, const int64_t* cand, int64_t n, int32_t num, int32_t M,
+                                 float* scores, uint32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

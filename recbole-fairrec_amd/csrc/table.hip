@@ -35,22 +35,9 @@ __device__ __forceinline__ void gather_row(const TableV& T_, const AdamC& c, con
                                            float* __restrict__ out, uint32_t* err, const long long j, const int lane) {
     const TableV T = resolved(T_);
     if (j >= M) return;
-    long long r = idx[j];
-    if (r < 0 || r >= T.n_rows) {
-        if (lane == 0 && err) atomicOr(err, FR_DEV_ERR_INDEX_RANGE);
-        r = 0;
-    }
-    const int row = uniform((int)r);
-    const int D = T.D;
-    const int t0 = uniform(T.last[row]);
-    RowFrag<E> p, m, v;
-    load_row<E>(p, T.p + (size_t)row * D, D, lane);
-    if (t0 < T.step) {
-        load_row<E>(m, T.m + (size_t)row * D, D, lane);
-        load_row<E>(v, T.v + (size_t)row * D, D, lane);
-        replay<E>(p, m, v, t0, T.step, c, lane);
-    }
-    store_row<E>(p, out + (size_t)j * D, D, lane);
+    RowFrag<E> p;
+    row_at_step<E>(T, c, idx[j], p, err, lane);
+    store_row<E>(p, out + (size_t)j * T.D, T.D, lane);
 }
 
 template <int E>

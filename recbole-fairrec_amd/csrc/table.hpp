@@ -5,6 +5,28 @@
 
 namespace fr {
 
+// Row `r` of a resolved table as of its step T.step, in registers (d = lane + 64*e): the parameters, caught up through
+// the zero-gradient steps it has not seen (replay of the lazy Adam update).  An id outside [0, n_rows) sets
+// FR_DEV_ERR_INDEX_RANGE and reads row 0.  fr_table_gather and fr_dyn_neg_dot_select read rows through this.
+template <int E>
+__device__ __forceinline__ void row_at_step(const TableV& T, const AdamC& c, long long r, RowFrag<E>& p, uint32_t* err,
+                                            const int lane) {
+    if (r < 0 || r >= T.n_rows) {
+        if (lane == 0 && err) atomicOr(err, FR_DEV_ERR_INDEX_RANGE);
+        r = 0;
+    }
+    const int row = uniform((int)r);
+    const int D = T.D;
+    const int t0 = uniform(T.last[row]);
+    RowFrag<E> m, v;
+    load_row<E>(p, T.p + (size_t)row * D, D, lane);
+    if (t0 < T.step) {
+        load_row<E>(m, T.m + (size_t)row * D, D, lane);
+        load_row<E>(v, T.v + (size_t)row * D, D, lane);
+        replay<E>(p, m, v, t0, T.step, c, lane);
+    }
+}
+
 // Gradient row of one distinct row of a batch: sum of the contributions of its members [j0, j1) of the sorted list in
 // ascending batch position (the reference's accumulation order); b0 = perm[j0] is known already.
 //   coef != nullptr : contribution of member b = coef[b] * other[b,:]   (rank-1 form: MF models)

@@ -248,6 +248,11 @@ _PROTOS = {
     "fr_linear_bwd_input_bnstats": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                             c_void_p, c_size_t, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),
     "fr_rowdot_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "fr_dyn_neg_select": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "fr_dyn_neg_dot_select": (c_int, [POINTER(FrTable), POINTER(FrAdam), POINTER(FrTable), POINTER(FrAdam), c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "fr_dyn_neg_dot_scores": (c_int, [POINTER(FrTable), POINTER(FrAdam), POINTER(FrTable), POINTER(FrAdam), c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_rowdot_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_bpr_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "fr_bpr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -64,10 +64,15 @@ class TrainDataLoader(AbstractDataLoader):
         self.uid_field, self.iid_field = dataset.uid_field, dataset.iid_field
         self.neg_sample_args = config['train_neg_sample_args'] or {'strategy': 'none'}
         self.times = 1
+        self.candidate_num = None        # M of `neg_sampling: {..., dynamic: M}`; None = plain negative sampling
+        self.model = None
         if sampler is not None and self.neg_sample_args['strategy'] == 'by':
-            if self.neg_sample_args.get('dynamic', 'none') != 'none':
-                raise NotImplementedError('dynamic negative sampling is not on the device path')
             self.neg_sample_num = int(self.neg_sample_args['by'])
+            dynamic = self.neg_sample_args.get('dynamic', 'none')
+            if dynamic != 'none':
+                if isinstance(dynamic, bool) or int(dynamic) != dynamic or int(dynamic) < 1:
+                    raise ValueError(f'neg_sampling dynamic: [{dynamic}] should be an integer >= 1')
+                self.candidate_num = int(dynamic)
             self.dl_format = config['MODEL_INPUT_TYPE']
             from ..utils.enum_type import InputType
             if self.dl_format == InputType.POINTWISE:
@@ -84,11 +89,56 @@ class TrainDataLoader(AbstractDataLoader):
             self.sampler = None
         _prejoin(self.dataset)
 
+    @property
+    def dynamic(self):
+        """The loader scores candidate negatives with the model being trained: a batch depends on the parameters of the
+        steps before it (a consumer must not fetch it ahead of the preceding optimizer step)."""
+        return self.sampler is not None and self.candidate_num is not None
+
+    def get_model(self, model):
+        """abstract_dataloader.py `get_model`: the model whose `predict` ranks the candidates of dynamic negative sampling
+        (the trainer hands it over at the start of `fit`)."""
+        self.model = model
+
+    def _dynamic_negatives(self, inter_feat):
+        """abstract_dataloader.py `_neg_sampling`, dynamic branch: draw num*M candidates per row, score them with the model
+        in eval mode and keep, per negative slot, the candidate with the highest score (torch.max(dim=0): first maximum,
+        NaN first).  Block r*num + j of the draws holds candidate r of slot j, as in the reference's reshape(M, -1).
+
+        The scoring pass runs without autograd: the ids are detached in the reference, and a lookup with autograd on would
+        record a pending batch in the engine's lazy tables for the coming optimizer step.  A model with a fused scorer
+        (`dyn_neg_select`, the dot-product PFCN models) returns the ids itself; any other goes through its `predict` on
+        the repeated interaction and fr_dyn_neg_select."""
+        model = self.model
+        if model is None:
+            raise RuntimeError('dynamic negative sampling ranks candidates with the model being trained: '
+                               'call get_model(model) on the training loader before iterating it')
+        M, num = self.candidate_num, self.neg_sample_num
+        dev = inter_feat[self.uid_field].device
+        cand = self.sampler.sample_by_user_ids(inter_feat[self.uid_field], inter_feat[self.iid_field], num * M).to(dev)
+        model.eval()
+        try:
+            with torch.no_grad():
+                fused = getattr(model, 'dyn_neg_select', None)
+                neg = fused(inter_feat, cand, num, M) if fused is not None else None
+                if neg is None:
+                    from ..functional import dyn_neg_select
+                    inter = inter_feat.repeat(num * M)
+                    inter.update(Interaction({self.iid_field: cand}))
+                    scores = model.predict(inter).reshape(M, -1)
+                    neg = dyn_neg_select(scores, cand.view(M, -1))
+        finally:
+            model.train()
+        return neg
+
     def _neg_sampling(self, inter_feat):
         from ..utils.enum_type import InputType
-        neg = self.sampler.sample_by_user_ids(inter_feat[self.uid_field], inter_feat[self.iid_field], self.neg_sample_num)
         dev = inter_feat[self.uid_field].device
-        neg = neg.to(dev)
+        if self.candidate_num is not None:
+            neg = self._dynamic_negatives(inter_feat)
+        else:
+            neg = self.sampler.sample_by_user_ids(inter_feat[self.uid_field], inter_feat[self.iid_field],
+                                                  self.neg_sample_num).to(dev)
         if self.dl_format == InputType.PAIRWISE:                 # abstract_dataloader.py:182-188
             out = inter_feat.repeat(self.times)
             out.update(Interaction({self.neg_item_id: neg}))

@@ -2,6 +2,8 @@
 backward are single kernel launches through the C ABI; torch only chains them."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _C
@@ -484,3 +486,44 @@ class RowGather(torch.autograd.Function):
         _C.check(_C.lib().fr_row_scatter_sum(g.data_ptr(), idx.data_ptr(), M, N, D, dX.data_ptr(), ws.data_ptr(), ws.numel(),
                                              _C.ptr(ctx.err), _C.current_stream()), "fr_row_scatter_sum")
         return dX, None, None
+
+
+def dyn_neg_select(scores: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """`cand[argmax(scores, 0), range(cols)]` of [M, cols] scores and candidate ids -- the pick of dynamic negative sampling
+    (abstract_dataloader.py `_neg_sampling`: `torch.max(scores, dim=0)[1]` then the advanced index), in one launch
+    (fr_dyn_neg_select): the first maximum wins ties, a NaN wins, the first NaN among several."""
+    scores = scores.to(torch.float32).contiguous()
+    cand = cand.to(torch.int64).contiguous()
+    if scores.dim() != 2 or cand.shape != scores.shape:
+        raise ValueError(f'dyn_neg_select: scores {tuple(scores.shape)} and candidates {tuple(cand.shape)} must be the same [M, cols]')
+    M, cols = scores.shape
+    out = torch.empty(cols, dtype=torch.int64, device=scores.device)
+    _C.check(_C.lib().fr_dyn_neg_select(scores.data_ptr(), cand.data_ptr(), cols, M, out.data_ptr(), _C.current_stream()),
+             "fr_dyn_neg_select")
+    return out
+
+
+def dyn_neg_dot_select(item_table, item_hyper, user_rows, cand, num, M, err_flag, item_bias=None, user_bias=None,
+                       global_bias=None, scores_only=False):
+    """fr_dyn_neg_dot_select: of the M candidates cand[(r*num + j)*n + i] of column j*n + i keep the one with the highest
+    sigmoid(((user_rows[i] . item row + user_bias[i]) + item bias) + global_bias) -- PFCNBase.predict's values, the item rows
+    read as of the lazy table's step, never materialised.  `item_bias` = (LazyTable, AdamHyper) or None.  `scores_only`: the
+    [M*num*n] scores in cand's order instead (fr_dyn_neg_dot_scores)."""
+    user_rows = user_rows.to(torch.float32).contiguous()
+    cand = cand.to(torch.int64).contiguous()
+    n = user_rows.shape[0]
+    if user_rows.dim() != 2 or user_rows.shape[1] != item_table.dim or cand.numel() != n * int(num) * int(M):
+        raise ValueError('dyn_neg_dot_select: user rows [n, D] against [M*num*n] candidates of a D-wide table')
+    ub = user_bias.to(torch.float32).contiguous().view(-1) if user_bias is not None else None
+    gb = global_bias.detach().to(torch.float32).contiguous() if global_bias is not None else None
+    bt, bh = (item_bias[0].c(), item_bias[1].c()) if item_bias is not None else (None, None)
+    it = item_table.c()
+    dev = user_rows.device
+    if scores_only:
+        out, fn, name = torch.empty(cand.numel(), dtype=torch.float32, device=dev), _C.lib().fr_dyn_neg_dot_scores, "fr_dyn_neg_dot_scores"
+    else:
+        out, fn, name = torch.empty(n * int(num), dtype=torch.int64, device=dev), _C.lib().fr_dyn_neg_dot_select, "fr_dyn_neg_dot_select"
+    _C.check(fn(ctypes.byref(it), ctypes.byref(item_hyper.c()), ctypes.byref(bt) if bt is not None else None,
+                ctypes.byref(bh) if bh is not None else None, user_rows.data_ptr(), _C.ptr(ub), _C.ptr(gb), cand.data_ptr(),
+                n, int(num), int(M), out.data_ptr(), _C.ptr(err_flag), _C.current_stream()), name)
+    return out

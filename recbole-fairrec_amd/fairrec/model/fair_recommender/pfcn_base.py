@@ -261,6 +261,37 @@ class PFCNBase(FairRecommender):
     def _predict_score(self, ue, ie):
         return RowDot.apply(ue, ie).unsqueeze(-1)
 
+    def dyn_neg_select(self, interaction, cand, num, M):
+        """Dynamic negative sampling (TrainDataLoader._dynamic_negatives) for a dot-product model on one device: of the M
+        candidates of each negative slot the id `predict` scores highest, in one launch (fr_dyn_neg_dot_select) -- the
+        user rows are looked up once for the n batch rows instead of for the num*M*n repeated ones, and the candidates'
+        rows are read in the kernel instead of gathered into a [num*M*n, D] buffer.  Same values as predict() on the
+        repeated interaction, so the same ids.  None = no fused path for this model: the loader goes through predict()."""
+        if self.filter_mode != 'none':
+            # predict() without an attribute subset: the reference's filters have none to pick (pfcn_biasedmf.py predict,
+            # `sst_list=None`), so the reference's dynamic branch stops there too
+            raise NotImplementedError(f'dynamic negative sampling with filter_mode [{self.filter_mode}]: predict() is called '
+                                      'without sst_list, which the filtered PFCN models need')
+        cls = type(self)
+        if (self.shard is not None or cls._predict_score is not PFCNBase._predict_score
+                or cls._item_tower is not PFCNBase._item_tower or cls._user_tower is not PFCNBase._user_tower
+                or cls.predict is not PFCNBase.predict):
+            return None
+        from ...functional import dyn_neg_dot_select
+        eng = self.hip_engine()
+        if type(eng) is not GenericEngine:      # row-sharded / replicated engines: the generic path
+            return None
+        user = interaction[self.USER_ID]
+        with torch.no_grad():
+            ue = eng.lookup(self._utab, user)
+            ub = ib = gb = None
+            if self.biased:
+                ub = eng.lookup("user_bias.weight", user)
+                ib = (eng._tables["item_bias.weight"], eng._hyper("item_bias.weight"))
+                gb = self.global_bias
+            return dyn_neg_dot_select(eng._tables[self._itab], eng._hyper(self._itab), ue, cand, num, M, eng.err_flag,
+                                      item_bias=ib, user_bias=ub, global_bias=gb)
+
     def get_sst_embed(self, user_data, sst_list=None):
         ret = {}
         idx = torch.arange(1, self.n_users)

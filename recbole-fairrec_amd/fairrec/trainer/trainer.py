@@ -101,6 +101,13 @@ class Trainer(AbstractTrainer):
             graphs[key] = GraphedStep(eng, self.optimizer, loss_fn)
         return graphs[key]
 
+    def _give_model(self, train_data):
+        """trainer.py `fit`: `train_data.get_model(self.model)` when the training negatives are dynamic (the loader ranks
+        candidates with the model being trained)."""
+        args = self.config['train_neg_sample_args'] or {}
+        if args.get('dynamic', 'none') != 'none' and hasattr(train_data, 'get_model'):
+            train_data.get_model(self.model)
+
     def _train_epoch(self, train_data, epoch_idx, loss_func=None, show_progress=False):
         self.model.train()
         loss_func = loss_func or self.model.calculate_loss
@@ -154,24 +161,34 @@ class Trainer(AbstractTrainer):
             return self._epoch_loss(True, 0)
         it = iter(train_data)
         # dataloader look-ahead: a model that can use it (FOCF sorts the coming batches' ids ahead, several per launch)
-        # says how many batches it wants announced
+        # says how many batches it wants announced.  None with a loader whose batches depend on the parameters (dynamic
+        # negative sampling scores the candidates of batch k+1 with the model after step k): the next batch is fetched only
+        # once the current step is done.
+        lazy = bool(getattr(train_data, 'dynamic', False))
         depth = max(1, int(getattr(self.model, 'PREFETCH', 1))) if hint is not None else 1
+        cap = 1 if lazy else depth + 1
         queue = collections.deque()
 
         done = []
 
         def fill():
-            while not done and len(queue) < depth + 1:
+            while not done and len(queue) < cap:
                 b = next(it, None)
                 if b is None:
                     done.append(True)            # a recbole-style loader rewinds after StopIteration: never ask again
                     return
                 queue.append(b.to(self.device))
 
-        fill()
-        while queue:
-            interaction = queue.popleft()
+        if not lazy:
             fill()
+        while True:
+            if lazy:
+                fill()                                 # after the previous step's optimizer.step()
+            if not queue:
+                break
+            interaction = queue.popleft()
+            if not lazy:
+                fill()
             if hint is not None:
                 hint(*queue)                           # lets the model start the coming batches' index sorts early
             if graphed is not None:
@@ -296,6 +313,7 @@ class Trainer(AbstractTrainer):
     def fit(self, train_data, valid_data=None, verbose=True, saved=True, show_progress=False, callback_fn=None):
         """reference trainer.py:332-418: returns (best_valid_score, best_valid_result)."""
         self._train_data_for_eval = train_data                        # eval_collector.data_collect(train_data), :341
+        self._give_model(train_data)
         if saved and self.start_epoch >= self.epochs:
             self._save_checkpoint(-1, verbose=verbose)
         for epoch_idx in range(self.start_epoch, self.epochs):
@@ -658,6 +676,7 @@ class FairGoTrainer(PFCNTrainer):
         self.optimizer = self.optimizer_pretrain
         self._pretrain_file_written = False
         self._train_data_for_eval = train_data                        # eval_collector.data_collect(train_data), :621
+        self._give_model(train_data)
         for epoch_idx in range(self.start_epoch, self.pretrain_epochs):
             t0 = time()
             loss = self._train_epoch_with_mask(train_data, epoch_idx, self.model.calculate_loss, None)
