@@ -858,7 +858,11 @@ FR_API size_t fr_sample_negatives_workspace_bytes(int64_t total);
  * calls is resolved SPECULATIVELY -- the stream's accepted values generated once, every call laid out as if none before it
  * had collided with its used-set, the rare colliding call resolved round by round and the rest shifted (csrc/sampler.hip) --
  * instead of call by call: the same values and the same generator state, 30 ms -> ~1.5 ms for the ~2 800 calls of an
- * evaluation batch.  With fr_sample_negatives_workspace_bytes(max_call) bytes the calls run one after the other. */
+ * evaluation batch.  With fr_sample_negatives_workspace_bytes(max_call) bytes the calls run one after the other.  The host
+ * can not read `total` (call_offsets[n_calls] is device memory), so it lays the workspace out for the largest total it holds:
+ * a workspace of this size for a smaller total than the sequence's -- room for n_calls values or more but fewer than the
+ * sequence draws -- is accepted, and the calls then run one after the other from the incoming state (the same values and
+ * state, at the call-by-call speed).  ws_bytes must also be >= fr_sample_negatives_workspace_bytes(max_call). */
 FR_API size_t fr_sample_negatives_calls_workspace_bytes(int64_t total, int64_t max_call);
 FR_API int fr_sample_negatives(uint32_t* state, int64_t low, int64_t high, const int64_t* key_ids, int64_t n_keys,
                                int32_t num, const int64_t* used_indptr, const int32_t* used_items, int64_t n_users,

@@ -200,7 +200,8 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_negatives_kernel(
 // far; the first call with a collision is found in parallel, everything before it is final, that one call is resolved round
 // by round exactly as the sequential kernel does, D grows by what it consumed beyond its size, and the search resumes behind
 // it.  The generator state handed back is the block of the last consumed raw word and the position behind it: the same
-// values, the same stream position as call-by-call consumption (tests/test_sampler_hip.py holds both forms against numpy).
+// values, the same stream position as call-by-call consumption (tests/test_sampler_calls_hip.py holds both forms against numpy,
+// path by path).
 // If the slack does not suffice (a pathological collision rate), nothing has been published yet and the sequence runs call by
 // call from the start.
 static constexpr int CALLS_WINDOW = 1 << 16;      // positions examined per search for the next colliding call
@@ -380,9 +381,12 @@ __global__ __launch_bounds__(64) void sample_calls_temper_kernel(uint32_t span, 
 // (P) every position of the sequence, in parallel over the chip: its call, and for each shift d < CALLS_SHIFTS whether the
 // accepted value it would take under that shift (acc_val[p + d]) lies in its user's used-set -- one bit per shift.  The
 // sequential part (B) then finds "the first position that collides under the current shift" by reading one word per position.
+// hmask and pos_call hold lo_t positions (the capacity the workspace was laid out for): a longer sequence is left to (B)'s
+// call-by-call fallback.
 static constexpr int CALLS_SHIFTS = 32;
 __global__ __launch_bounds__(256) void sample_calls_hits_kernel(long long low, const int64_t* __restrict__ call_keys,
                                                                 const int64_t* __restrict__ call_offsets, long long n_calls,
+                                                                long long lo_t,
                                                                 const int64_t* __restrict__ used_indptr,
                                                                 const int32_t* __restrict__ used_items, long long n_users,
                                                                 const uint32_t* __restrict__ acc_val,
@@ -390,7 +394,7 @@ __global__ __launch_bounds__(256) void sample_calls_hits_kernel(long long low, c
                                                                 int32_t* __restrict__ pos_call, uint32_t* err) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = call_offsets[n_calls];
-    if (p >= total) return;
+    if (p >= total || p >= lo_t) return;
     long long a = 0, b = n_calls - 1;      // the call of position p: the largest c with call_offsets[c] <= p
     while (a < b) {
         const long long mid = (a + b + 1) >> 1;
@@ -417,7 +421,7 @@ __global__ __launch_bounds__(256) void sample_calls_hits_kernel(long long low, c
 // (B) ONE workgroup: the calls in order, everything before the next colliding position final
 __global__ __launch_bounds__(SAMPLER_THREADS) void sample_calls_fast_kernel(
     uint32_t* __restrict__ state, long long low, uint32_t span, uint32_t mask, const int64_t* __restrict__ call_keys,
-    const int64_t* __restrict__ call_offsets, long long n_calls, const int64_t* __restrict__ used_indptr,
+    const int64_t* __restrict__ call_offsets, long long n_calls, long long lo_t, const int64_t* __restrict__ used_indptr,
     const int32_t* __restrict__ used_items, long long n_users, int64_t* __restrict__ out, const uint32_t* __restrict__ acc_val,
     const uint32_t* __restrict__ acc_raw, const uint32_t* __restrict__ snap, const long long* __restrict__ n_acc_in,
     const uint32_t* __restrict__ hmask, const int32_t* __restrict__ pos_call, int32_t* list_a, int32_t* list_b, uint32_t* err) {
@@ -433,7 +437,7 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_calls_fast_kernel(
     const long long n_acc = n_acc_in[0];
     __syncthreads();
     long long D = 0, p0 = 0;      // positions before p0 are final; D = accepted values consumed beyond the positions so far
-    bool over = total + D > n_acc;
+    bool over = total > lo_t || total + D > n_acc;      // (more positions than the layout holds: call by call)
     while (p0 < total && !over) {
         const long long pe = p0 + CALLS_WINDOW < total ? p0 + CALLS_WINDOW : total;
         if (t == 0) s_first = pe;
@@ -628,8 +632,9 @@ extern "C" int fr_sample_negatives_calls(uint32_t* state, int64_t low, int64_t h
     FR_CHECK_ARG(used_indptr && used_items && n_users >= 1 && ws, "fr_sample_negatives_calls: used-set arguments");
     // With a workspace of fr_sample_negatives_calls_workspace_bytes(total, max_call) a sequence of many calls is resolved
     // speculatively (sample_calls_fast_kernel); `total` is not known to the host without a synchronisation, so the caller says
-    // how much room there is and the size is read back from it: the layout for `total_hint` = the largest total the workspace
-    // holds is what the kernel uses (it stops generating at its capacity, and falls back call by call if that is too little).
+    // how much room there is and the size is read back from it: the layout for lo_t = the largest total the workspace holds
+    // is what the kernels use (they stop generating at its capacity, mark hits for its first lo_t positions only, and fall
+    // back call by call if the total exceeds lo_t or the accepted values fall short).
     static const bool fast_env = !(getenv("FAIRREC_SAMPLER_CALLS_FAST") && atoi(getenv("FAIRREC_SAMPLER_CALLS_FAST")) == 0);
     if (fast_env && n_calls >= 16 && high - 1 - low > 0) {
         // the largest `total` whose layout fits the workspace (bisection on the monotone size function)
@@ -657,11 +662,13 @@ extern "C" int fr_sample_negatives_calls(uint32_t* state, int64_t low, int64_t h
                       (const uint32_t*)(w + off[2]), (long long*)(w + off[5]), (uint32_t*)(w + off[8]), (uint32_t*)(w + off[0]),
                       (uint32_t*)(w + off[1]));
             FR_LAUNCH(prof, sample_calls_hits_kernel, dim3((unsigned)((lo_t + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
-                      (long long)low, call_keys, call_offsets, (long long)n_calls, used_indptr, used_items, (long long)n_users,
+                      (long long)low, call_keys, call_offsets, (long long)n_calls, (long long)lo_t, used_indptr, used_items,
+                      (long long)n_users,
                       (const uint32_t*)(w + off[0]), (const long long*)(w + off[5]), (uint32_t*)(w + off[6]), (int32_t*)(w + off[7]),
                       err_flag);
             FR_LAUNCH(prof, sample_calls_fast_kernel, dim3(1), dim3(SAMPLER_THREADS), 0, (hipStream_t)stream_, state, (long long)low,
-                      span, mask, call_keys, call_offsets, (long long)n_calls, used_indptr, used_items, (long long)n_users, out,
+                      span, mask, call_keys, call_offsets, (long long)n_calls, (long long)lo_t, used_indptr, used_items,
+                      (long long)n_users, out,
                       (const uint32_t*)(w + off[0]), (const uint32_t*)(w + off[1]), (const uint32_t*)(w + off[2]),
                       (const long long*)(w + off[5]), (const uint32_t*)(w + off[6]), (const int32_t*)(w + off[7]),
                       (int32_t*)(w + off[3]), (int32_t*)(w + off[4]), err_flag);

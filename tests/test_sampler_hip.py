@@ -115,10 +115,14 @@ def test_sampler_matches_oracle_on_adversarial_used_sets():
     assert st[2] == ors.pos
 
 
-def test_full_size_batch_properties():
+@pytest.mark.parametrize("num", [1, 4])
+def test_full_size_batch_properties(num):
     """BASELINE sizes (B = 8192, 1,000,001 items, 1,000,001 users x 20 interactions): every negative is in range and
-    outside its user's used-set; the stream position matches numpy when no rejection by used-set occurs."""
+    outside its user's used-set, and -- id for id, with the generator state afterwards -- what numpy's own RandomState
+    draws through sample_by_key_ids (tests/sampler_ref.py).  num = 4: the dynamic-negative candidate shape (num * M per
+    row)."""
     from fairrec.sampler import Sampler
+    from sampler_ref import by_key_ids_ref
     g = torch.Generator().manual_seed(0)
     user_num = item_num = 1_000_001
     u = torch.arange(1, user_num).repeat_interleave(20)
@@ -126,14 +130,17 @@ def test_full_size_batch_properties():
     rs = _rs(2020)
     sampler = Sampler("train", _DS(user_num, item_num, u.numpy(), i.numpy()), device="cuda", random_state=rs).set_phase("train")
     users = torch.randint(1, user_num, (8192,), generator=g)
-    neg = sampler.sample_by_user_ids(users.cuda(), None, 1).cpu()
+    neg = sampler.sample_by_user_ids(users.cuda(), None, num).cpu()
     assert int(neg.min()) >= 1 and int(neg.max()) < item_num
     key = u * item_num + i
-    assert not torch.isin(users * item_num + neg, key).any()
-    np.random.seed(2020)
-    ref = np.random.randint(1, item_num, 8192)
-    same = neg.numpy() == ref
-    assert same.mean() > 0.99          # the rare used-set hits are re-drawn from later in the stream
+    assert not torch.isin(users.repeat(num) * item_num + neg, key).any()
+    nrs = np.random.RandomState(2020)
+    indptr, items, _ = sampler.used_ids
+    ref = by_key_ids_ref(nrs, 1, item_num, users.numpy(), num, (indptr.cpu().numpy(), items.cpu().numpy()))
+    np.testing.assert_array_equal(neg.numpy(), ref)
+    st, want = rs.get_state(), nrs.get_state()
+    np.testing.assert_array_equal(st[1], want[1])
+    assert st[2] == want[2]
 
 
 @pytest.mark.parametrize("model,pairwise", [("PFCN_PMF", True), ("NFCF", False)])
@@ -353,9 +360,11 @@ def test_device_randperm_speculation_is_dropped_when_somebody_else_draws():
 def test_call_sequence_of_an_evaluation_batch_at_baseline_sizes():
     """The evaluation loader's draws at the sizes of BASELINE configs[1] -- 100 001 items, 1 000 001 users with 20 interactions
     each, a batch of 2 800 users x 100 negatives per positive (280 k values, ~290 calls with a collision among them): the
-    speculative form against the SAME calls issued one by one on a twin generator (the single-call kernel, itself held to
-    numpy by the tests above): every id, and the generator state afterwards."""
+    speculative form against numpy's own RandomState making the same consecutive calls (tests/sampler_ref.py), and against
+    the SAME calls issued one by one on a twin generator (the single-call kernel): every id, and the generator state
+    afterwards."""
     from fairrec.sampler import Sampler
+    from sampler_ref import calls_ref
     g = torch.Generator().manual_seed(1)
     user_num, item_num, n_calls = 1_000_001, 100_001, 2800
     u = torch.arange(1, user_num).repeat_interleave(20)
@@ -373,6 +382,12 @@ def test_call_sequence_of_an_evaluation_batch_at_baseline_sizes():
     a, b = rs.get_state(), rs1.get_state()
     np.testing.assert_array_equal(a[1], b[1])
     assert a[2] == b[2]
+    nrs = np.random.RandomState(404)
+    want, consumed, _ = calls_ref(nrs, 1, item_num, keys.numpy(), counts.numpy(), (indptr.cpu().numpy(), items.cpu().numpy()))
+    assert (consumed > counts.numpy()).any()           # (some call collides)
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    np.testing.assert_array_equal(a[1], nrs.get_state()[1])
+    assert a[2] == nrs.get_state()[2]
     # ... and no id is one its user has seen
     owner = torch.repeat_interleave(keys, counts).cuda()
     key_used = (u * item_num + i).cuda()
