@@ -86,13 +86,33 @@ typedef struct fr_table {
  *   scalars[4*j+3] = (float)(eps / (step_size_j * k1))                         k2 = (1-beta2)*wd^2 (0 when wd = 0)
  * for j = 1..cap ; entry 0 unused.  Entries 2,3 let a replayed step (gradient = wd*p only) run on scaled moments.
  * Steps beyond `cap` use entry `cap` (the host guarantees the scalars have saturated there).
+ *
+ * `learner` selects the optimizer (torch.optim.<Learner> with torch's defaults and coupled L2 weight decay; the reference's
+ * trainer passes only lr and weight_decay).  The same struct carries every learner; per learner:
+ *   FR_LEARNER_ADAM    as above.  State: fr_table.m = exp_avg, fr_table.v = exp_avg_sq.
+ *   FR_LEARNER_SGD     momentum 0.  scalars[4j] = (float)lr_j, scalars[4j+1] = (float)(-lr_j * wd) (the coefficient of the
+ *                      one fma of a replayed step, p <- p + k_j*p), 4j+2..3 = 0.  beta1, beta2, eps unused.
+ *                      State: none -- fr_table.m and .v may be NULL and are never read or written.
+ *   FR_LEARNER_ADAGRAD lr_decay 0, initial_accumulator_value 0.  scalars[4j] = (float)(lr / (1 + (j-1)*lr_decay)) (clr),
+ *                      4j+1..3 = 0.  eps = 1e-10 by default.  beta1, beta2 unused.
+ *                      State: fr_table.m = sum; fr_table.v may be NULL and is never read or written.
+ *   FR_LEARNER_RMSPROP momentum 0, not centered.  scalars[4j] = (float)lr_j, 4j+1..3 = 0.  beta2 = alpha (0.99), eps = 1e-8.
+ *                      beta1 unused.  State: fr_table.m = square_avg; fr_table.v may be NULL and is never touched.
+ * A zero-data-gradient step is the identity for SGD and Adagrad with weight_decay = 0: their tables are never replayed or
+ * swept (rows outside a batch do not change), and fr_table_flush launches nothing.  RMSprop with weight_decay = 0 only
+ * decays square_avg.  The FOCF entry points (fr_focf_*) run Adam only and refuse any other learner with FR_EINVAL.
  */
+#define FR_LEARNER_ADAM 0
+#define FR_LEARNER_SGD 1
+#define FR_LEARNER_ADAGRAD 2
+#define FR_LEARNER_RMSPROP 3
 typedef struct fr_adam {
     const float* scalars;  /* device, float[4*(cap+1)] */
     int32_t cap;
-    int32_t reserved_;
+    int32_t learner;       /* FR_LEARNER_*; 0 = Adam */
     double weight_decay, beta1, beta2, eps; /* doubles: torch derives (1 - beta) in double before the fp32 cast */
 } fr_adam;
+typedef fr_adam fr_optim;   /* the same struct under a learner-neutral name */
 
 FR_API int fr_version(void);
 FR_API const char* fr_last_error(void);

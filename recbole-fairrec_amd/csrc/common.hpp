@@ -341,4 +341,155 @@ __device__ __forceinline__ void replay2(RowFrag<E>& p0, RowFrag<E>& m0, RowFrag<
     replay_n<E, 2>(pp, mm, vv, from, to, c);
 }
 
+// ---- learner policies (fr_adam.learner) ------------------------------------------------------------------------------
+// Each policy names the state arrays its learner keeps (the kernels never touch the others: a table may have them NULL),
+// one step on one element with a data gradient (`elem`, scalars s0 / s1 = entries 4j / 4j+1 of the step table), the
+// wave-uniform test for "a zero-data-gradient step is the identity on (p, state)" (then nothing is replayed or swept) and
+// the one for "... leaves p as it is" (`p_invariant`: a read-only gather then needs the parameters alone).
+// AdamC carries the constants of every learner: wd, eps, and for RMSprop alpha in b2 / 1-alpha in omb2.
+struct LearnerAdam {
+    static constexpr int ID = FR_LEARNER_ADAM;
+    static constexpr bool HAS_M = true, HAS_V = true;
+    __device__ static __forceinline__ bool identity(const AdamC&) { return false; }
+    __device__ static __forceinline__ bool p_invariant(const AdamC&) { return false; }
+    __device__ static __forceinline__ void elem(float& p, float& m, float& v, float gd, float s0, float s1, const AdamC& c) {
+        adam_elem(p, m, v, gd, s0, s1, c);
+    }
+};
+
+// p + num / den as the Adam step rounds it (1-ulp reciprocal, or a correctly rounded division with FR_ADAM_PRECISE)
+__device__ __forceinline__ float step_div(float p, float num, float den) {
+#if FR_ADAM_PRECISE
+    return p + __fdiv_rn(num, den);
+#else
+    return fmaf(num, __builtin_amdgcn_rcpf(den), p);
+#endif
+}
+__device__ __forceinline__ float step_sqrt(float x) {
+#if FR_ADAM_PRECISE
+    return __fsqrt_rn(x);
+#else
+    return __builtin_amdgcn_sqrtf(x);
+#endif
+}
+
+// torch/optim/sgd.py (momentum 0): grad.add(param, alpha=wd); param.add_(grad, alpha=-lr).  s0 = lr.
+// A replayed step is ONE fma, p <- p + k_j*p with k_j = -lr_j*wd from the table (s1): the exact product p*(1 - lr*wd)
+// rounded once, against torch's two roundings (wd*p, then the add).
+struct LearnerSgd {
+    static constexpr int ID = FR_LEARNER_SGD;
+    static constexpr bool HAS_M = false, HAS_V = false;
+    __device__ static __forceinline__ bool identity(const AdamC& c) { return c.wd == 0.f; }
+    __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }
+    __device__ static __forceinline__ void elem(float& p, float&, float&, float gd, float s0, float, const AdamC& c) {
+        const float g = fmaf(c.wd, p, gd);
+        p = fmaf(-s0, g, p);
+    }
+    __device__ static __forceinline__ void zero(float& p, float&, float&, float, float s1, const AdamC&) {
+        p = fmaf(s1, p, p);
+    }
+};
+
+// torch/optim/adagrad.py (lr_decay 0, initial_accumulator_value 0): grad.add(param, alpha=wd);
+// state_sum.addcmul_(grad, grad, value=1); std = state_sum.sqrt().add_(eps); param.addcdiv_(grad, std, value=-clr).
+// s0 = clr_j.  State: m = sum.
+struct LearnerAdagrad {
+    static constexpr int ID = FR_LEARNER_ADAGRAD;
+    static constexpr bool HAS_M = true, HAS_V = false;
+    __device__ static __forceinline__ bool identity(const AdamC& c) { return c.wd == 0.f; }
+    __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }
+    __device__ static __forceinline__ void elem(float& p, float& m, float&, float gd, float s0, float, const AdamC& c) {
+        const float g = fmaf(c.wd, p, gd);
+        m = fmaf(g, g, m);
+        p = step_div(p, -s0 * g, step_sqrt(m) + c.eps);
+    }
+    __device__ static __forceinline__ void zero(float& p, float& m, float&, float s0, float, const AdamC& c) {
+        const float g = c.wd * p;
+        m = fmaf(g, g, m);
+        p = step_div(p, -s0 * g, step_sqrt(m) + c.eps);
+    }
+};
+
+// torch/optim/rmsprop.py (alpha = b2, momentum 0, not centered): grad.add(param, alpha=wd);
+// square_avg.mul_(alpha).addcmul_(grad, grad, value=1-alpha); avg = square_avg.sqrt().add_(eps);
+// param.addcdiv_(grad, avg, value=-lr).  s0 = lr.  State: m = square_avg.  With wd = 0 a replayed step only decays m.
+struct LearnerRmsprop {
+    static constexpr int ID = FR_LEARNER_RMSPROP;
+    static constexpr bool HAS_M = true, HAS_V = false;
+    __device__ static __forceinline__ bool identity(const AdamC&) { return false; }
+    __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }   // (only square_avg decays)
+    __device__ static __forceinline__ void elem(float& p, float& m, float&, float gd, float s0, float, const AdamC& c) {
+        const float g = fmaf(c.wd, p, gd);
+        m = fmaf(c.omb2 * g, g, m * c.b2);
+        p = step_div(p, -s0 * g, step_sqrt(m) + c.eps);
+    }
+    __device__ static __forceinline__ void zero(float& p, float& m, float&, float s0, float, const AdamC& c) {
+        if (c.wd == 0.f) {        // wave-uniform: g = 0, so p stays and m <- alpha*m (the same bits as elem with gd = 0)
+            m = m * c.b2;
+            return;
+        }
+        const float g = c.wd * p;
+        m = fmaf(c.omb2 * g, g, m * c.b2);
+        p = step_div(p, -s0 * g, step_sqrt(m) + c.eps);
+    }
+};
+
+// Replay of the zero-data-gradient steps (from, to] for the learners other than Adam: one step at a time, scalars of steps
+// inside the table fetched per step, the constant entry `cap` once for all steps beyond it.
+template <class L, int E, int NR>
+__device__ __forceinline__ void replay_plain(RowFrag<E>* (&p)[NR], RowFrag<E>* (&m)[NR], RowFrag<E>* (&v)[NR], int from,
+                                             int to, const AdamC& c) {
+    if (from >= to || L::identity(c)) return;
+    auto one = [&](float s0, float s1) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) L::zero(p[r]->x[e], m[r]->x[e], v[r]->x[e], s0, s1, c);
+        }
+    };
+    int j = from + 1;
+    for (; j <= to && j < c.cap; ++j) {
+        const float4 s = step_scalars4(c, j);
+        one(s.x, s.y);
+    }
+    if (j <= to) {
+        const float4 s = step_scalars4(c, c.cap);
+        for (; j <= to; ++j) one(s.x, s.y);
+    }
+}
+
+// replay_n for any learner: Adam keeps its own (scaled, prefetching) loops
+template <class L, int E, int NR>
+__device__ __forceinline__ void replay_l(RowFrag<E>* (&p)[NR], RowFrag<E>* (&m)[NR], RowFrag<E>* (&v)[NR], int from, int to,
+                                         const AdamC& c) {
+    if constexpr (L::ID == FR_LEARNER_ADAM) replay_n<E, NR>(p, m, v, from, to, c);
+    else replay_plain<L, E, NR>(p, m, v, from, to, c);
+}
+
+template <class L, int E>
+__device__ __forceinline__ void replay1(RowFrag<E>& p, RowFrag<E>& m, RowFrag<E>& v, int from, int to, const AdamC& c) {
+    RowFrag<E>* pp[1] = {&p};
+    RowFrag<E>* mm[1] = {&m};
+    RowFrag<E>* vv[1] = {&v};
+    replay_l<L, E, 1>(pp, mm, vv, from, to, c);
+}
+
+template <class L, int E>
+__device__ __forceinline__ void replay2l(RowFrag<E>& p0, RowFrag<E>& m0, RowFrag<E>& v0, RowFrag<E>& p1, RowFrag<E>& m1,
+                                         RowFrag<E>& v1, int from, int to, const AdamC& c) {
+    RowFrag<E>* pp[2] = {&p0, &p1};
+    RowFrag<E>* mm[2] = {&m0, &m1};
+    RowFrag<E>* vv[2] = {&v0, &v1};
+    replay_l<L, E, 2>(pp, mm, vv, from, to, c);
+}
+
+// host: launch `__VA_ARGS__` with `L` bound to the policy of learner `id` (validated by check_adam before)
+#define FR_DISPATCH_L(id, ...)                                                          \
+    switch (id) {                                                                       \
+        case FR_LEARNER_SGD: { using L = ::fr::LearnerSgd; __VA_ARGS__; } break;         \
+        case FR_LEARNER_ADAGRAD: { using L = ::fr::LearnerAdagrad; __VA_ARGS__; } break; \
+        case FR_LEARNER_RMSPROP: { using L = ::fr::LearnerRmsprop; __VA_ARGS__; } break; \
+        default: { using L = ::fr::LearnerAdam; __VA_ARGS__; } break;                   \
+    }
+
 }  // namespace fr

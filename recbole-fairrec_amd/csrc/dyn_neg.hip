@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void dyn_neg_select_kernel(const float* __rest
 // values PFCNBase.predict returns.  Candidates are processed NR at a time so that NR rows are in flight per wave.
 constexpr int DYN_NR = 4;
 
-template <int E>
+template <class L, int E>
 __global__ __launch_bounds__(256) void dyn_neg_dot_select_kernel(TableV It_, AdamC ci, TableV Bt_, AdamC cb, bool has_ib,
                                                                  const float* __restrict__ user_rows,
                                                                  const float* __restrict__ user_bias,
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void dyn_neg_dot_select_kernel(TableV It_, Ada
             id[q] = r0 + q < M ? cand[((size_t)(r0 + q) * num + j) * n + i] : -1;
 #pragma unroll
         for (int q = 0; q < DYN_NR; ++q)
-            if (r0 + q < M) row_at_step<E>(It, ci, id[q], p[q], err, lane);
+            if (r0 + q < M) row_at_step<E, L>(It, ci, id[q], p[q], err, lane);
 #pragma unroll
         for (int q = 0; q < DYN_NR; ++q) {
             if (r0 + q >= M) break;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void dyn_neg_dot_select_kernel(TableV It_, Ada
             if (has_ib) {
                 const TableV Bt = resolved(Bt_);
                 RowFrag<1> b;
-                row_at_step<1>(Bt, cb, id[q], b, err, lane);
+                row_at_step<1, L>(Bt, cb, id[q], b, err, lane);
                 x = x + __shfl(b.x[0], 0, 64);
             }
             if (global_bias) x = x + gb;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void dyn_neg_dot_select_kernel(TableV It_, Ada
 }
 
 // The scores alone (the values the kernel above picks from), for the tests that pin them to torch.sigmoid.
-template <int E>
+template <class L, int E>
 __global__ __launch_bounds__(256) void dyn_neg_dot_scores_kernel(TableV It_, AdamC ci, TableV Bt_, AdamC cb, bool has_ib,
                                                                  const float* __restrict__ user_rows,
                                                                  const float* __restrict__ user_bias,
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void dyn_neg_dot_scores_kernel(TableV It_, Ada
     RowFrag<E> u, p;
     load_row<E>(u, user_rows + (size_t)i * D, D, lane);
     const int64_t id = cand[k];
-    row_at_step<E>(It, ci, id, p, err, lane);
+    row_at_step<E, L>(It, ci, id, p, err, lane);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < E; ++e)
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void dyn_neg_dot_scores_kernel(TableV It_, Ada
     if (has_ib) {
         const TableV Bt = resolved(Bt_);
         RowFrag<1> b;
-        row_at_step<1>(Bt, cb, id, b, err, lane);
+        row_at_step<1, L>(Bt, cb, id, b, err, lane);
         x = x + __shfl(b.x[0], 0, 64);
     }
     if (global_bias) x = x + *global_bias;
@@ -151,10 +151,12 @@ static int dyn_neg_dot(const char* who, const fr_table* item_t, const fr_adam* i
                        const float* global_bias, const int64_t* cand, int64_t n, int32_t num, int32_t M, int64_t* out,
                        float* scores, uint32_t* err_flag, void* stream_) {
     int rc;
-    if ((rc = check_table(item_t, who)) || (rc = check_adam(item_adam, who))) return rc;
+    if ((rc = check_table_for(item_t, item_adam, who))) return rc;
     if (item_bias_t) {
-        if ((rc = check_table(item_bias_t, who)) || (rc = check_adam(item_bias_adam, who))) return rc;
+        if ((rc = check_table_for(item_bias_t, item_bias_adam, who))) return rc;
         FR_CHECK_ARG(item_bias_t->dim == 1, "%s: the item bias table must have one column", who);
+        FR_CHECK_ARG(item_bias_adam->learner == item_adam->learner, "%s: the item and item bias tables have different learners",
+                     who);
     }
     FR_CHECK_ARG(user_rows && cand && (out || scores) && n >= 0 && num >= 1 && M >= 1, "%s: bad argument", who);
     FR_CHECK_ARG(n * num <= 0x7fffffffLL * 4, "%s: too many columns", who);
@@ -168,15 +170,17 @@ static int dyn_neg_dot(const char* who, const fr_table* item_t, const fr_adam* i
     ProfScope prof(K_DYN_NEG_DOT_SELECT, stream);
     if (out) {
         const long long cols = (long long)n * num;
-        FR_DISPATCH_E(item_t->dim, FR_LAUNCH(prof, (dyn_neg_dot_select_kernel<E>), dim3((unsigned)((cols + 3) / 4)), dim3(256),
-                                             0, stream, It, ci, Bt, cb, has_ib, user_rows, user_bias, global_bias, cand,
-                                             (long long)n, (int)num, (int)M, out, err_flag));
+        FR_DISPATCH_L(item_adam->learner,
+                      FR_DISPATCH_E(item_t->dim, FR_LAUNCH(prof, (dyn_neg_dot_select_kernel<L, E>), dim3((unsigned)((cols + 3) / 4)),
+                                                           dim3(256), 0, stream, It, ci, Bt, cb, has_ib, user_rows, user_bias,
+                                                           global_bias, cand, (long long)n, (int)num, (int)M, out, err_flag)));
     } else {
         const long long k = (long long)n * num * M;
         FR_CHECK_ARG(k <= 0x7fffffffLL * 4, "%s: too many candidates", who);
-        FR_DISPATCH_E(item_t->dim, FR_LAUNCH(prof, (dyn_neg_dot_scores_kernel<E>), dim3((unsigned)((k + 3) / 4)), dim3(256),
-                                             0, stream, It, ci, Bt, cb, has_ib, user_rows, user_bias, global_bias, cand,
-                                             (long long)n, (int)num, (int)M, scores, err_flag));
+        FR_DISPATCH_L(item_adam->learner,
+                      FR_DISPATCH_E(item_t->dim, FR_LAUNCH(prof, (dyn_neg_dot_scores_kernel<L, E>), dim3((unsigned)((k + 3) / 4)),
+                                                           dim3(256), 0, stream, It, ci, Bt, cb, has_ib, user_rows, user_bias,
+                                                           global_bias, cand, (long long)n, (int)num, (int)M, scores, err_flag)));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;

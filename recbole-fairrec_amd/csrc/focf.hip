@@ -613,7 +613,7 @@ extern "C" int fr_focf_forward(const fr_table* U, const fr_table* I, const fr_ad
     hipStream_t stream = (hipStream_t)stream_;
     int rc;
     if ((rc = check_table(U, "fr_focf_forward(U)")) || (rc = check_table(I, "fr_focf_forward(I)")) ||
-        (rc = check_adam(adam, "fr_focf_forward")))
+        (rc = check_focf_adam(adam, "fr_focf_forward")))
         return rc;
     FR_CHECK_ARG(U->dim == I->dim, "fr_focf_forward: user dim %d != item dim %d", U->dim, I->dim);
     FR_CHECK_ARG(user && item && rating && loss_out && ws, "fr_focf_forward: null pointer");
@@ -721,7 +721,7 @@ extern "C" int fr_focf_backward_adam(const fr_table* U, const fr_table* I, const
     hipStream_t stream = (hipStream_t)stream_;
     int rc;
     if ((rc = check_table(U, "fr_focf_backward_adam(U)")) || (rc = check_table(I, "fr_focf_backward_adam(I)")) ||
-        (rc = check_adam(adam, "fr_focf_backward_adam")))
+        (rc = check_focf_adam(adam, "fr_focf_backward_adam")))
         return rc;
     FR_CHECK_ARG(U->dim == I->dim && ws && B >= 1 && B <= FR_SORT_MAX, "fr_focf_backward_adam: bad argument");
     FocfWs w = focf_layout(ws, B, U->dim);
@@ -750,7 +750,7 @@ extern "C" int fr_focf_predict(const fr_table* U, const fr_table* I, const fr_ad
     hipStream_t stream = (hipStream_t)stream_;
     int rc;
     if ((rc = check_table(U, "fr_focf_predict(U)")) || (rc = check_table(I, "fr_focf_predict(I)")) ||
-        (rc = check_adam(adam, "fr_focf_predict")))
+        (rc = check_focf_adam(adam, "fr_focf_predict")))
         return rc;
     FR_CHECK_ARG(U->dim == I->dim && user && item && out && B >= 0, "fr_focf_predict: bad argument");
     if (B == 0) return FR_OK;

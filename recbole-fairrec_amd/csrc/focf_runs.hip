@@ -634,7 +634,7 @@ extern "C" int fr_focf_step_runs_pipe(const fr_table* U, const fr_table* I, cons
     hipStream_t stream = (hipStream_t)stream_;
     int rc;
     if ((rc = check_table(U, "fr_focf_step_runs_pipe(U)")) || (rc = check_table(I, "fr_focf_step_runs_pipe(I)")) ||
-        (rc = check_adam(adam, "fr_focf_step_runs_pipe")))
+        (rc = check_focf_adam(adam, "fr_focf_step_runs_pipe")))
         return rc;
     const bool gather = user != nullptr && B > 0, finish = fin_ws != nullptr && fin_B > 0;
     FR_CHECK_ARG(U->dim == I->dim && U->step >= 1 && U->step == I->step && !U->step_dev && !I->step_dev,
@@ -708,7 +708,7 @@ extern "C" int fr_focf_step_runs(const fr_table* U, const fr_table* I, const fr_
     hipStream_t stream = (hipStream_t)stream_;
     int rc;
     if ((rc = check_table(U, "fr_focf_step_runs(U)")) || (rc = check_table(I, "fr_focf_step_runs(I)")) ||
-        (rc = check_adam(adam, "fr_focf_step_runs")))
+        (rc = check_focf_adam(adam, "fr_focf_step_runs")))
         return rc;
     FR_CHECK_ARG(U->dim == I->dim, "fr_focf_step_runs: user dim %d != item dim %d", U->dim, I->dim);
     FR_CHECK_ARG(ws && user && item && rating, "fr_focf_step_runs: null pointer");
@@ -762,6 +762,7 @@ extern "C" int fr_focf_runs_many(const fr_table* U, const fr_table* I, const fr_
                                  void* fin_ws, int64_t fin_B, int32_t fin_step, float* fin_loss_out, void* prev_ws,
                                  int64_t prev_B, float* prev_loss_out, float* loss_ring, int32_t loss_slots, int32_t first_slot,
                                  float* loss_acc, int32_t* own_u, int32_t* own_i, uint32_t* err_flag, void* stream_) {
+    if (const int rc_ = check_focf_adam(adam, "fr_focf_runs_many")) return rc_;
     hipStream_t stream = (hipStream_t)stream_;
     FR_CHECK_ARG(U && I && batches && n >= 1, "fr_focf_runs_many: null pointer / no batch");
     FR_CHECK_ARG(loss_ring && loss_slots >= 1 && first_slot >= 0 && first_slot < loss_slots,

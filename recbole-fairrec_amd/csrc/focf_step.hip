@@ -1863,9 +1863,8 @@ static int focf_step_impl(const fr_table* U, const fr_table* I, const fr_adam* a
     hipStream_t stream = (hipStream_t)stream_;
     const bool staged = row_words != nullptr;
     int rc;
-    if ((rc = check_table(U, "fr_focf_step(U)")) || (rc = check_table(I, "fr_focf_step(I)")) ||
-        (rc = check_adam(adam, "fr_focf_step")))
-        return rc;
+    // (the learner was checked by the entry points, fr_focf_step and fr_focf_step_staged, before any device work)
+    if ((rc = check_table(U, "fr_focf_step(U)")) || (rc = check_table(I, "fr_focf_step(I)"))) return rc;
     FR_CHECK_ARG(U->dim == I->dim, "fr_focf_step: user dim %d != item dim %d", U->dim, I->dim);
     FR_CHECK_ARG(ws, "fr_focf_step: null pointer");
     FR_CHECK_ARG(objective >= FR_FOCF_NONE && objective <= FR_FOCF_OVER,
@@ -1942,6 +1941,7 @@ extern "C" int fr_focf_step(const fr_table* U, const fr_table* I, const fr_adam*
                             float fair_weight, int32_t sweep_period, int32_t stamp, void* ws, size_t ws_bytes,
                             float* loss_out, void* prev_ws, int64_t prev_B, float* prev_loss_out, float* loss_acc,
                             uint32_t* err_flag, void* stream_) {
+    if (const int rc_ = check_focf_adam(adam, "fr_focf_step")) return rc_;
     (void)user; (void)item; (void)rating;    // fr_focf_prepare_step packed them into the workspace
     (void)loss_out;                          // reduced by the NEXT fr_focf_step (prev_*) or by fr_focf_step_finish
     return focf_step_impl(U, I, adam, sst, B, objective, fair_weight, sweep_period, stamp, ws, ws_bytes, prev_ws, prev_B,
@@ -1954,6 +1954,7 @@ extern "C" int fr_focf_step_staged(const fr_table* U, const fr_table* I, const f
                                    float* loss_acc, uint64_t* row_words, const fr_focf_batch* claim, int32_t claim_stamp,
                                    int32_t claim_gen, const fr_focf_batch* place, int32_t place_stamp, int32_t place_gen,
                                    uint32_t* err_flag, void* stream_) {
+    if (const int rc_ = check_focf_adam(adam, "fr_focf_step_staged")) return rc_;
     FR_CHECK_ARG(row_words && gen >= 0 && gen < 3, "fr_focf_step_staged: row words / generation");
     FR_CHECK_ARG((!claim || claim_gen != gen) && (!place || place_gen != gen) && (!claim || !place || claim_gen != place_gen),
                  "fr_focf_step_staged: the three batches in flight need three different generations of row words");
@@ -1981,6 +1982,7 @@ extern "C" int fr_focf_steps_many(const fr_table* U, const fr_table* I, const fr
                                   int32_t first_gen, void* prev_ws, int64_t prev_B, float* prev_loss_out, float* loss_ring,
                                   int32_t loss_slots, int32_t first_slot, float* loss_acc, uint64_t* row_words,
                                   uint32_t* err_flag, void* stream_) {
+    if (const int rc_ = check_focf_adam(adam, "fr_focf_steps_many")) return rc_;
     FR_CHECK_ARG(U && I && batches && n >= 1, "fr_focf_steps_many: null pointer / no batch");
     FR_CHECK_ARG(loss_ring && loss_slots >= 1 && first_slot >= 0 && first_slot < loss_slots,
                  "fr_focf_steps_many: loss ring (float[4 * loss_slots]) and a first slot inside it");

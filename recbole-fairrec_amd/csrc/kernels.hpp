@@ -141,6 +141,42 @@ inline int check_adam(const fr_adam* a, const char* who) {
         set_error("%s: bad fr_adam", who);
         return FR_EINVAL;
     }
+    if (a->learner < FR_LEARNER_ADAM || a->learner > FR_LEARNER_RMSPROP) {
+        set_error("%s: unknown learner %d in fr_adam", who, a->learner);
+        return FR_EINVAL;
+    }
+    return FR_OK;
+}
+
+// The FOCF entry points: their fused step is Adam's (focf*.hip), so any other learner is refused before device work.
+inline int check_focf_adam(const fr_adam* a, const char* who) {
+    int rc = check_adam(a, who);
+    if (rc) return rc;
+    if (a->learner != FR_LEARNER_ADAM) {
+        set_error("%s: FOCF runs learner adam only (fr_adam.learner = %d)", who, a->learner);
+        return FR_EINVAL;
+    }
+    return FR_OK;
+}
+
+// A lazy table for learner `a->learner` (check_adam first): the state arrays that learner keeps must be there, the others
+// may be NULL (fairrec_hip.h).
+inline int check_table_for(const fr_table* t, const fr_adam* a, const char* who) {
+    int rc = check_adam(a, who);
+    if (rc) return rc;
+    const bool need_m = a->learner != FR_LEARNER_SGD, need_v = a->learner == FR_LEARNER_ADAM;
+    if (!t || !t->p || (need_m && !t->m) || (need_v && !t->v) || !t->last || !t->stamp) {
+        set_error("%s: table has null pointers", who);
+        return FR_EINVAL;
+    }
+    if (t->dim < 1 || t->dim > 256) {
+        set_error("%s: embedding dim %d not in 1..256", who, t->dim);
+        return FR_EUNSUPPORTED;
+    }
+    if (t->n_rows < 1 || t->n_rows > 0x7fffffffLL) {
+        set_error("%s: n_rows %lld not in 1..2^31-1", who, (long long)t->n_rows);
+        return FR_EUNSUPPORTED;
+    }
     return FR_OK;
 }
 

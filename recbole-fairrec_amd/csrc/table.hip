@@ -16,44 +16,47 @@ namespace fr {
 // ------------------------------------------------------------------------------------------------
 // table maintenance
 // ------------------------------------------------------------------------------------------------
-template <int E>
+template <class L, int E>
 __global__ __launch_bounds__(256) void table_flush_kernel(TableV T_, AdamC c) {
     const TableV T = resolved(T_);
     const int lane = threadIdx.x & 63;
     const long long nw = (long long)gridDim.x * 4;
     if (E == 1 && T.D == 1) {      // narrow table: 64 rows per wave (table.hpp)
         for (long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); w * 64 < T.n_rows; w += nw)
-            sweep_rows_narrow(T, c, w * 64, T.n_rows, T.step, 0x7fffffff, lane);
+            sweep_rows_narrow<L>(T, c, w * 64, T.n_rows, T.step, 0x7fffffff, lane);
         return;
     }
     for (long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); row < T.n_rows; row += nw)
-        sweep_row<E>(T, c, row, T.step, 0x7fffffff, lane);
+        sweep_row<E, L>(T, c, row, T.step, 0x7fffffff, lane);
 }
 
-template <int E>
+template <class L, int E>
 __device__ __forceinline__ void gather_row(const TableV& T_, const AdamC& c, const int64_t* __restrict__ idx, long long M,
                                            float* __restrict__ out, uint32_t* err, const long long j, const int lane) {
     const TableV T = resolved(T_);
     if (j >= M) return;
     RowFrag<E> p;
-    row_at_step<E>(T, c, idx[j], p, err, lane);
+    row_at_step<E, L>(T, c, idx[j], p, err, lane);
     store_row<E>(p, out + (size_t)j * T.D, T.D, lane);
 }
 
-template <int E>
+template <class L, int E>
 __global__ __launch_bounds__(256) void table_gather_kernel(TableV T_, AdamC c, const int64_t* __restrict__ idx,
                                                            long long M, float* __restrict__ out, uint32_t* err) {
-    gather_row<E>(T_, c, idx, M, out, err, (long long)blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    gather_row<L, E>(T_, c, idx, M, out, err, (long long)blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
+template <class L>
 __global__ __launch_bounds__(256) void adam_dense_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, long long n,
                                                          AdamC c, int step) {
     const float2 s = step_scalars(c, step);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float pp = p[i], mm = m[i], vv = v[i];
-        adam_elem(pp, mm, vv, g[i], s.x, s.y, c);
-        p[i] = pp; m[i] = mm; v[i] = vv;
+        float pp = p[i], mm = L::HAS_M ? m[i] : 0.f, vv = L::HAS_V ? v[i] : 0.f;
+        L::elem(pp, mm, vv, g[i], s.x, s.y, c);
+        p[i] = pp;
+        if (L::HAS_M) m[i] = mm;
+        if (L::HAS_V) v[i] = vv;
     }
 }
 
@@ -65,13 +68,16 @@ struct DenseBatch {
     fr_dense_desc t[FR_ADAM_DENSE_MAX];
 };
 
+template <class L>
 __global__ __launch_bounds__(256) void adam_dense_multi_kernel(DenseBatch b, AdamC c) {
     const fr_dense_desc& d = b.t[blockIdx.y];
     const float2 s = step_scalars(c, d.step + (d.step_dev ? *d.step_dev : 0));
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < d.n; i += (long long)gridDim.x * 256) {
-        float pp = d.p[i], mm = d.m[i], vv = d.v[i];
-        adam_elem(pp, mm, vv, d.g[i], s.x, s.y, c);
-        d.p[i] = pp; d.m[i] = mm; d.v[i] = vv;
+        float pp = d.p[i], mm = L::HAS_M ? d.m[i] : 0.f, vv = L::HAS_V ? d.v[i] : 0.f;
+        L::elem(pp, mm, vv, d.g[i], s.x, s.y, c);
+        d.p[i] = pp;
+        if (L::HAS_M) d.m[i] = mm;
+        if (L::HAS_V) d.v[i] = vv;
     }
 }
 
@@ -85,7 +91,7 @@ struct GatherJob {
     TableWs w;
 };
 
-template <int E>
+template <class L, int E>
 __device__ __forceinline__ void gather_train_row(const GatherJob& J, const AdamC& c, long long M, const Lay& lay, uint32_t* err,
                                                  const long long j, const int lane) {
     const TableV T = resolved(J.T);
@@ -108,20 +114,21 @@ __device__ __forceinline__ void gather_train_row(const GatherJob& J, const AdamC
     const int lt = T.last[row];        // requested together with the row: one dependent round trip, not two
     RowFrag<E> p, m, v;
     load_row<E>(p, T.p + (size_t)row * D, D, lane);
-    load_row<E>(m, T.m + (size_t)row * D, D, lane);
-    load_row<E>(v, T.v + (size_t)row * D, D, lane);
+    if (L::HAS_M) load_row<E>(m, T.m + (size_t)row * D, D, lane);
+    if (L::HAS_V) load_row<E>(v, T.v + (size_t)row * D, D, lane);
     const int t0 = uniform(lt);
-    replay<E>(p, m, v, t0, T.step - 1, c, lane);
+    if constexpr (L::ID == FR_LEARNER_ADAM) replay<E>(p, m, v, t0, T.step - 1, c, lane);
+    else replay1<L, E>(p, m, v, t0, T.step - 1, c);      // (nothing at all where a missed step is the identity)
     store_row<E>(p, J.rows_out + (size_t)jp * D, D, lane);
-    store_row<E>(m, J.w.m_side + (size_t)j * D, D, lane);
-    store_row<E>(v, J.w.v_side + (size_t)j * D, D, lane);
+    if (L::HAS_M) store_row<E>(m, J.w.m_side + (size_t)j * D, D, lane);
+    if (L::HAS_V) store_row<E>(v, J.w.v_side + (size_t)j * D, D, lane);
     if (lane == 0) T.stamp[row] = T.step;
 }
 
-template <int E>
+template <class L, int E>
 __global__ __launch_bounds__(256) void table_gather_train_kernel(GatherJob ja, GatherJob jb, AdamC c, long long M,
                                                                  Lay lay, uint32_t* err) {
-    gather_train_row<E>(blockIdx.y == 0 ? ja : jb, c, M, lay, err, (long long)blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    gather_train_row<L, E>(blockIdx.y == 0 ? ja : jb, c, M, lay, err, (long long)blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // The lookups of a step in ONE launch: the sort of the id list(s) as the first workgroup(s) (sort_body.hpp: one latency-bound
@@ -134,7 +141,7 @@ struct PlainJob {
     float* out;
     long long M;
 };
-template <int E, int KPT>
+template <class L, int E, int KPT>
 __global__ __launch_bounds__(SORT_THREADS) void table_lookup_kernel(SortJobList jobs, int npass, GatherJob ja, GatherJob jb,
                                                                     int n_train, PlainJob pj, AdamC c, AdamC cp, long long M,
                                                                     Lay lay, uint32_t* err) {
@@ -149,11 +156,11 @@ __global__ __launch_bounds__(SORT_THREADS) void table_lookup_kernel(SortJobList 
     long long b = (long long)blockIdx.x - jobs.n;
     if (b < per * n_train) {
         const bool second = b >= per;
-        gather_train_row<E>(second ? jb : ja, c, M, lay, err, (second ? b - per : b) * WPB + (threadIdx.x >> 6), lane);
+        gather_train_row<L, E>(second ? jb : ja, c, M, lay, err, (second ? b - per : b) * WPB + (threadIdx.x >> 6), lane);
         return;
     }
     b -= per * n_train;
-    gather_row<E>(pj.T, cp, pj.idx, pj.M, pj.out, err, b * WPB + (threadIdx.x >> 6), lane);
+    gather_row<L, E>(pj.T, cp, pj.idx, pj.M, pj.out, err, b * WPB + (threadIdx.x >> 6), lane);
 }
 
 struct ApplyJob {
@@ -166,7 +173,7 @@ struct ApplyJob {
     long long M;          // ids of this table's batch (fr_table_apply_grad_two: each table its own)
 };
 
-template <int E>
+template <class L, int E>
 __global__ __launch_bounds__(256) void table_apply_grad_kernel(ApplyJob ja, ApplyJob jb, AdamC c, long long M, Lay lay) {
     const ApplyJob& J = blockIdx.y == 0 ? ja : jb;
     const TableV T = resolved(J.T);
@@ -177,18 +184,18 @@ __global__ __launch_bounds__(256) void table_apply_grad_kernel(ApplyJob ja, Appl
         sweep_range(T.n_rows, T.step, J.sweep_period, lo, hi);
         if (E == 1 && T.D == 1) {     // narrow table: 64 adjacent rows of the slice, one per lane
             const long long a = lo + 64 * wv;
-            if (a < hi) sweep_rows_narrow(T, c, a, hi, T.step, T.step, lane);
+            if (a < hi) sweep_rows_narrow<L>(T, c, a, hi, T.step, T.step, lane);
         } else if (sweep_pairs(E)) {     // a wave takes two adjacent rows of the slice (see sweep_row_pair)
             const long long a = lo + 2 * wv;
-            if (a < hi) sweep_row_pair<E>(T, c, a, a + 1 < hi ? a + 1 : -1, T.step, T.step, lane);
+            if (a < hi) sweep_row_pair<E, L>(T, c, a, a + 1 < hi ? a + 1 : -1, T.step, T.step, lane);
         } else if (lo + wv < hi) {
-            sweep_row<E>(T, c, lo + wv, T.step, T.step, lane);
+            sweep_row<E, L>(T, c, lo + wv, T.step, T.step, lane);
         }
         return;
     }
     wv -= J.sw_n;
     if (wv < J.M && wv < J.w.nseg[0])
-        segment_update<E>(T, c, (int)wv, J.w.seg_start, J.w.seg_row, J.w.perm, nullptr, J.rows, J.w.m_side, J.w.v_side,
+        segment_update<E, L>(T, c, (int)wv, J.w.seg_start, J.w.seg_row, J.w.perm, nullptr, J.rows, J.w.m_side, J.w.v_side,
                           J.grad_rows, lane, lay, J.w.seg_first);
 }
 
@@ -196,17 +203,25 @@ __global__ __launch_bounds__(256) void table_apply_grad_kernel(ApplyJob ja, Appl
 
 using namespace fr;
 
+// a zero-data-gradient step leaves (p, state) as they are: SGD and Adagrad without weight decay
+static inline bool replay_is_identity(const fr_adam* a) {
+    return (a->learner == FR_LEARNER_SGD || a->learner == FR_LEARNER_ADAGRAD) && (float)a->weight_decay == 0.f;
+}
+static inline bool learner_has_m(const fr_adam* a) { return a->learner != FR_LEARNER_SGD; }
+static inline bool learner_has_v(const fr_adam* a) { return a->learner == FR_LEARNER_ADAM; }
+
 extern "C" int fr_table_flush(const fr_table* t, const fr_adam* adam, void* stream_) {
     int rc;
-    if ((rc = check_table(t, "fr_table_flush")) || (rc = check_adam(adam, "fr_table_flush"))) return rc;
+    if ((rc = check_table_for(t, adam, "fr_table_flush"))) return rc;
     if (t->step < 1 && !t->step_dev) return FR_OK;
+    if (replay_is_identity(adam)) return FR_OK;       // no row can be behind: nothing to move
     const AdamC c = make_adamc(adam);
     const TableV Tv = view(t);
     long long blocks = (t->n_rows + 3) / 4;
     if (blocks > 256 * 32) blocks = 256 * 32;
     {
         ProfScope prof(K_TABLE_FLUSH, (hipStream_t)stream_);
-        FR_DISPATCH_E(t->dim, FR_LAUNCH(prof, (table_flush_kernel<E>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, Tv, c));
+        FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(t->dim, FR_LAUNCH(prof, (table_flush_kernel<L, E>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, Tv, c)));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;
@@ -215,14 +230,14 @@ extern "C" int fr_table_flush(const fr_table* t, const fr_adam* adam, void* stre
 extern "C" int fr_table_gather(const fr_table* t, const fr_adam* adam, const int64_t* idx, int64_t M, float* out,
                                uint32_t* err_flag, void* stream_) {
     int rc;
-    if ((rc = check_table(t, "fr_table_gather")) || (rc = check_adam(adam, "fr_table_gather"))) return rc;
+    if ((rc = check_table_for(t, adam, "fr_table_gather"))) return rc;
     FR_CHECK_ARG(idx && out && M >= 0, "fr_table_gather: bad argument");
     if (M == 0) return FR_OK;
     const AdamC c = make_adamc(adam);
     const TableV Tv = view(t);
     {
         ProfScope prof(K_TABLE_GATHER, (hipStream_t)stream_);
-        FR_DISPATCH_E(t->dim, FR_LAUNCH(prof, (table_gather_kernel<E>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, Tv, c, idx, (long long)M, out, err_flag));
+        FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(t->dim, FR_LAUNCH(prof, (table_gather_kernel<L, E>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, Tv, c, idx, (long long)M, out, err_flag)));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;
@@ -232,14 +247,15 @@ extern "C" int fr_adam_dense(float* p, const float* g, float* m, float* v, int64
                              int32_t step, void* stream_) {
     int rc;
     if ((rc = check_adam(adam, "fr_adam_dense"))) return rc;
-    FR_CHECK_ARG(p && g && m && v && n >= 0 && step >= 1, "fr_adam_dense: bad argument");
+    FR_CHECK_ARG(p && g && (m || !learner_has_m(adam)) && (v || !learner_has_v(adam)) && n >= 0 && step >= 1,
+                 "fr_adam_dense: bad argument");
     if (n == 0) return FR_OK;
     long long blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     {
         ProfScope prof(K_ADAM_DENSE, (hipStream_t)stream_);
-        FR_LAUNCH(prof, adam_dense_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p, g, m, v,
-                           (long long)n, make_adamc(adam), step);
+        FR_DISPATCH_L(adam->learner, FR_LAUNCH(prof, adam_dense_kernel<L>, dim3((unsigned)blocks), dim3(256), 0,
+                                               (hipStream_t)stream_, p, g, m, v, (long long)n, make_adamc(adam), step));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;
@@ -256,15 +272,16 @@ extern "C" int fr_adam_dense_multi(const fr_dense_desc* descs, int32_t n_tensors
         long long nmax = 1;
         for (int k = 0; k < cnt; ++k) {
             const fr_dense_desc& d = descs[base + k];
-            FR_CHECK_ARG(d.p && d.g && d.m && d.v && d.n >= 0 && (d.step >= 1 || d.step_dev), "fr_adam_dense_multi: bad descriptor %d", base + k);
+            FR_CHECK_ARG(d.p && d.g && (d.m || !learner_has_m(adam)) && (d.v || !learner_has_v(adam)) && d.n >= 0 &&
+                             (d.step >= 1 || d.step_dev), "fr_adam_dense_multi: bad descriptor %d", base + k);
             b.t[k] = d;
             nmax = std::max<long long>(nmax, d.n);
         }
         for (int k = cnt; k < FR_ADAM_DENSE_MAX; ++k) b.t[k] = fr_dense_desc{nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr};
         const long long blocks = std::min<long long>((nmax + 255) / 256, 256);
         ProfScope prof(K_ADAM_DENSE, (hipStream_t)stream_);
-        FR_LAUNCH(prof, adam_dense_multi_kernel, dim3((unsigned)blocks, (unsigned)cnt), dim3(256), 0, (hipStream_t)stream_, b,
-                  c);
+        FR_DISPATCH_L(adam->learner, FR_LAUNCH(prof, adam_dense_multi_kernel<L>, dim3((unsigned)blocks, (unsigned)cnt), dim3(256), 0,
+                                               (hipStream_t)stream_, b, c));
         FR_CHECK_LAUNCH();
     }
     return FR_OK;
@@ -286,7 +303,7 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
                              const fr_adam* ro_adam = nullptr, const int64_t* ro_idx = nullptr, int64_t ro_M = 0,
                              float* ro_out = nullptr) {
     int rc;
-    if ((rc = check_table(ta, who)) || (tb && (rc = check_table(tb, who))) || (rc = check_adam(adam, who))) return rc;
+    if ((rc = check_table_for(ta, adam, who)) || (tb && (rc = check_table_for(tb, adam, who)))) return rc;
     FR_CHECK_ARG(idx_a && rows_a && ws_a && M >= 1 && M <= FR_SORT_MAX && ta->step >= 1 && lay_ok(chunk, stride),
                  "%s: bad argument (M=%lld, step=%d)", who, (long long)M, ta->step);
     FR_CHECK_ARG(!tb || (idx_b && rows_b && ws_b && ws_b != ws_a && tb->dim == ta->dim && tb->step >= 1),
@@ -313,8 +330,10 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
     // one launch for the sort and the gathers where nothing would overlap otherwise (and whenever a frozen table rides along)
     static const bool no_merge = getenv("FAIRREC_LOOKUP_SEPARATE") != nullptr;
     const int kpt = M <= 2 * SORT_THREADS ? 2 : (M <= 4 * SORT_THREADS ? 4 : (M <= 8 * SORT_THREADS ? 8 : 16));
-    if (!prepared && !no_merge && kpt != 0 && (!overlap || ro) && (!ro || (ro->dim + 63) / 64 == (ta->dim + 63) / 64)) {
-        if (ro && ((rc = check_table(ro, who)) || (rc = check_adam(ro_adam, who)))) return rc;
+    // (the read-only table rides along only under the same learner: one policy per launch)
+    if (!prepared && !no_merge && kpt != 0 && (!overlap || ro) && (!ro || (ro->dim + 63) / 64 == (ta->dim + 63) / 64) &&
+        (!ro || (ro_adam && ro_adam->learner == adam->learner))) {
+        if (ro && (rc = check_table_for(ro, ro_adam, who))) return rc;
         FR_CHECK_ARG(!ro || (ro_idx && ro_out && ro_M >= 0), "%s: bad read-only lookup", who);
         SortJobList jobs{};
         jobs.j[0] = sa;
@@ -339,25 +358,25 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
         ProfScope prof(K_TABLE_GATHER_TRAIN, stream);
 #define FR_LOOKUP_LAUNCH(KPT)                                                                                              \
     {                                                                                                                      \
-        static bool attr_set[5] = {false, false, false, false, false};                                                     \
-        if (!attr_set[E]) {                                                                                                \
-            FR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(table_lookup_kernel<E, KPT>),                   \
+        static bool attr_set[4][5] = {};                                                                                   \
+        if (!attr_set[L::ID][E]) {                                                                                         \
+            FR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(table_lookup_kernel<L, E, KPT>),                \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds_bytes<KPT>()));     \
-            attr_set[E] = true;                                                                                            \
+            attr_set[L::ID][E] = true;                                                                                     \
         }                                                                                                                  \
         const int passes_ = (bits + sort_digit_bits(KPT) - 1) / sort_digit_bits(KPT);                                      \
         const int npass = passes_ | ((bits - sort_digit_bits(KPT) * (passes_ - 1)) << 8);                                  \
-        FR_LAUNCH(prof, (table_lookup_kernel<E, KPT>), dim3((unsigned)blocks), dim3(SORT_THREADS), sort_lds_bytes<KPT>(),  \
+        FR_LAUNCH(prof, (table_lookup_kernel<L, E, KPT>), dim3((unsigned)blocks), dim3(SORT_THREADS), sort_lds_bytes<KPT>(),  \
                   stream, jobs, npass, ja, jb, tb ? 2 : 1, pj, c, cp, (long long)M, lay, err_flag);                        \
     }
         if (kpt == 2) {
-            FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(2));
+            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(2)));
         } else if (kpt == 4) {
-            FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(4));
+            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(4)));
         } else if (kpt == 8) {
-            FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(8));
+            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(8)));
         } else {
-            FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(16));
+            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(16)));
         }
 #undef FR_LOOKUP_LAUNCH
         FR_CHECK_LAUNCH();
@@ -382,7 +401,7 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
     GatherJob jb = tb ? GatherJob{view(tb), idx_b, rows_b, wb} : ja;
     {
         ProfScope prof(K_TABLE_GATHER_TRAIN, stream);
-        FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_gather_train_kernel<E>), dim3((unsigned)((M + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)M, lay, err_flag));
+        FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_gather_train_kernel<L, E>), dim3((unsigned)((M + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)M, lay, err_flag)));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;
@@ -462,7 +481,7 @@ static int apply_grad_impl(const char* who, const fr_table* ta, const fr_table* 
                            hipStream_t stream, int64_t Mb = -1, size_t ws_b_bytes = 0) {
     int rc;
     if (Mb < 0) Mb = M, ws_b_bytes = ws_bytes;
-    if ((rc = check_table(ta, who)) || (tb && (rc = check_table(tb, who))) || (rc = check_adam(adam, who))) return rc;
+    if ((rc = check_table_for(ta, adam, who)) || (tb && (rc = check_table_for(tb, adam, who)))) return rc;
     FR_CHECK_ARG(rows_a && grad_a && ws_a && M >= 1 && M <= FR_SORT_MAX && ta->step >= 1 && lay_ok(chunk, stride),
                  "%s: bad argument", who);
     FR_CHECK_ARG(!tb || (rows_b && grad_b && ws_b && ws_b != ws_a && tb->dim == ta->dim && tb->step >= 1 && Mb >= 1 &&
@@ -476,6 +495,7 @@ static int apply_grad_impl(const char* who, const fr_table* ta, const fr_table* 
     // waves reserved for the sweeper = rows of a full slice (the slice itself depends on the effective step, which may
     // live on the device)
     const int per_wave = sweep_rows_per_wave(ta->dim);
+    if (replay_is_identity(adam)) sweep_a = sweep_b = 0;     // rows outside the batch do not change: no sweeper waves
     const long long sw_a = sweep_a > 0 ? ((ta->n_rows + sweep_a - 1) / sweep_a + per_wave - 1) / per_wave : 0;
     const long long sw_b = tb && sweep_b > 0 ? ((tb->n_rows + sweep_b - 1) / sweep_b + per_wave - 1) / per_wave : 0;
     const long long waves = std::max(M + sw_a, tb ? Mb + sw_b : 0);
@@ -484,7 +504,7 @@ static int apply_grad_impl(const char* who, const fr_table* ta, const fr_table* 
     ApplyJob jb = tb ? ApplyJob{view(tb), wb, rows_b, grad_b, (int)sweep_b, (int)sw_b, (long long)Mb} : ja;
     {
         ProfScope prof(K_TABLE_APPLY_GRAD, stream);
-        FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_apply_grad_kernel<E>), dim3((unsigned)((waves + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)M, lay));
+        FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_apply_grad_kernel<L, E>), dim3((unsigned)((waves + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)M, lay)));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;

@@ -8,7 +8,7 @@ namespace fr {
 // Row `r` of a resolved table as of its step T.step, in registers (d = lane + 64*e): the parameters, caught up through
 // the zero-gradient steps it has not seen (replay of the lazy Adam update).  An id outside [0, n_rows) sets
 // FR_DEV_ERR_INDEX_RANGE and reads row 0.  fr_table_gather and fr_dyn_neg_dot_select read rows through this.
-template <int E>
+template <int E, class L = LearnerAdam>
 __device__ __forceinline__ void row_at_step(const TableV& T, const AdamC& c, long long r, RowFrag<E>& p, uint32_t* err,
                                             const int lane) {
     if (r < 0 || r >= T.n_rows) {
@@ -17,6 +17,17 @@ __device__ __forceinline__ void row_at_step(const TableV& T, const AdamC& c, lon
     }
     const int row = uniform((int)r);
     const int D = T.D;
+    if constexpr (L::ID != FR_LEARNER_ADAM) {
+        load_row<E>(p, T.p + (size_t)row * D, D, lane);
+        if (L::p_invariant(c)) return;    // (no weight decay: a missed step leaves p as it is; nothing else is read here)
+        const int t0 = uniform(T.last[row]);
+        if (t0 < T.step) {
+            RowFrag<E> m, v;
+            if (L::HAS_M) load_row<E>(m, T.m + (size_t)row * D, D, lane);
+            replay1<L, E>(p, m, v, t0, T.step, c);
+        }
+        return;
+    }
     const int t0 = uniform(T.last[row]);
     RowFrag<E> m, v;
     load_row<E>(p, T.p + (size_t)row * D, D, lane);
@@ -108,7 +119,7 @@ __device__ __forceinline__ void segment_grad_sum(RowFrag<E>& g, int j0, int j1, 
 // Adam step `T.step` to the caught-up state parked in the workspace, write the row back once.
 //   coef != nullptr : contribution of member b = coef[b] * other[b,:]   (rank-1 form: MF models)
 //   coef == nullptr : contribution of member b = other[b,:]             (gradient rows from an MLP backward)
-template <int E>
+template <int E, class L = LearnerAdam>
 __device__ __forceinline__ void segment_update(const TableV& T, const AdamC& c, int k, const int32_t* seg_start,
                                                const int32_t* seg_row, const int32_t* perm, const float* coef,
                                                const float* sp, const float* sm, const float* sv, const float* other,
@@ -124,21 +135,21 @@ __device__ __forceinline__ void segment_update(const TableV& T, const AdamC& c, 
     const int b0 = seg_first ? uniform(rb0) : uniform(perm[j0]);
     RowFrag<E> p, m, v, g;
     load_row<E>(p, sp + (size_t)lay.at(b0) * D, D, lane);
-    load_row<E>(m, sm + (size_t)b0 * D, D, lane);
-    load_row<E>(v, sv + (size_t)b0 * D, D, lane);
+    if (L::HAS_M) load_row<E>(m, sm + (size_t)b0 * D, D, lane);
+    if (L::HAS_V) load_row<E>(v, sv + (size_t)b0 * D, D, lane);
     segment_grad_sum<E>(g, j0, j1, b0, perm, coef, other, D, lane, lay);
     const float2 s = step_scalars(c, T.step);
 #pragma unroll
-    for (int e = 0; e < E; ++e) adam_elem(p.x[e], m.x[e], v.x[e], g.x[e], s.x, s.y, c);
+    for (int e = 0; e < E; ++e) L::elem(p.x[e], m.x[e], v.x[e], g.x[e], s.x, s.y, c);
     store_row<E>(p, T.p + (size_t)row * D, D, lane);
-    store_row<E>(m, T.m + (size_t)row * D, D, lane);
-    store_row<E>(v, T.v + (size_t)row * D, D, lane);
+    if (L::HAS_M) store_row<E>(m, T.m + (size_t)row * D, D, lane);
+    if (L::HAS_V) store_row<E>(v, T.v + (size_t)row * D, D, lane);
     if (lane == 0) T.last[row] = T.step;
 }
 
 // Bring one untouched row up to `upto` (all missed steps have zero data gradient).  Rows whose stamp is >= skip_from
 // belong to a batch of step skip_from or later (a segment wave owns them) and are left alone.
-template <int E>
+template <int E, class L = LearnerAdam>
 __device__ __forceinline__ void sweep_row(const TableV& T, const AdamC& c, long long row, int upto, int skip_from,
                                           int lane) {
     const int D = T.D;
@@ -147,15 +158,16 @@ __device__ __forceinline__ void sweep_row(const TableV& T, const AdamC& c, long 
     const int lt = T.last[row];
     RowFrag<E> p, m, v;
     load_row<E>(p, T.p + (size_t)row * D, D, lane);
-    load_row<E>(m, T.m + (size_t)row * D, D, lane);
-    load_row<E>(v, T.v + (size_t)row * D, D, lane);
+    if (L::HAS_M) load_row<E>(m, T.m + (size_t)row * D, D, lane);
+    if (L::HAS_V) load_row<E>(v, T.v + (size_t)row * D, D, lane);
     if (uniform(st) >= skip_from) return;
     const int t0 = uniform(lt);
     if (t0 >= upto) return;
-    replay<E>(p, m, v, t0, upto, c, lane);
+    if constexpr (L::ID == FR_LEARNER_ADAM) replay<E>(p, m, v, t0, upto, c, lane);
+    else replay1<L, E>(p, m, v, t0, upto, c);
     store_row<E>(p, T.p + (size_t)row * D, D, lane);
-    store_row<E>(m, T.m + (size_t)row * D, D, lane);
-    store_row<E>(v, T.v + (size_t)row * D, D, lane);
+    if (L::HAS_M) store_row<E>(m, T.m + (size_t)row * D, D, lane);
+    if (L::HAS_V) store_row<E>(v, T.v + (size_t)row * D, D, lane);
     if (lane == 0) T.last[row] = upto;
 }
 
@@ -164,13 +176,14 @@ __device__ __forceinline__ void sweep_row(const TableV& T, const AdamC& c, long 
 // from as much VALU time as the embedding tables' sweep (128 us of 1.2 ms at 10 M rows) to a few us.  Every lane replays its
 // own stretch (last[row], upto] inside one wave-uniform loop over the steps (the per-step scalars are the same for all rows),
 // masked off before its own first step: the same operations per element as replay<1>, so the same bits.
+template <class L = LearnerAdam>
 __device__ __forceinline__ void sweep_rows_narrow(const TableV& T, const AdamC& c, long long row0, long long hi, int upto,
                                                   int skip_from, int lane) {
     const long long row = row0 + lane;
     const bool in = row < hi;
     const int st = in ? T.stamp[row] : 0x7fffffff;
     const int lt = in ? T.last[row] : upto;
-    float p = in ? T.p[row] : 0.f, m = in ? T.m[row] : 0.f, v = in ? T.v[row] : 0.f;
+    float p = in ? T.p[row] : 0.f, m = in && L::HAS_M ? T.m[row] : 0.f, v = in && L::HAS_V ? T.v[row] : 0.f;
     const bool act = in && st < skip_from && lt < upto;
     const int t0 = act ? lt : upto;
     int jmin = t0;
@@ -178,6 +191,22 @@ __device__ __forceinline__ void sweep_rows_narrow(const TableV& T, const AdamC& 
     for (int o = 32; o > 0; o >>= 1) jmin = min(jmin, __shfl_xor(jmin, o, 64));
     jmin = uniform(jmin);
     if (jmin >= upto) return;
+    if constexpr (L::ID != FR_LEARNER_ADAM) {   // one step at a time, kept by the lanes whose stretch has begun
+        for (int j = jmin + 1; j <= upto; ++j) {
+            const float4 s = step_scalars4(c, j);
+            float pn = p, mn = m, vn = v;
+            L::zero(pn, mn, vn, s.x, s.y, c);
+            const bool on = j > t0;
+            p = on ? pn : p;
+            m = on ? mn : m;
+        }
+        if (act) {
+            T.p[row] = p;
+            if (L::HAS_M) T.m[row] = m;
+            T.last[row] = upto;
+        }
+        return;
+    }
     const bool scaled = !FR_ADAM_PRECISE && c.k1 != 0.f;       // as replay_n chooses
     if (scaled) {
         m *= c.inv_k1;
@@ -239,11 +268,16 @@ __host__ __device__ constexpr bool sweep_pairs(int E) { return E <= 1; }
 // Two rows of a sweep slice in one wave: both are requested at once (twice the rows in flight per wave slot) and their
 // common stretch of missed steps is replayed interleaved, which the compiler packs into v_pk_* instructions (26 instead
 // of 36 issue cycles per row and step).  rowB < 0: only rowA.
-template <int E>
+template <int E, class L = LearnerAdam>
 __device__ __forceinline__ void sweep_row_pair(const TableV& T, const AdamC& c, long long rowA, long long rowB, int upto,
                                                int skip_from, int lane) {
     if (rowB < 0) {
-        sweep_row<E>(T, c, rowA, upto, skip_from, lane);
+        sweep_row<E, L>(T, c, rowA, upto, skip_from, lane);
+        return;
+    }
+    if constexpr (L::ID != FR_LEARNER_ADAM) {   // (no packed replay for these: one row after the other)
+        sweep_row<E, L>(T, c, rowA, upto, skip_from, lane);
+        sweep_row<E, L>(T, c, rowB, upto, skip_from, lane);
         return;
     }
     const int D = T.D;

@@ -35,7 +35,7 @@ class FrDenseDesc(Structure):   # include/fairrec_hip.h: fr_dense_desc
 
 
 class FrAdam(Structure):
-    _fields_ = [("scalars", c_void_p), ("cap", c_int32), ("reserved_", c_int32), ("weight_decay", c_double),
+    _fields_ = [("scalars", c_void_p), ("cap", c_int32), ("learner", c_int32), ("weight_decay", c_double),
                 ("beta1", c_double), ("beta2", c_double), ("eps", c_double)]
 
 

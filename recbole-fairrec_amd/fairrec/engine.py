@@ -15,19 +15,45 @@ from typing import Dict, Optional
 import torch
 
 from . import _C
-from .optim import AdamHyper, LazyLookup, LazyTable
+from .optim import LEARNER_ADAM, LEARNER_RMSPROP, LEARNER_STATE, AdamHyper, LazyLookup, LazyTable
 
 
 class DenseState:
-    def __init__(self, p: torch.nn.Parameter):
+    def __init__(self, p: torch.nn.Parameter, learner: int = LEARNER_ADAM):
         self.p = p
-        self.m = torch.zeros_like(p.data)
-        self.v = torch.zeros_like(p.data)
+        self.learner = learner
+        self._alloc()
         self.step = 0
         self.step_dev = None     # optional device-resident counter (graph mode), as LazyTable.step_dev
 
+    def _alloc(self):
+        # only the state the learner keeps (include/fairrec_hip.h): Adam m and v, Adagrad / RMSprop m, SGD none
+        has_m, has_v = (k is not None for k in LEARNER_STATE[self.learner])
+        self.m = torch.zeros_like(self.p.data) if has_m else None
+        self.v = torch.zeros_like(self.p.data) if has_v else None
+
+    def set_learner(self, learner: int):
+        if learner != self.learner:
+            if self.step != 0:
+                raise _C.FairrecError("a parameter that has been stepped cannot change its learner")
+            self.learner = learner
+            self._alloc()
+
+    def state(self):
+        """torch.optim.<Learner>'s per-parameter state (None where torch keeps none)."""
+        m_name, v_name = LEARNER_STATE[self.learner]
+        if m_name is None or (self.learner == LEARNER_RMSPROP and self.step == 0):
+            return None
+        st = {"step": torch.tensor(float(self.step)), m_name: self.m}
+        if v_name is not None:
+            st[v_name] = self.v
+        return st
+
 
 class GenericEngine:
+    # the learners other than Adam run on this engine only (the row-sharded / replicated subclasses step with Adam's kernels)
+    lazy_learners = True
+
     def __init__(self, device):
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -113,9 +139,11 @@ class GenericEngine:
         """`group` = the subset of entries this optimizer owns (PFCN: optimizer_filter / optimizer_dis,
         trainer.py:1201-1212); None = everything (the single default optimizer)."""
         self.optimizer, self.hyper, self.sweep_period = opt, opt.hyper, sweep_period
+        learner = opt.hyper.learner
         for name in list(self._tables) + list(self._dense):
             if self._owned(name, group):
                 self._hyper_of[name] = opt.hyper
+                (self._tables[name] if name in self._tables else self._dense[name]).set_learner(learner)
         for t in self._tables.values():
             t.ensure_state()
 
@@ -270,10 +298,10 @@ class GenericEngine:
             descs = (_C.FrDenseDesc * len(items))()
             for k, (d, g) in enumerate(items):
                 if d.step_dev is not None:      # effective step = device counter + 1
-                    descs[k] = _C.FrDenseDesc(d.p.data.data_ptr(), g.data_ptr(), d.m.data_ptr(), d.v.data_ptr(),
+                    descs[k] = _C.FrDenseDesc(d.p.data.data_ptr(), g.data_ptr(), _C.ptr(d.m), _C.ptr(d.v),
                                               d.p.numel(), 1, d.step_dev.data_ptr())
                 else:
-                    descs[k] = _C.FrDenseDesc(d.p.data.data_ptr(), g.data_ptr(), d.m.data_ptr(), d.v.data_ptr(),
+                    descs[k] = _C.FrDenseDesc(d.p.data.data_ptr(), g.data_ptr(), _C.ptr(d.m), _C.ptr(d.v),
                                               d.p.numel(), d.step, None)
             _C.check(_C.lib().fr_adam_dense_multi(descs, len(items), ctypes.byref(h.c()), st), "fr_adam_dense_multi")
             for d, _ in items:
@@ -293,10 +321,23 @@ class GenericEngine:
     # --- torch.optim.Adam-shaped state for checkpoints ----------------------------------------------------
     def dense_state(self, group=None):
         self.sync_steps()
-        return {k: {"step": torch.tensor(float(d.step)), "exp_avg": d.m, "exp_avg_sq": d.v}
-                for k, d in self._dense.items() if self._owned(k, group)}
+        return {k: d.state() for k, d in self._dense.items() if self._owned(k, group)}
 
-    def load_dense_state(self, sd):
+    def load_dense_state(self, sd, group=None):
+        """Adam: the entries of `sd`.  Other learners: every dense tensor of `group` (one without an entry -- SGD, an
+        RMSprop tensor never stepped -- is reset to no state); names that are no dense tensor here are ignored."""
+        if group is not None or any(d.learner != LEARNER_ADAM for d in self._dense.values()):
+            for k, d in self._dense.items():
+                if d.learner == LEARNER_ADAM or not self._owned(k, group):
+                    continue
+                st = sd.get(k)
+                m_name = LEARNER_STATE[d.learner][0]
+                d.step = int(st["step"]) if st is not None and m_name is not None else 0
+                if d.m is not None:
+                    d.m.copy_(st[m_name]) if st is not None else d.m.zero_()
+                if d.step_dev is not None:
+                    d.step_dev.fill_(d.step)
+            sd = {k: st for k, st in sd.items() if k in self._dense and self._dense[k].learner == LEARNER_ADAM}
         for k, st in sd.items():
             d = self._dense[k]
             d.step = int(st["step"])

@@ -1,10 +1,12 @@
-"""Host side of the lazily-applied dense Adam that backs every trainable embedding table.
+"""Host side of the lazily-applied dense Adam (and SGD / Adagrad / RMSprop) that backs every trainable embedding table.
 
 Replaces `torch.optim.Adam(params, lr=..., weight_decay=...)` as built by the reference at
 recbole/trainer/trainer.py:114-153 (learner 'adam').  The arithmetic is torch's `_single_tensor_adam`
 (coupled L2, bias corrections computed in double on the host); what changes is WHEN a row is updated:
 the HIP kernels replay the steps a row missed when it is next read, so the per-step HBM traffic is
-proportional to the batch, not to the table.
+proportional to the batch, not to the table.  Learners 'sgd', 'adagrad' and 'rmsprop' (reference
+trainer.py:114-153, torch's defaults) run on the same tables: `SGDHyper` / `AdagradHyper` / `RMSpropHyper` and
+`FusedLazySGD` / `FusedLazyAdagrad` / `FusedLazyRMSprop`.
 """
 from __future__ import annotations
 
@@ -54,8 +56,40 @@ def _used_on_side_stream(t: torch.Tensor):
         t.record_stream(side)
 
 
+LEARNER_ADAM, LEARNER_SGD, LEARNER_ADAGRAD, LEARNER_RMSPROP = 0, 1, 2, 3     # fr_adam.learner (include/fairrec_hip.h)
+LEARNER_NAMES = {LEARNER_ADAM: "adam", LEARNER_SGD: "sgd", LEARNER_ADAGRAD: "adagrad", LEARNER_RMSPROP: "rmsprop"}
+# the state arrays each learner keeps: (fr_table.m, fr_table.v) and their names in torch's state_dict
+LEARNER_STATE = {LEARNER_ADAM: ("exp_avg", "exp_avg_sq"), LEARNER_SGD: (None, None), LEARNER_ADAGRAD: ("sum", None),
+                 LEARNER_RMSPROP: ("square_avg", None)}
+
+
+def sgd_step_scalars(lr: float, weight_decay: float, cap: int) -> np.ndarray:
+    """float32[4*(cap+1)]: entry j = (lr, -lr*wd, 0, 0).  The second is the coefficient of a replayed step p <- p + k*p."""
+    out = np.zeros(4 * (cap + 1), dtype=np.float32)
+    for j in range(1, cap + 1):
+        out[4 * j] = lr
+        out[4 * j + 1] = -lr * weight_decay
+    return out
+
+
+def adagrad_step_scalars(lr: float, lr_decay: float, cap: int) -> np.ndarray:
+    """float32[4*(cap+1)]: entry j = (clr_j, 0, 0, 0) with clr_j = lr / (1 + (j - 1) * lr_decay) in Python double, as
+    torch/optim/adagrad.py computes it."""
+    out = np.zeros(4 * (cap + 1), dtype=np.float32)
+    out[4::4] = lr / (1 + np.arange(cap, dtype=np.float64) * lr_decay)     # (numpy float64: Python's double arithmetic)
+    return out
+
+
+def rmsprop_step_scalars(lr: float, cap: int) -> np.ndarray:
+    """float32[4*(cap+1)]: entry j = (lr, 0, 0, 0)."""
+    out = np.zeros(4 * (cap + 1), dtype=np.float32)
+    out[4::4] = lr
+    return out
+
+
 class AdamHyper:
     """lr / weight_decay / betas / eps + the device table of per-step scalars (fr_adam in the C ABI)."""
+    learner = LEARNER_ADAM
 
     def __init__(self, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, device="cuda", cap=32768):
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
@@ -81,6 +115,66 @@ class AdamHyper:
                                   "corrections have not saturated; raise `cap`")
 
 
+class _PlainHyper:
+    """The fr_adam struct of a learner whose per-step scalars are constant from step 1 on (lr_decay = 0): a one-entry
+    table.  Same `c()` / `check_step` contract as AdamHyper."""
+    learner = None
+
+    def _finish(self, tab: np.ndarray, cap: int, beta1: float, beta2: float, eps: float, saturated: bool = True):
+        self.cap, self.saturated, self.host_scalars = cap, saturated, tab
+        self.scalars = torch.from_numpy(tab).to(self.device) if self.device.type == "cuda" else None
+        self._c = _C.FrAdam(_C.ptr(self.scalars), cap, self.learner, self.weight_decay, beta1, beta2, eps)
+
+    def c(self) -> "_C.FrAdam":
+        return self._c
+
+    def check_step(self, step: int):
+        if step > self.cap and not self.saturated:
+            raise _C.FairrecError(f"{LEARNER_NAMES[self.learner]} step {step} exceeds the scalar table ({self.cap}); "
+                                  "raise `cap`")
+
+
+class SGDHyper(_PlainHyper):
+    """torch.optim.SGD(params, lr, weight_decay=wd): momentum 0, no state."""
+    learner = LEARNER_SGD
+
+    def __init__(self, lr=1e-3, weight_decay=0.0, device="cuda"):
+        self.lr, self.weight_decay, self.eps = float(lr), float(weight_decay), 0.0
+        self.device = torch.device(device)
+        self._finish(sgd_step_scalars(self.lr, self.weight_decay, 1), 1, 0.0, 0.0, 0.0)
+
+
+class AdagradHyper(_PlainHyper):
+    """torch.optim.Adagrad(params, lr, weight_decay=wd): eps 1e-10, initial_accumulator_value 0; state `sum`.  With
+    lr_decay > 0 the table holds clr_j for j <= cap (grown until clr stops changing in fp32, or 2^22 steps)."""
+    learner = LEARNER_ADAGRAD
+
+    def __init__(self, lr=1e-2, lr_decay=0.0, weight_decay=0.0, eps=1e-10, device="cuda", cap=1):
+        self.lr, self.lr_decay, self.weight_decay, self.eps = float(lr), float(lr_decay), float(weight_decay), float(eps)
+        self.device = torch.device(device)
+        if self.lr_decay == 0.0:
+            cap = 1
+        while True:
+            tab = adagrad_step_scalars(self.lr, self.lr_decay, cap)
+            if self.lr_decay == 0.0 or cap >= (1 << 22) or tab[4 * cap] == np.float32(
+                    self.lr / (1 + cap * self.lr_decay)):
+                break
+            cap *= 2
+        saturated = self.lr_decay == 0.0 or bool(tab[4 * cap] == np.float32(self.lr / (1 + cap * self.lr_decay)))
+        self._finish(tab, cap, 0.0, 0.0, self.eps, saturated)
+
+
+class RMSpropHyper(_PlainHyper):
+    """torch.optim.RMSprop(params, lr, weight_decay=wd): alpha 0.99 (fr_adam.beta2), eps 1e-8, momentum 0, not
+    centered; state `square_avg`."""
+    learner = LEARNER_RMSPROP
+
+    def __init__(self, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, device="cuda"):
+        self.lr, self.alpha, self.eps, self.weight_decay = float(lr), float(alpha), float(eps), float(weight_decay)
+        self.device = torch.device(device)
+        self._finish(rmsprop_step_scalars(self.lr, 1), 1, 0.0, self.alpha, self.eps)
+
+
 class LazyTable:
     """An nn.Embedding weight with lazily-applied Adam state (fr_table in the C ABI).
 
@@ -94,6 +188,7 @@ class LazyTable:
         self.n_rows, self.dim = weight.shape
         self.trainable = trainable
         self.step = 0            # optimizer steps applied so far (torch: state['step'])
+        self.learner = LEARNER_ADAM   # the learner of the optimizer that owns the table: which state arrays it keeps
         self.m = self.v = self.last = self.stamp = None
         self.stamp_gen = 0       # bumped whenever the stamps are reset: look-ahead stamping done before is void
         self._ws = None
@@ -111,12 +206,26 @@ class LazyTable:
         if self.last is None:
             self.last = torch.zeros(self.n_rows, dtype=torch.int32, device=dev)
             self.stamp = torch.zeros(self.n_rows, dtype=torch.int32, device=dev)
-        if self.m is None:
+        if self.m is None and self.v is None:
             if self.trainable:
-                self.m = torch.zeros_like(self.weight)
-                self.v = torch.zeros_like(self.weight)
+                # only the state its learner keeps (SGD: none, Adagrad / RMSprop: m; include/fairrec_hip.h)
+                has_m, has_v = (k is not None for k in LEARNER_STATE[self.learner])
+                self.m = torch.zeros_like(self.weight) if has_m else None
+                self.v = torch.zeros_like(self.weight) if has_v else None
             else:  # frozen table: never replayed (last == step == 0), m/v never touched
                 self.m = self.v = self.weight
+
+    def set_learner(self, learner: int):
+        """Bind the table to an optimizer's learner (before its first step): the state arrays are re-allocated for it."""
+        if learner == self.learner:
+            return
+        if self.step != 0:
+            raise _C.FairrecError("a table that has been stepped cannot change its learner")
+        self.learner = learner
+        if self.trainable:
+            self.m = self.v = None
+        self._cstruct_key = None
+        self.ensure_state()
 
     def c(self, step: Optional[int] = None) -> "_C.FrTable":
         self.ensure_state()
@@ -124,9 +233,10 @@ class LazyTable:
         step = self.step if step is None else step
         # the struct is rebuilt only when a buffer moved; per call just the step field changes (callers pass it to the
         # library with byref() before asking for another one)
-        key = (w.data_ptr(), self.m.data_ptr(), self.step_dev.data_ptr() if self.step_dev is not None else 0)
+        m_ptr, v_ptr = _C.ptr(self.m) or 0, _C.ptr(self.v) or 0
+        key = (w.data_ptr(), m_ptr, v_ptr, self.step_dev.data_ptr() if self.step_dev is not None else 0)
         if self._cstruct_key != key:
-            self._cstruct = [_C.FrTable(w.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(),
+            self._cstruct = [_C.FrTable(w.data_ptr(), m_ptr, v_ptr, self.last.data_ptr(),
                                         self.stamp.data_ptr(), self.n_rows, self.dim, 0,
                                         self.step_dev.data_ptr() if self.step_dev is not None else None) for _ in range(2)]
             self._cstruct_key, self._cstruct_turn = key, 0
@@ -353,11 +463,41 @@ class LazyTable:
         self.flush(hyper)
         return {"step": torch.tensor(float(self.step)), "exp_avg": self.m, "exp_avg_sq": self.v}
 
+    def optim_state(self, hyper) -> Optional[Dict[str, torch.Tensor]]:
+        """This table's entry of its learner's torch state_dict, flushed to `step`: Adam's as `adam_state`; Adagrad
+        {step, sum}; RMSprop {step, square_avg} once stepped (torch creates it at the first step), else None; SGD None."""
+        if self.learner == LEARNER_ADAM:
+            return self.adam_state(hyper)
+        self.sync_step()
+        self.flush(hyper)
+        name = LEARNER_STATE[self.learner][0]
+        if name is None or (self.learner == LEARNER_RMSPROP and self.step == 0):
+            return None
+        return {"step": torch.tensor(float(self.step)), name: self.m}
+
+    def load_optim_state(self, state: Optional[Dict[str, torch.Tensor]]):
+        """Inverse of `optim_state`; `state` None (SGD, or an RMSprop parameter never stepped) leaves the table current as
+        it stands."""
+        if self.learner == LEARNER_ADAM:
+            return self.load_adam_state(state)
+        self.ensure_state()
+        name = LEARNER_STATE[self.learner][0]
+        if state is not None and name is not None:
+            self.step = int(state["step"])
+            self.m.copy_(state[name])
+        elif self.learner == LEARNER_RMSPROP:
+            self.step = 0
+            self.m.zero_()
+        self._mark_current()
+
     def load_adam_state(self, state: Dict[str, torch.Tensor]):
         self.ensure_state()
         self.step = int(state["step"])
         self.m.copy_(state["exp_avg"])
         self.v.copy_(state["exp_avg_sq"])
+        self._mark_current()
+
+    def _mark_current(self):
         self.last.fill_(self.step)
         self.stamp.zero_()          # stamps name the step of the batch that owns a row: none after a reload
         self.stamp_gen += 1
@@ -389,19 +529,30 @@ class LazyLookup(torch.autograd.Function):
         return None, None, None, None, None, None, None
 
 
-class FusedLazyAdam:
+def _torch_group_keys(cls, **kw) -> dict:
+    """param_groups[0] of the installed torch's optimizer `cls` built with `kw`, without 'params': the keys (and defaults)
+    that version writes into a state_dict."""
+    g = dict(cls([torch.nn.Parameter(torch.zeros(1))], **kw).param_groups[0])
+    g.pop("params")
+    return g
+
+
+class FusedLazyOptimizer:
     """Drop-in for the `optimizer` object the reference Trainer drives (zero_grad / step / state_dict).
 
     The embedding gradient is never materialised: `engine.backward_adam()` does loss.backward()'s embedding part
     + optimizer.step() for the batch of the preceding `calculate_loss`.  Dense parameters (MLPs, biases)
     registered with the engine go through fr_adam_dense.  `group` restricts the optimizer to a subset of the
-    engine's tensors (PFCN's optimizer_filter / optimizer_dis, trainer.py:1201-1212).
+    engine's tensors (PFCN's optimizer_filter / optimizer_dis, trainer.py:1201-1212).  The learner is the one of
+    `hyper` (AdamHyper, SGDHyper, AdagradHyper, RMSpropHyper); the subclasses below build it from torch's arguments.
     """
 
-    def __init__(self, engine, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, sweep_period=None, group=None,
-                 clip_grad_norm=None):
+    def __init__(self, engine, hyper, defaults: dict, sweep_period=None, group=None, clip_grad_norm=None):
         self.engine = engine
         self.group = group
+        if hyper.learner != LEARNER_ADAM and not getattr(engine, "lazy_learners", False):
+            raise NotImplementedError(f"learner '{LEARNER_NAMES[hyper.learner]}' runs on the single-device generic engine "
+                                      f"only, not on {type(engine).__name__} (its step is Adam's)")
         # config `clip_grad_norm` = kwargs of torch.nn.utils.clip_grad_norm_, which the reference's loop calls between
         # backward() and step() (trainer.py:194-195); the gradient only exists inside step() here, so it is clipped there
         self.clip = dict(clip_grad_norm) if clip_grad_norm else None
@@ -410,8 +561,9 @@ class FusedLazyAdam:
                 raise NotImplementedError("clip_grad_norm: this model's engine has no global-gradient-norm pass yet")
             if float(self.clip.get("norm_type", 2)) != 2.0:
                 raise NotImplementedError("clip_grad_norm: only norm_type 2 is on the device path")
-        self.hyper = AdamHyper(lr, weight_decay, betas, eps, device=engine.device)
-        self.defaults = dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)
+        self.hyper = hyper
+        self.learner = hyper.learner
+        self.defaults = defaults
         if group is None:
             engine.bind_optimizer(self, sweep_period)
         else:
@@ -434,16 +586,28 @@ class FusedLazyAdam:
     def _tables(self):
         return self.engine.tables(self.group) if self.group is not None else self.engine.tables()
 
+    def _torch_groups(self) -> dict:
+        return dict(self.defaults, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False,
+                    fused=None)
+
     def state_dict(self, param_names=None):
-        """torch.optim.Adam's state_dict content (`exp_avg`, `exp_avg_sq`, `step` per parameter, flushed to the current
-        step).  Keys: parameter NAMES by default; with `param_names` (the names of the parameters in the order the
-        reference hands them to its optimizer, i.e. `[n for n, _ in model.named_parameters()]`) torch's own layout --
-        integer indices and `param_groups[0]['params'] = [0, 1, ...]` -- which a reference `optimizer.load_state_dict`
-        accepts as it is (trainer.py:221-240, :258-284)."""
-        state = {name: t.adam_state(self.hyper) for name, t in self._tables().items()}
+        """torch.optim.<Learner>'s state_dict content, flushed to the current step (Adam: `exp_avg`, `exp_avg_sq`, `step`;
+        Adagrad: `sum`, `step`; RMSprop: `square_avg`, `step` for the stepped parameters; SGD: none).  Keys: parameter
+        NAMES by default; with `param_names` (the names of the parameters in the order the reference hands them to its
+        optimizer, i.e. `[n for n, _ in model.named_parameters()]`) torch's own layout -- integer indices and
+        `param_groups[0]['params'] = [0, 1, ...]` -- which the reference's `optimizer.load_state_dict` accepts as it is
+        (trainer.py:221-240, :258-284)."""
+        state = {name: t.optim_state(self.hyper) for name, t in self._tables().items()}
         if hasattr(self.engine, "dense_state"):
             state.update(self.engine.dense_state(self.group) if self.group is not None else self.engine.dense_state())
+        state = {n: st for n, st in state.items() if st is not None}
         if param_names is not None:
+            if self.learner == LEARNER_ADAGRAD:
+                # torch.optim.Adagrad creates the state of EVERY parameter at construction (step 0, sum 0)
+                for n in param_names:
+                    like = self._param_like(n)
+                    if n not in state and like is not None:
+                        state[n] = {"step": torch.tensor(0.0), "sum": torch.zeros_like(like)}
             idx = {n: k for k, n in enumerate(param_names)}
             missing = [n for n in state if n not in idx]
             if missing:
@@ -452,13 +616,19 @@ class FusedLazyAdam:
             # torch lists EVERY parameter the optimizer was built on, in order, and keeps state only for those that were
             # stepped (a frozen table -- NFCF's user table after reset_params, FairGo's tables in the finetune stage -- has
             # an index and no state); load_state_dict maps saved ids to parameters by POSITION and checks the group length
-            groups = dict(self.defaults, params=list(range(len(param_names))), amsgrad=False, maximize=False, foreach=None,
-                          capturable=False, differentiable=False, fused=None)
+            groups = dict(self._torch_groups(), params=list(range(len(param_names))))
             return {"state": state, "param_groups": [groups]}
         return {"state": state, "param_groups": [dict(self.defaults, params=list(state.keys()))]}
 
+    def _param_like(self, name):
+        w = getattr(self.engine, "_weights", {}).get(name)
+        if w is not None:
+            return w.data
+        d = getattr(self.engine, "_dense", {}).get(name)
+        return d.p.data if d is not None else None
+
     def load_state_dict(self, sd, param_names=None):
-        """Accepts this class's name-keyed layout and torch.optim.Adam's integer-keyed one (a checkpoint written by the
+        """Accepts this class's name-keyed layout and torch.optim.<Learner>'s integer-keyed one (a checkpoint written by the
         reference); the latter needs `param_names`, the parameter names in the reference optimizer's order."""
         tables = self._tables()
         dense = {}
@@ -468,6 +638,14 @@ class FusedLazyAdam:
                 raise KeyError("optimizer state with torch's integer parameter indices: pass param_names "
                                "([n for n, _ in model.named_parameters()]) to name them")
             state = {param_names[k]: st for k, st in state.items()}
+        if self.learner != LEARNER_ADAM:
+            # a table with no entry (SGD; RMSprop never stepped) is current as loaded
+            for name, t in tables.items():
+                t.load_optim_state(state.get(name))
+            dense = {k: st for k, st in state.items() if k not in tables}
+            if hasattr(self.engine, "load_dense_state"):
+                self.engine.load_dense_state(dense, self.group)
+            return
         for name, st in state.items():
             if name in tables:
                 tables[name].load_adam_state(st)
@@ -475,3 +653,56 @@ class FusedLazyAdam:
                 dense[name] = st
         if dense:
             self.engine.load_dense_state(dense)
+
+
+class FusedLazyAdam(FusedLazyOptimizer):
+    """torch.optim.Adam on the lazy tables (learner 'adam')."""
+
+    def __init__(self, engine, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, sweep_period=None, group=None,
+                 clip_grad_norm=None):
+        super().__init__(engine, AdamHyper(lr, weight_decay, betas, eps, device=engine.device),
+                         dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps), sweep_period, group, clip_grad_norm)
+
+
+class FusedLazySGD(FusedLazyOptimizer):
+    """torch.optim.SGD(params, lr, weight_decay) (learner 'sgd'): momentum 0, no state.  Without weight decay a row
+    outside the batch never changes, so nothing is replayed or swept."""
+
+    def __init__(self, engine, lr=1e-3, weight_decay=0.0, sweep_period=None, group=None, clip_grad_norm=None):
+        super().__init__(engine, SGDHyper(lr, weight_decay, device=engine.device),
+                         _torch_group_keys(torch.optim.SGD, lr=lr, weight_decay=weight_decay), sweep_period, group,
+                         clip_grad_norm)
+
+    def _torch_groups(self):
+        return dict(self.defaults)
+
+
+class FusedLazyAdagrad(FusedLazyOptimizer):
+    """torch.optim.Adagrad(params, lr, weight_decay) (learner 'adagrad'): eps 1e-10, initial_accumulator_value 0; state
+    `sum` in the table's m.  Without weight decay a row outside the batch never changes (nothing replayed or swept)."""
+
+    def __init__(self, engine, lr=1e-2, lr_decay=0.0, weight_decay=0.0, eps=1e-10, sweep_period=None, group=None,
+                 clip_grad_norm=None):
+        super().__init__(engine, AdagradHyper(lr, lr_decay, weight_decay, eps, device=engine.device),
+                         _torch_group_keys(torch.optim.Adagrad, lr=lr, lr_decay=lr_decay, weight_decay=weight_decay, eps=eps),
+                         sweep_period, group, clip_grad_norm)
+
+    def _torch_groups(self):
+        return dict(self.defaults)
+
+
+class FusedLazyRMSprop(FusedLazyOptimizer):
+    """torch.optim.RMSprop(params, lr, weight_decay) (learner 'rmsprop'): alpha 0.99, eps 1e-8, momentum 0, not
+    centered; state `square_avg` in the table's m.  A replayed step decays square_avg (and, with weight decay, p)."""
+
+    def __init__(self, engine, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, sweep_period=None, group=None,
+                 clip_grad_norm=None):
+        super().__init__(engine, RMSpropHyper(lr, alpha, eps, weight_decay, device=engine.device),
+                         _torch_group_keys(torch.optim.RMSprop, lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay),
+                         sweep_period, group, clip_grad_norm)
+
+    def _torch_groups(self):
+        return dict(self.defaults)
+
+
+FUSED_LAZY = {"adam": FusedLazyAdam, "sgd": FusedLazySGD, "adagrad": FusedLazyAdagrad, "rmsprop": FusedLazyRMSprop}

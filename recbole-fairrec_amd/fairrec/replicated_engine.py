@@ -41,6 +41,8 @@ class _ReplicatedLookup(torch.autograd.Function):
 
 
 class ReplicatedGenericEngine(GenericEngine):
+    lazy_learners = False     # its steps run Adam's kernels only (fairrec.optim.FusedLazyOptimizer)
+
     def __init__(self, device, group=None, ops=None):
         self.pg = group
         self.G = dist.get_world_size(group)

@@ -193,6 +193,8 @@ class _ShardedLookup(torch.autograd.Function):
 
 
 class ShardedGenericEngine(GenericEngine):
+    lazy_learners = False     # its steps run Adam's kernels only (fairrec.optim.FusedLazyOptimizer)
+
     def clip_grad_norm(self, max_norm: float, group=None):
         """GenericEngine.clip_grad_norm on row-sharded tables: the gradient of a table is held by the owners of its rows
         (the rows every requester sent back, duplicates summed per owned row in slot order: requester rank, then batch

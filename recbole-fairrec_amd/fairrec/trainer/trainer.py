@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import _C
-from ..optim import FusedLazyAdam
+from ..optim import FUSED_LAZY, FusedLazyAdam
 from ..sampler import host_numpy_stream
 from ..utils import calculate_valid_score, dict2str, early_stopping, ensure_dir, get_local_time
 
@@ -68,18 +68,39 @@ class Trainer(AbstractTrainer):
 
     # --- optimizer ----------------------------------------------------------------------------------------
     def _build_optimizer(self, **kwargs):
-        """reference trainer.py:114-153.  Only learner 'adam' runs on the fused HIP path (the only learner the
-        reference's fair-model configs use)."""
+        """reference trainer.py:114-153: `learner` adam / sgd / adagrad / rmsprop (case-insensitive) with lr and
+        weight_decay, torch's defaults otherwise.  sgd / adagrad / rmsprop run on the single-device generic engine only
+        (FOCF's fused step and the multi-GPU engines are Adam's: NotImplementedError).  sparse_adam raises ValueError: the
+        reference's torch.optim.SparseAdam cannot step on the dense gradients these models produce.  Any other name warns
+        and falls back to Adam without weight decay, as the reference does."""
         learner = kwargs.pop('learner', self.learner)
         learning_rate = kwargs.pop('learning_rate', self.learning_rate)
         weight_decay = kwargs.pop('weight_decay', self.weight_decay)
         engine = kwargs.pop('engine', None) or self.model.hip_engine()
+        group = kwargs.pop('group', None)
         if engine is None:
             raise NotImplementedError(f'{type(self.model).__name__} exposes no HIP engine')
-        if learner.lower() != 'adam':
-            raise NotImplementedError(f"learner '{learner}' is not on the MI355X hot path yet (adam only)")
-        return FusedLazyAdam(engine, lr=learning_rate, weight_decay=weight_decay,
-                             sweep_period=self.config['lazy_adam_sweep_period'], clip_grad_norm=self.clip_grad_norm)
+        extra = {} if group is None else {'group': group}
+        cls = self._learner_class(learner)
+        if cls is None:
+            weight_decay = 0.0
+            cls = FusedLazyAdam
+        if cls is not FusedLazyAdam and not getattr(engine, 'lazy_learners', False):
+            raise NotImplementedError(f"learner '{learner}' is not on the MI355X hot path for {type(engine).__name__} "
+                                      "(its optimizer step is Adam's): use learner adam")
+        return cls(engine, lr=learning_rate, weight_decay=weight_decay, sweep_period=self.config['lazy_adam_sweep_period'],
+                   clip_grad_norm=self.clip_grad_norm, **extra)
+
+    def _learner_class(self, learner):
+        """The fused optimizer class of a `learner` config value; None = unknown (the reference warns and uses Adam)."""
+        name = (learner or 'adam').lower()
+        if name == 'sparse_adam':
+            raise ValueError("learner 'sparse_adam': the reference's torch.optim.SparseAdam cannot step on the dense "
+                             "embedding gradients these models produce (it fails at the first step); use adam")
+        if name not in FUSED_LAZY:
+            self.logger.warning('Received unrecognized optimizer, set default Adam optimizer')
+            return None
+        return FUSED_LAZY[name]
 
     # --- training -----------------------------------------------------------------------------------------
     def _graphed_step(self, key, loss_fn):
@@ -469,13 +490,7 @@ class PFCNTrainer(Trainer):
         group = kwargs.pop('group', None)
         if group is None and self.filter_mode != 'none':
             return None           # the reference's default optimizer is never stepped when filters are on (PFCN, FairGo)
-        from ..optim import FusedLazyAdam
-        if (kwargs.get('learner', self.learner) or 'adam').lower() != 'adam':
-            raise NotImplementedError('only learner adam is on the MI355X hot path')
-        return FusedLazyAdam(self.model.hip_engine(), lr=kwargs.get('learning_rate', self.learning_rate),
-                             weight_decay=kwargs.get('weight_decay', self.weight_decay),
-                             sweep_period=self.config['lazy_adam_sweep_period'], group=group,
-                             clip_grad_norm=self.clip_grad_norm)
+        return Trainer._build_optimizer(self, group=group, **kwargs)
 
     def _train_epoch(self, train_data, epoch_idx, loss_func=None, show_progress=False):
         dis_loss, filter_loss = 0., 0.
