@@ -7,11 +7,14 @@ already resident in HBM.  Workload: FOCF, fair_objective=value, 1 000 001 users 
 embedding_size 64, B = 8192 per GPU, Adam lr 1e-3 with the reference's coupled weight_decay 1e-3
 (SURVEY.md §8-d cfg 2; uniform-random pairs = the figure of record).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns torch.distributed.run itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] (N > 1 without a launcher: spawns torch.distributed.run itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --workload nfcf100m [--gpus N]               (BASELINE.json configs[4]: NFCF finetune, tables row-sharded)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain FOCF run sets up, ages the optimizer state, warms up, times the K steps, writes
+--dump-outputs and prints the headline; `roofline` and `config.launch_modes_timed` are null.  `--full` adds what takes runs of
+its own: the other launch modes, the per-kernel `roofline`, the other batch shapes, `trainer_fit`, `next_rows`, the other
+BASELINE workloads, `cpu_baseline` (and with N > 1 the NFCF configs[4] block).
 """
 import argparse
 import json
@@ -583,11 +586,16 @@ def main():
                          "(host preparation of the run + three stage launches, ~0.1 ms) that the trainer spreads over runs of 256 "
                          "steps and a 20-step timed region cannot")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly (= --launch eager; the N > 1 path: no hipGraph)")
-    ap.add_argument("--graph-only", action="store_true", help="do not also time the other launch modes (single-GPU default: all three)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the grouped / zipf blocks of the default FOCF run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the other launch modes, the per-kernel "
+                         "roofline, the grouped / zipf shapes, trainer_fit, next_rows, the other BASELINE workloads, the CPU "
+                         "baseline (N > 1: the NFCF configs[4] block).  Without it a FOCF run reports the headline only")
+    ap.add_argument("--graph-only", action="store_true",
+                    help="--full: do not also time the other launch modes (single GPU: all three otherwise)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline block")
+    ap.add_argument("--no-shapes", action="store_true", help="--full: skip the grouped / zipf blocks of the FOCF run")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the other_workloads block of the default FOCF run (BASELINE configs[2..4] at full size, ~3 min)")
+                    help="--full: skip the other_workloads block of the FOCF run (BASELINE configs[2..4] at full size, ~3 min)")
     ap.add_argument("--item-dist", default="uniform", choices=["uniform", "zipf", "grouped", "unique"])
     ap.add_argument("--sweep", type=int, default=None, help="lazy-Adam sweep period (default: auto)")
     ap.add_argument("--force-sharded", action="store_true", help="use the row-sharded engine even on one GPU")
@@ -737,8 +745,8 @@ def main():
         launch_mode = "library" if K >= 64 else "graph"
         if launch_mode == "graph":
             auto_note = (f"--launch auto with {K} timed steps: one hipGraph replay; the library's step loop (the trainer's path, "
-                         "timed beside it in launch_modes_timed and over 1024 steps in trainer_fit) pays ~0.1 ms per CALL, "
-                         "which its runs of 256 steps absorb and a 20-step region does not")
+                         "timed by --full beside it in launch_modes_timed and over 1024 steps in trainer_fit) pays ~0.1 ms per "
+                         "CALL, which its runs of 256 steps absorb and a 20-step region does not")
     if sharded and launch_mode == "library":
         launch_mode = "graph"
     if launch_mode == "library" and not eng.can_step_many():
@@ -833,10 +841,10 @@ def main():
     launch = {"library": "library step loop (fr_focf_runs_many)" if (not sharded and eng.item_runs) else "library step loop (fr_focf_steps_many)",
               "graph": "hipGraph" if graph is not None else "eager", "eager": "eager"}[launch_mode]
     other = None
-    if not sharded and not args.graph_only and launch_mode != "eager":
-        # Single-GPU FOCF: `value` is the launch mode named in config.launch (default: the library's step loop); the same K
-        # steps' worth of work in the other launch modes (fresh batches, same distribution) is timed as well and reported in
-        # `config.launch_modes_timed`, for orientation only.
+    if args.full and not sharded and not args.graph_only and launch_mode != "eager":
+        # Single-GPU FOCF: `value` is the launch mode named in config.launch (default: the library's step loop); with --full the
+        # same K steps' worth of work in the other launch modes (fresh batches, same distribution) is timed as well and
+        # reported in `config.launch_modes_timed`, for orientation only.
         key = {"library": "library_loop_ms_per_step", "graph": "hipGraph_ms_per_step"}[launch_mode]
         other = {key: round(dt / K * 1e3, 5)}
 
@@ -900,110 +908,111 @@ def main():
             other["library_loop_ms_per_step"] = round((time.perf_counter() - t0) / K * 1e3, 5)
             eng.check_device_errors()
 
-    # ---- per-kernel device time: K more steps, eager, with the library's HIP-event profiler -----------
+    # ---- per-kernel device time (--full): K more steps, eager, with the library's HIP-event profiler -----------
     roofline = None
-    # every rank runs the extra steps (the collectives need all ranks); rank 0 reports
-    u2, i2, r2, s2 = (t.to(dev) for t in synth_batches(K, BATCH, N_USERS, N_ITEMS, SEED + 7919 + rank, args.item_dist))
-    def profiled_pass(sync_every_step):
-        _C.prof_reset()
-        _C.prof_enable(rank == 0)
-        torch.cuda.synchronize()
-        t_pass = time.perf_counter()
-        for k in range(K):
-            if sharded:
-                nxt = (u2[k + 1], i2[k + 1], s2[k + 1], r2[k + 1]) if k + 1 < K else None
-            else:
-                nxt = coming(k, u2, i2, s2, r2)
-            eng.forward(u2[k], i2[k], r2[k], s2[k], next_batch=nxt)
-            eng.backward_adam()
-            if sync_every_step:
-                torch.cuda.synchronize()
-        torch.cuda.synchronize()
-        t_pass = time.perf_counter() - t_pass
-        _C.prof_enable(False)
-        return (_C.prof_read() if rank == 0 else {}), t_pass
+    if args.full:
+        # every rank runs the extra steps (the collectives need all ranks); rank 0 reports
+        u2, i2, r2, s2 = (t.to(dev) for t in synth_batches(K, BATCH, N_USERS, N_ITEMS, SEED + 7919 + rank, args.item_dist))
+        def profiled_pass(sync_every_step):
+            _C.prof_reset()
+            _C.prof_enable(rank == 0)
+            torch.cuda.synchronize()
+            t_pass = time.perf_counter()
+            for k in range(K):
+                if sharded:
+                    nxt = (u2[k + 1], i2[k + 1], s2[k + 1], r2[k + 1]) if k + 1 < K else None
+                else:
+                    nxt = coming(k, u2, i2, s2, r2)
+                eng.forward(u2[k], i2[k], r2[k], s2[k], next_batch=nxt)
+                eng.backward_adam()
+                if sync_every_step:
+                    torch.cuda.synchronize()
+            torch.cuda.synchronize()
+            t_pass = time.perf_counter() - t_pass
+            _C.prof_enable(False)
+            return (_C.prof_read() if rank == 0 else {}), t_pass
 
-    prof, t_pass = profiled_pass(False)
-    # On one stream the step kernels run one after the other, so a launch cannot be longer than the step the hipGraph replay
-    # just timed.  Seen in about one run in five on a fresh box: the eager pass with event pairs on every launch runs ten
-    # times slower (380 us per 32 us kernel -- the runtime's profiling path, not the kernel).  Such a pass is taken again with
-    # the queue kept empty (a synchronise after every step); if that does not help either, the kernel's time is taken to be
-    # the whole timed step (an upper bound: the step IS that one launch) and the JSON says so.
-    events_ok = True
-    if rank == 0 and not sharded:
-        def step_kernel_us(pr):
-            ms, n = pr.get("focf_step_kernel", (0.0, 0))
-            if os.environ.get("FAIRREC_BENCH_TEST_EVENT_FLAKE"):     # (exercises the two branches below in a test run)
-                ms *= 12
-            return ms / n * 1e3 if n else 0.0
-        if step_kernel_us(prof) > 1.3 * dt / K * 1e6:
-            print(f"[bench] per-launch events inconsistent with the timed step ({step_kernel_us(prof):.1f} us per launch against "
-                  f"{dt / K * 1e6:.1f} us per step); measuring again with an empty queue", file=sys.stderr)
-            prof, t_pass = profiled_pass(True)
+        prof, t_pass = profiled_pass(False)
+        # On one stream the step kernels run one after the other, so a launch cannot be longer than the step the hipGraph replay
+        # just timed.  Seen in about one run in five on a newly started machine: the eager pass with event pairs on every launch
+        # runs ten times slower (380 us per 32 us kernel -- the runtime's profiling path, not the kernel).  Such a pass is taken
+        # again with the queue kept empty (a synchronise after every step); if that does not help either, the kernel's time is
+        # taken to be the whole timed step (an upper bound: the step IS that one launch) and the JSON says so.
+        events_ok = True
+        if rank == 0 and not sharded:
+            def step_kernel_us(pr):
+                ms, n = pr.get("focf_step_kernel", (0.0, 0))
+                if os.environ.get("FAIRREC_BENCH_TEST_EVENT_FLAKE"):     # (exercises the two branches below in a test run)
+                    ms *= 12
+                return ms / n * 1e3 if n else 0.0
             if step_kernel_us(prof) > 1.3 * dt / K * 1e6:
-                events_ok = False
-                ms, n = prof["focf_step_kernel"]
-                prof["focf_step_kernel"] = (dt / K * 1e3 * n, n)
-    if rank == 0:
-        per_kernel = {name: ms / n * 1e3 for name, (ms, n) in prof.items()}   # us per launch
-        # dominant = the longest kernel of the dependent chain gather -> fair -> backward_adam; sort_segments runs on
-        # 2 CUs, one step ahead and concurrently with that chain (fr_focf_prepare), so it is not on the critical path
-        # (sort_segments_kernel and focf_lpt_kernel are the look-ahead prepare: side stream, one launch per 8 batches)
-        chain = {k: v for k, v in per_kernel.items() if k not in ("sort_segments_kernel", "focf_lpt_kernel")} or per_kernel
-        dom = max(chain, key=chain.get)
-        algo_bytes = ALGO_BYTES_PER_INTERACTION * BATCH
-        achieved = algo_bytes / (per_kernel[dom] * 1e-6) / 1e9
-        traffic, traffic_stale = None, None
-        pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc_file):
-            pmc = json.load(open(pmc_file))
-            traffic = pmc.get(dom)
-            # the figure is a stored one (the last profiles/collect.sh pass): say so when the kernel sources have moved since
-            import hashlib
-            src = os.path.join(ROOT, "recbole-fairrec_amd", "csrc")
-            now = hashlib.sha1(b"".join(open(os.path.join(src, f), "rb").read()
-                                        for f in ("focf_step.hip", "focf_ws.hpp", "common.hpp"))).hexdigest()
-            traffic_stale = pmc.get("_kernel_source_sha1") != now
-            if traffic is not None and traffic_stale:
-                print("[bench] roofline.traffic comes from profiles/pmc_traffic.json, collected on OTHER kernel sources than "
-                      "the ones running now: re-run profiles/collect.sh", file=sys.stderr)
-        copy_gbs = stream_copy_ceiling(dev)
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                    # `traffic` is not measured by this run: it is the PMC figure of the last profiles/collect.sh pass
-                    "traffic_source": "profiles/pmc_traffic.json" if traffic is not None else None,
-                    "traffic_stale": traffic_stale if traffic is not None else None,
-                    "measured_copy_ceiling": round(copy_gbs, 1), "frac_of_measured_ceiling": round(achieved / copy_gbs, 4),
-                    "algorithmic_bytes_per_launch": algo_bytes,
-                    # ... plus the launch's slice of the bounded-staleness sweep (rows / period, p m v read and written, last
-                    # written): traffic the lazy update owes for the rows no batch touched -- what `traffic` is to be held against
-                    "sweep_bytes_per_launch": (0 if sharded or not eng._sweep(BATCH) else
-                                               int((N_USERS + N_ITEMS) / eng._sweep(BATCH) * (6 * 4 * DIM + 8))),
-                    # the same bytes over the WHOLE timed step (every launch of the step + gaps): the honest figure
-                    "whole_step_GBps": round(algo_bytes / (dt / K) / 1e9, 1),
-                    "frac_step": round(algo_bytes / (dt / K) / 1e9 / HBM_PEAK_GBS, 4),
-                    # What actually bounds the kernel: with the reference's weight_decay != 0 every row of both
-                    # tables takes one Adam step per training step, replayed lazily without traffic -- (N_users + N_items)
-                    # row-steps of 64 elements per launch at 34 SIMD cycles each (two quarter-rate transcendentals are 32 of
-                    # them; measured with table_flush_kernel), on 1024 SIMDs at 2.4 GHz.  Informative only: `frac` stays the
-                    # HBM figure the contract asks for.
-                    "valu_floor_us_per_launch": (None if sharded else
-                                                 round((N_USERS + N_ITEMS) * (DIM / 64) * 34 / (1024 * 2.4e9) * 1e6, 2)),
-                    "frac_of_valu_floor": (None if sharded else
-                                           round((N_USERS + N_ITEMS) * (DIM / 64) * 34 / (1024 * 2.4e9) * 1e6 / per_kernel[dom], 4)),
-                    "kernel_us": {k: round(v, 2) for k, v in sorted(per_kernel.items())},
-                    "dominant_rule": ("longest kernel of the dependent chain; sort_segments_kernel runs on 1-2 workgroups "
-                                      "concurrently with the gather kernels on a side stream" if sharded else
-                                      ("the step IS one kernel (focf_step_kernel), and the index work of the two coming "
-                                       "batches rides in it as ~100 extra workgroups (claim / place stages); "
-                                       "focf_stage_kernel = those stages on their own launch for the first two batches of a loop"
-                                       if getattr(eng, "staged", False) else
-                                       "the step IS one kernel (focf_step_kernel); sort_segments_kernel + focf_lpt_kernel run "
-                                       "twice per 16 steps on a side stream, ahead of the steps they serve")),
-                    "measured": ("" if events_ok else "FALLBACK for focf_step_kernel: the timed step itself (per-launch events "
-                                 "were inconsistent in this run, twice); otherwise ") +
-                                f"hipExtLaunchKernelGGL start/stop events on every launch, {K} eager steps after the "
-                                "timed region (same look-ahead sort overlap as the timed steps)"}
+                print(f"[bench] per-launch events inconsistent with the timed step ({step_kernel_us(prof):.1f} us per launch against "
+                      f"{dt / K * 1e6:.1f} us per step); measuring again with an empty queue", file=sys.stderr)
+                prof, t_pass = profiled_pass(True)
+                if step_kernel_us(prof) > 1.3 * dt / K * 1e6:
+                    events_ok = False
+                    ms, n = prof["focf_step_kernel"]
+                    prof["focf_step_kernel"] = (dt / K * 1e3 * n, n)
+        if rank == 0:
+            per_kernel = {name: ms / n * 1e3 for name, (ms, n) in prof.items()}   # us per launch
+            # dominant = the longest kernel of the dependent chain gather -> fair -> backward_adam; sort_segments runs on
+            # 2 CUs, one step ahead and concurrently with that chain (fr_focf_prepare), so it is not on the critical path
+            # (sort_segments_kernel and focf_lpt_kernel are the look-ahead prepare: side stream, one launch per 8 batches)
+            chain = {k: v for k, v in per_kernel.items() if k not in ("sort_segments_kernel", "focf_lpt_kernel")} or per_kernel
+            dom = max(chain, key=chain.get)
+            algo_bytes = ALGO_BYTES_PER_INTERACTION * BATCH
+            achieved = algo_bytes / (per_kernel[dom] * 1e-6) / 1e9
+            traffic, traffic_stale = None, None
+            pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc_file):
+                pmc = json.load(open(pmc_file))
+                traffic = pmc.get(dom)
+                # the figure is a stored one (the last profiles/collect.sh pass): say so when the kernel sources have moved since
+                import hashlib
+                src = os.path.join(ROOT, "recbole-fairrec_amd", "csrc")
+                now = hashlib.sha1(b"".join(open(os.path.join(src, f), "rb").read()
+                                            for f in ("focf_step.hip", "focf_ws.hpp", "common.hpp"))).hexdigest()
+                traffic_stale = pmc.get("_kernel_source_sha1") != now
+                if traffic is not None and traffic_stale:
+                    print("[bench] roofline.traffic comes from profiles/pmc_traffic.json, collected on OTHER kernel sources than "
+                          "the ones running now: re-run profiles/collect.sh", file=sys.stderr)
+            copy_gbs = stream_copy_ceiling(dev)
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                        # `traffic` is not measured by this run: it is the PMC figure of the last profiles/collect.sh pass
+                        "traffic_source": "profiles/pmc_traffic.json" if traffic is not None else None,
+                        "traffic_stale": traffic_stale if traffic is not None else None,
+                        "measured_copy_ceiling": round(copy_gbs, 1), "frac_of_measured_ceiling": round(achieved / copy_gbs, 4),
+                        "algorithmic_bytes_per_launch": algo_bytes,
+                        # ... plus the launch's slice of the bounded-staleness sweep (rows / period, p m v read and written, last
+                        # written): traffic the lazy update owes for the rows no batch touched -- what `traffic` is to be held against
+                        "sweep_bytes_per_launch": (0 if sharded or not eng._sweep(BATCH) else
+                                                   int((N_USERS + N_ITEMS) / eng._sweep(BATCH) * (6 * 4 * DIM + 8))),
+                        # the same bytes over the WHOLE timed step (every launch of the step + gaps): the honest figure
+                        "whole_step_GBps": round(algo_bytes / (dt / K) / 1e9, 1),
+                        "frac_step": round(algo_bytes / (dt / K) / 1e9 / HBM_PEAK_GBS, 4),
+                        # What actually bounds the kernel: with the reference's weight_decay != 0 every row of both
+                        # tables takes one Adam step per training step, replayed lazily without traffic -- (N_users + N_items)
+                        # row-steps of 64 elements per launch at 34 SIMD cycles each (two quarter-rate transcendentals are 32 of
+                        # them; measured with table_flush_kernel), on 1024 SIMDs at 2.4 GHz.  Informative only: `frac` stays the
+                        # HBM figure the contract asks for.
+                        "valu_floor_us_per_launch": (None if sharded else
+                                                     round((N_USERS + N_ITEMS) * (DIM / 64) * 34 / (1024 * 2.4e9) * 1e6, 2)),
+                        "frac_of_valu_floor": (None if sharded else
+                                               round((N_USERS + N_ITEMS) * (DIM / 64) * 34 / (1024 * 2.4e9) * 1e6 / per_kernel[dom], 4)),
+                        "kernel_us": {k: round(v, 2) for k, v in sorted(per_kernel.items())},
+                        "dominant_rule": ("longest kernel of the dependent chain; sort_segments_kernel runs on 1-2 workgroups "
+                                          "concurrently with the gather kernels on a side stream" if sharded else
+                                          ("the step IS one kernel (focf_step_kernel), and the index work of the two coming "
+                                           "batches rides in it as ~100 extra workgroups (claim / place stages); "
+                                           "focf_stage_kernel = those stages on their own launch for the first two batches of a loop"
+                                           if getattr(eng, "staged", False) else
+                                           "the step IS one kernel (focf_step_kernel); sort_segments_kernel + focf_lpt_kernel run "
+                                           "twice per 16 steps on a side stream, ahead of the steps they serve")),
+                        "measured": ("" if events_ok else "FALLBACK for focf_step_kernel: the timed step itself (per-launch events "
+                                     "were inconsistent in this run, twice); otherwise ") +
+                                    f"hipExtLaunchKernelGGL start/stop events on every launch, {K} eager steps after the "
+                                    "timed region (same look-ahead sort overlap as the timed steps)"}
 
     if rank == 0:
         total = K * BATCH * world
@@ -1037,7 +1046,7 @@ def main():
                        "aged_steps": None if sharded else n_age},
             "roofline": roofline,
         }
-        if world == 1 and not sharded and args.item_dist == "uniform" and not args.no_shapes:
+        if args.full and world == 1 and not sharded and args.item_dist == "uniform" and not args.no_shapes:
             # the figure of record is the uniform run above; the item-complete shape FOCF's real loader
             # produces (and a popularity-skewed one) are reported next to it, each under the bytes definition it names
             if graph is not None:
@@ -1056,9 +1065,9 @@ def main():
                 out["next_rows"] = {"error": f"{type(e).__name__}: {e}"}
             if not args.no_workloads:
                 out["other_workloads"] = other_workloads_block(args, dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
-    if (world > 1 or os.environ.get("FAIRREC_BENCH_NFCF_BLOCK") == "1") and not args.no_shapes:      # (the env: this code path on one GPU)
+    if args.full and (world > 1 or os.environ.get("FAIRREC_BENCH_NFCF_BLOCK") == "1") and not args.no_shapes:   # (the env: on one GPU)
         # BASELINE.json configs[4] next to the FOCF line: the config the >= 6 x scaling target is stated on (NFCF finetune,
         # 100 000 001 x 10 000 001, D = 256, both tables row-sharded over the ranks).  Every rank runs it; rank 0 reports.
         if graph is not None:

@@ -7,7 +7,7 @@ for lib in "$@"; do
   for ch in 0 1; do
     tag=$(basename $lib .so)_ch$ch
     if [ "$lib" = main ]; then unset FAIRREC_HIP_LIB; else export FAIRREC_HIP_LIB=$PWD/$lib; fi
-    FAIRREC_FOCF_CHAIN=$ch timeout 300 python bench.py --no-shapes --no-cpu-baseline $BENCH_ARGS > $out/$tag.json 2> $out/$tag.err
+    FAIRREC_FOCF_CHAIN=$ch timeout 300 python bench.py --full --no-shapes --no-cpu-baseline $BENCH_ARGS > $out/$tag.json 2> $out/$tag.err
     echo "$tag rc=$? $(python -c "
 import json,sys
 try:

@@ -8,7 +8,7 @@ from fairrec import _C
 lib = ctypes.CDLL(_C.LIB_PATH)
 target = int(os.environ.get("TRACE_STEP", "250"))
 assert lib.fr_debug_set_trace_step(target) == 0
-sys.argv = ["bench.py", "--no-cpu-baseline", "--graph-only"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--graph-only"] + sys.argv[1:]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     bench.main()

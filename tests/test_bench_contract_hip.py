@@ -1,5 +1,6 @@
 """bench.py's one-line JSON contract (task statement + ④): run a short bench on the GPU and check the fields the driver and
-the judge read.  Also the item-complete distribution (the shape FOCFDataLoader produces) and the eager-only mode."""
+the judge read, in a plain run (the headline only) and with --full (every block).  Also the item-complete distribution (the
+shape FOCFDataLoader produces) and the eager-only mode."""
 import json
 import os
 import subprocess
@@ -11,13 +12,37 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--age", "8",
-                          "--no-cpu-baseline", *args], capture_output=True, text=True, timeout=600, cwd=ROOT)
+def _line(*args):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--age", "8", *args],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]          # ONE JSON line
     return json.loads(lines[0])
+
+
+def _bench(*args):
+    return _line("--no-cpu-baseline", *args)
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                 "vs_baseline", "dtype", "data", "config", "roofline")
+FULL_ONLY_BLOCKS = ("other_batch_shapes", "trainer_fit", "next_rows", "other_workloads", "cpu_baseline", "nfcf100m")
+
+
+def test_bench_plain_line():
+    """Without --full (`bench.py --gpus 1 --steps K --warmup W`) the run ends at the headline: the same headline fields, and
+    nothing that takes runs of its own -- no other launch modes, no per-kernel roofline, no other shapes or workloads, no
+    CPU baseline."""
+    d = _line("--gpus", "1")
+    assert set(HEADLINE_KEYS) <= set(d) and not set(FULL_ONLY_BLOCKS) & set(d), sorted(d)
+    assert d["metric"].startswith("training interactions/sec") and "FOCF emb=64" in d["metric"]
+    assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["unit"] == "interactions/s" and d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 12 * 8192 / (d["ms_per_step"] * 12e-3)) <= 1e-3 * d["value"]
+    assert d["roofline"] is None and d["config"]["launch_modes_timed"] is None
+    assert d["config"]["launch"] == "hipGraph" and d["config"]["aged_steps"] == 8
+    assert d["config"]["final_loss"] == d["config"]["final_loss"]      # not NaN
 
 
 SMALL = ("--users", "200001", "--items", "50001", "--nfcf-users", "200001", "--nfcf-items", "50001")   # the other_workloads tables
@@ -27,9 +52,8 @@ SMALL = ("--users", "200001", "--items", "50001", "--nfcf-users", "200001", "--n
                                   ("--launch", "library", "--no-workloads"), ("--launch", "library", "--item-dist", "grouped")],
                          ids=["default", "grouped", "eager", "graph", "library", "library_grouped"])
 def test_bench_json_contract(args):
-    d = _bench(*args)
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-              "vs_baseline", "dtype", "data", "config", "roofline"):
+    d = _bench("--full", *args)
+    for k in HEADLINE_KEYS:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 2 and d["higher_is_better"] is True
     assert d["unit"] == "interactions/s" and d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None
@@ -63,7 +87,7 @@ def test_bench_json_contract(args):
         assert "auto" in d["config"]["launch_note"]
     assert d["config"]["launch"].startswith(mode), d["config"]["launch"]
     if args is SMALL:
-        # BASELINE.json configs[2..4] ride in the default line (here on small tables): ms per step, rate, roofline of each
+        # BASELINE.json configs[2..4] ride in the --full line (here on small tables): ms per step, rate, roofline of each
         modes = d["config"]["launch_modes_timed"]
         assert {"library_loop_ms_per_step", "hipGraph_ms_per_step", "eager_ms_per_step"} <= set(modes)
         assert abs(modes["hipGraph_ms_per_step"] - d["ms_per_step"]) < 1e-4
