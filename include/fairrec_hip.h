@@ -44,6 +44,7 @@ extern "C" {
 
 #define FR_DEV_ERR_BUCKET_OVERFLOW 4u /* a per-owner exchange bucket exceeded its fixed capacity (raise shard_capacity) */
 #define FR_DEV_ERR_PIPE_WAIT 8u     /* fr_focf_step_runs_pipe: a row of the previous batch was not published within the wait bound */
+#define FR_DEV_ERR_SAMPLE_ROUNDS 16u /* fr_sample_negatives_pop*: a call still had positions open after its round cap (2^20) */
 
 /* FOCF fairness objectives -- FOCF.get_loss_fun, focf.py:50-68 */
 enum fr_focf_objective {
@@ -892,6 +893,35 @@ FR_API int fr_sample_negatives_calls(uint32_t* state, int64_t low, int64_t high,
                                      const int64_t* call_offsets, int64_t n_calls, int64_t max_call,
                                      const int64_t* used_indptr, const int32_t* used_items, int64_t n_users, int64_t* out,
                                      void* ws, size_t ws_bytes, uint32_t* err_flag, void* stream);
+/* Popularity-biased negatives: Sampler._pop_sampling (the alias method, sampler.py:72-118) inside the same rejection loop.
+ * The table is the reference's, built on the host in float64 (fairrec/sampler/sampler.py _build_alias_table): n keys in
+ * insertion order, prob[i] and alias[i] of key keys[i] (alias -1 = none, copied into the output as numpy does).
+ * A round over the m positions still open draws idx = np.random.randint(0, n, m) (no words when n == 1), then
+ * coin = np.random.random(m) (2m raw words, fp64), value = keys[idx] if prob[idx] > coin else alias[idx]; the positions
+ * whose value is in the key's used-set, ascending, form the next round.
+ *   fr_sample_negatives_pop       : fr_sample_negatives' semantics with that draw (used_indptr = NULL: a plain
+ *                                   _pop_sampling(n_keys * num), key_ids unused); workspace fr_sample_negatives_workspace_bytes(
+ *                                   n_keys * num).
+ *   fr_sample_negatives_pop_calls : fr_sample_negatives_calls' semantics with that draw, the calls one after the other in one
+ *                                   launch; workspace fr_sample_negatives_workspace_bytes(max_call).  A call longer than
+ *                                   max_call is skipped with FR_DEV_ERR_INDEX_RANGE.
+ * A call that is still open after 2^20 rounds ends the launch with FR_DEV_ERR_SAMPLE_ROUNDS (a used-set covering every key
+ * never terminates in the reference; the host refuses it before launching).  FR_EINVAL for a null table pointer, n < 1,
+ * n - 1 >= 2^32 - 1, bad sizes or a workspace that is too small. */
+typedef struct fr_alias_table {
+    const int64_t* keys;
+    const double* prob;
+    const int64_t* alias;
+    int64_t n;
+} fr_alias_table;
+FR_API int fr_sample_negatives_pop(uint32_t* state, const fr_alias_table* table, const int64_t* key_ids, int64_t n_keys,
+                                   int32_t num, const int64_t* used_indptr, const int32_t* used_items, int64_t n_users,
+                                   int64_t* out, int32_t* rounds_out, void* ws, size_t ws_bytes, uint32_t* err_flag,
+                                   void* stream);
+FR_API int fr_sample_negatives_pop_calls(uint32_t* state, const fr_alias_table* table, const int64_t* call_keys,
+                                         const int64_t* call_offsets, int64_t n_calls, int64_t max_call,
+                                         const int64_t* used_indptr, const int32_t* used_items, int64_t n_users, int64_t* out,
+                                         void* ws, size_t ws_bytes, uint32_t* err_flag, void* stream);
 
 /* ---- the row sets of a frontier-restricted propagation (csrc/frontier.hip) -----------------------------------------------------
  * Which rows of H_l = L H_(l-1) a batch can see (fairgo_pmf.py:196-216 aggregates every layer's rows of the batch's users): the

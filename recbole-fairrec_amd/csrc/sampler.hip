@@ -531,6 +531,177 @@ __global__ __launch_bounds__(SAMPLER_THREADS) void sample_calls_fast_kernel(
     }
 }
 
+// ---- Popularity-biased negatives -------------------------------------------------------------------------------------
+// Replaces: recbole/sampler/sampler.py Sampler._pop_sampling (the alias method over the items of every phase's interactions)
+// inside the same rejection loop of sample_by_key_ids.  A round over the m positions still open draws
+//   idx  = np.random.randint(0, n, m)   -- masked rejection on single words, span n - 1 (no words at all when n == 1)
+//   coin = np.random.random(m)          -- 2m consecutive raw words, coin = ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53 in fp64
+//   value = keys[idx] if prob[idx] > coin else alias[idx]   (alias copied verbatim, -1 included)
+// and the positions whose value is in the key's used-set, in ascending order, form the next round.  The structure is
+// sample_negatives_kernel's: one workgroup runs every round of every call, the state stays in LDS between them.
+// A call that is still open after POP_MAX_ROUNDS rounds stops the launch with FR_DEV_ERR_SAMPLE_ROUNDS instead of spinning:
+// with 32768 positions open that takes a used-set carrying more than 99.998 % of the popularity mass, and a used-set that
+// covers every key (the reference loops forever) is refused on the host before any launch (fairrec/sampler/sampler.py).
+static constexpr int POP_MAX_ROUNDS = 1 << 20;
+
+__global__ __launch_bounds__(SAMPLER_THREADS) void sample_negatives_pop_kernel(
+    uint32_t* __restrict__ state, const int64_t* __restrict__ tab_keys, const double* __restrict__ tab_prob,
+    const int64_t* __restrict__ tab_alias, uint32_t span, uint32_t mask, const int64_t* __restrict__ key_ids,
+    long long n_keys, long long total_all, const int64_t* __restrict__ call_keys, const int64_t* __restrict__ call_offsets,
+    long long n_calls, long long max_call, const int64_t* __restrict__ used_indptr, const int32_t* __restrict__ used_items,
+    long long n_users, int64_t* __restrict__ out_all, int32_t* __restrict__ list_a, int32_t* __restrict__ list_b,
+    int32_t* __restrict__ rounds_out, uint32_t* err) {
+    __shared__ uint32_t mt[2][MT_N];
+    __shared__ int wave_cnt[SAMPLER_THREADS / 64];
+    __shared__ int s_last;
+    __shared__ uint32_t s_carry;      // first word of a coin whose second word lies behind the next twist
+    const int t = threadIdx.x;
+    int cur = 0;
+    if (t < MT_N) mt[0][t] = state[t];
+    int pos = (int)state[MT_N];
+    __syncthreads();
+
+    int rounds = 0;
+    bool stuck = false;
+    const long long calls = call_offsets ? n_calls : 1;
+    for (long long call = 0; call < calls && !stuck; ++call) {
+        const long long o0 = call_offsets ? call_offsets[call] : 0;
+        const long long total = call_offsets ? call_offsets[call + 1] - o0 : total_all;
+        if (total > max_call) {      // (the collision lists hold max_call positions)
+            if (t == 0 && err) atomicOr(err, FR_DEV_ERR_INDEX_RANGE);
+            continue;
+        }
+        int64_t* __restrict__ out = out_all + o0;
+        const long long call_key = call_keys ? call_keys[call] : -1;
+        const int32_t* list = nullptr;      // positions to (re)draw, ascending; nullptr = all of [0, total)
+        int32_t* next = list_a;
+        long long need = total;
+        int call_rounds = 0;
+        while (need > 0) {
+            if (call_rounds == POP_MAX_ROUNDS) {
+                if (t == 0 && err) atomicOr(err, FR_DEV_ERR_SAMPLE_ROUNDS);
+                stuck = true;
+                break;
+            }
+            ++call_rounds;
+            // ---- slots: np.random.randint(0, n, need), the uniform kernel's draw with low = 0 ----
+            if (span == 0) {
+                for (long long e = t; e < need; e += SAMPLER_THREADS) out[list ? (long long)list[e] : e] = 0;
+            } else {
+                long long produced = 0;
+                while (produced < need) {
+                    if (pos == MT_N) {
+                        mt_twist(mt[cur], mt[cur ^ 1], t);
+                        cur ^= 1;
+                        pos = 0;
+                    }
+                    uint32_t v = 0;
+                    bool acc = false;
+                    if (t >= pos && t < MT_N) {
+                        v = mt_temper(mt[cur][t]) & mask;
+                        acc = v <= span;
+                    }
+                    int cnt;
+                    const int k = flag_scan(acc, wave_cnt, cnt);
+                    const long long remaining = need - produced;
+                    if (acc && k < remaining) {
+                        const long long e = produced + k;
+                        out[list ? (long long)list[e] : e] = (long long)v;
+                        if (k == remaining - 1) s_last = t;
+                    }
+                    __syncthreads();
+                    if (cnt >= remaining) {
+                        pos = s_last + 1;
+                        produced = need;
+                    } else {
+                        pos = MT_N;
+                        produced += cnt;
+                    }
+                    __syncthreads();
+                }
+            }
+            __syncthreads();
+            __threadfence_block();
+            // ---- coins: np.random.random(need) = the next 2 * need raw words; word r of the phase is word 2e + (r & 1) of
+            // position e.  A pair split by a twist (the phase can start at either parity) passes its first word on in s_carry.
+            const long long cw = 2 * need;
+            long long cdone = 0;
+            while (cdone < cw) {
+                if (pos == MT_N) {
+                    mt_twist(mt[cur], mt[cur ^ 1], t);
+                    cur ^= 1;
+                    pos = 0;
+                }
+                const int take = (int)(cw - cdone < (long long)(MT_N - pos) ? cw - cdone : (long long)(MT_N - pos));
+                if (t >= pos && t < pos + take) {
+                    const long long r = cdone + (t - pos);
+                    uint32_t w0 = 0, w1 = 0;
+                    bool pair = false;
+                    if ((r & 1) == 0) {
+                        if (t + 1 < pos + take) {
+                            w0 = mt_temper(mt[cur][t]);
+                            w1 = mt_temper(mt[cur][t + 1]);
+                            pair = true;
+                        } else {
+                            s_carry = mt_temper(mt[cur][t]);      // (t == MT_N - 1: the second word is the next block's first)
+                        }
+                    } else if (t == pos) {
+                        w0 = s_carry;
+                        w1 = mt_temper(mt[cur][t]);
+                        pair = true;
+                    }
+                    if (pair) {
+                        const long long e = r >> 1;
+                        const long long i = list ? (long long)list[e] : e;
+                        const long long slot = out[i];
+                        const double coin = ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) / 9007199254740992.0;
+                        out[i] = tab_prob[slot] > coin ? tab_keys[slot] : tab_alias[slot];
+                    }
+                }
+                __syncthreads();
+                pos += take;
+                cdone += take;
+            }
+            ++rounds;
+            if (!used_indptr) break;
+            __threadfence_block();
+            // ---- which of the positions just drawn hit their key's used-set?  (ordered compaction -> next round) ----
+            long long kept = 0;
+            for (long long base = 0; base < need; base += SAMPLER_THREADS) {
+                const long long e = base + t;
+                bool hit = false;
+                long long i = 0;
+                if (e < need) {
+                    i = list ? (long long)list[e] : e;
+                    const long long u = call_keys ? call_key : key_ids[i % n_keys];
+                    if (u < 0 || u >= n_users) {
+                        if (err) atomicOr(err, FR_DEV_ERR_INDEX_RANGE);
+                    } else {
+                        const long long v = out[i];      // (alias -1: never in a used-set)
+                        hit = v >= 0 && used_contains(used_items, used_indptr[u], used_indptr[u + 1], (int)v);
+                    }
+                }
+                int cnt;
+                const int k = flag_scan(hit, wave_cnt, cnt);
+                if (hit) next[kept + k] = (int32_t)i;
+                kept += cnt;
+            }
+            __syncthreads();
+            __threadfence_block();
+            list = next;
+            next = (next == list_a) ? list_b : list_a;
+            need = kept;
+        }
+        __syncthreads();   // the next call reuses the collision lists
+    }
+    __syncthreads();
+    if (t < MT_N) state[t] = mt[cur][t];
+    if (t == 0) {
+        state[MT_N] = (uint32_t)pos;
+        if (rounds_out) rounds_out[0] = rounds;
+    }
+}
+
 // mt19937_seed(state, seed): Knuth's LCG over the 624 words, pos = 624 (np.random.seed(int))
 __global__ void mt19937_seed_kernel(uint32_t* __restrict__ state, uint32_t seed) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -678,4 +849,61 @@ extern "C" int fr_sample_negatives_calls(uint32_t* state, int64_t low, int64_t h
     }
     return sample_launch(state, low, high, nullptr, 1, 0, call_keys, call_offsets, n_calls, max_call, used_indptr, used_items,
                          n_users, out, nullptr, ws, ws_bytes, err_flag, (hipStream_t)stream_);
+}
+
+// ---- popularity-biased negatives: argument checks, then one launch of sample_negatives_pop_kernel ------------------------
+static int pop_launch(uint32_t* state, const fr_alias_table* table, const int64_t* key_ids, int64_t n_keys, int64_t total,
+                      const int64_t* call_keys, const int64_t* call_offsets, int64_t n_calls, int64_t max_call,
+                      const int64_t* used_indptr, const int32_t* used_items, int64_t n_users, int64_t* out,
+                      int32_t* rounds_out, void* ws, size_t ws_bytes, uint32_t* err_flag, hipStream_t stream) {
+    int32_t *la = nullptr, *lb = nullptr;
+    if (used_indptr) {
+        la = (int32_t*)ws;
+        lb = (int32_t*)((char*)ws + align_up((size_t)max_call * sizeof(int32_t), 256));
+    }
+    const uint32_t span = (uint32_t)(table->n - 1);
+    uint32_t mask = span;
+    mask |= mask >> 1;
+    mask |= mask >> 2;
+    mask |= mask >> 4;
+    mask |= mask >> 8;
+    mask |= mask >> 16;
+    ProfScope prof(K_SAMPLE_NEG, stream);
+    FR_LAUNCH(prof, sample_negatives_pop_kernel, dim3(1), dim3(SAMPLER_THREADS), 0, stream, state, table->keys, table->prob,
+              table->alias, span, mask, key_ids, (long long)n_keys, (long long)total, call_keys, call_offsets,
+              (long long)n_calls, (long long)max_call, used_indptr, used_items, (long long)n_users, out, la, lb, rounds_out,
+              err_flag);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+#define FR_CHECK_ALIAS_TABLE(table, who)                                                                                   \
+    FR_CHECK_ARG(table && table->keys && table->prob && table->alias, who ": null table pointer");                          \
+    FR_CHECK_ARG(table->n >= 1 && table->n - 1 < 0xffffffffll, who ": table of %lld keys (1 .. 2^32 - 1)", (long long)table->n)
+
+extern "C" int fr_sample_negatives_pop(uint32_t* state, const fr_alias_table* table, const int64_t* key_ids, int64_t n_keys,
+                                       int32_t num, const int64_t* used_indptr, const int32_t* used_items, int64_t n_users,
+                                       int64_t* out, int32_t* rounds_out, void* ws, size_t ws_bytes, uint32_t* err_flag,
+                                       void* stream_) {
+    FR_CHECK_ALIAS_TABLE(table, "fr_sample_negatives_pop");
+    FR_CHECK_ARG(state && out && n_keys >= 1 && num >= 1 && n_keys <= (1ll << 30) && n_keys * (int64_t)num <= (1ll << 30),
+                 "fr_sample_negatives_pop: bad size");
+    FR_CHECK_ARG(!used_indptr || (used_items && key_ids && n_users >= 1 && ws), "fr_sample_negatives_pop: used-set arguments");
+    const int64_t total = n_keys * (int64_t)num;
+    FR_CHECK_ARG(!used_indptr || ws_bytes >= fr_sample_negatives_workspace_bytes(total), "fr_sample_negatives_pop: workspace too small");
+    return pop_launch(state, table, key_ids, n_keys, total, nullptr, nullptr, 1, total, used_indptr, used_items, n_users, out,
+                      rounds_out, ws, ws_bytes, err_flag, (hipStream_t)stream_);
+}
+
+extern "C" int fr_sample_negatives_pop_calls(uint32_t* state, const fr_alias_table* table, const int64_t* call_keys,
+                                             const int64_t* call_offsets, int64_t n_calls, int64_t max_call,
+                                             const int64_t* used_indptr, const int32_t* used_items, int64_t n_users,
+                                             int64_t* out, void* ws, size_t ws_bytes, uint32_t* err_flag, void* stream_) {
+    FR_CHECK_ALIAS_TABLE(table, "fr_sample_negatives_pop_calls");
+    FR_CHECK_ARG(state && out && call_keys && call_offsets && n_calls >= 1 && max_call >= 1 && max_call <= (1ll << 30),
+                 "fr_sample_negatives_pop_calls: bad size");
+    FR_CHECK_ARG(used_indptr && used_items && n_users >= 1 && ws, "fr_sample_negatives_pop_calls: used-set arguments");
+    FR_CHECK_ARG(ws_bytes >= fr_sample_negatives_workspace_bytes(max_call), "fr_sample_negatives_pop_calls: workspace too small");
+    return pop_launch(state, table, nullptr, 1, 0, call_keys, call_offsets, n_calls, max_call, used_indptr, used_items, n_users,
+                      out, nullptr, ws, ws_bytes, err_flag, (hipStream_t)stream_);
 }

@@ -18,6 +18,7 @@ DEV_ERR_INDEX_RANGE = 1
 DEV_ERR_SST_GROUPS = 2
 DEV_ERR_BUCKET_OVERFLOW = 4
 DEV_ERR_PIPE_WAIT = 8
+DEV_ERR_SAMPLE_ROUNDS = 16
 EUNSUPPORTED = -3      # FR_EUNSUPPORTED
 WGRAD_MAX = 8          # FR_WGRAD_MAX
 
@@ -48,6 +49,10 @@ class FrScorer(Structure):      # include/fairrec_hip.h: fr_scorer
 class FrWgradJob(Structure):    # include/fairrec_hip.h: fr_wgrad_job
     _fields_ = [("dY", c_void_p), ("x0", c_void_p), ("k0", c_int32), ("x1", c_void_p), ("k1", c_int32), ("N", c_int32),
                 ("dW", c_void_p), ("db", c_void_p), ("parts", c_void_p), ("n_parts", c_int32)]
+
+
+class FrAliasTable(Structure):  # include/fairrec_hip.h: fr_alias_table
+    _fields_ = [("keys", c_void_p), ("prob", c_void_p), ("alias", c_void_p), ("n", c_int64)]
 
 
 class FrFocfBatch(Structure):
@@ -151,6 +156,10 @@ _PROTOS = {
     "fr_adam_dense_multi": (c_int, [POINTER(FrDenseDesc), c_int32, POINTER(FrAdam), c_void_p]),
     "fr_sample_negatives_calls": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fr_sample_negatives_pop": (c_int, [c_void_p, POINTER(FrAliasTable), c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                        c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fr_sample_negatives_pop_calls": (c_int, [c_void_p, POINTER(FrAliasTable), c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                              c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "fr_unbucket_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "fr_bucket_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "fr_focf_shard_score": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,

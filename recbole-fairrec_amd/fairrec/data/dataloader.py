@@ -8,6 +8,7 @@ but finds an item's interactions through a CSR built once instead of an O(#inter
 """
 from __future__ import annotations
 
+import copy
 import math
 
 import numpy as np
@@ -337,19 +338,34 @@ class FullSortEvalDataLoader:
         return user_df, history, positive_u, positive_i
 
 
+def eval_neg_sample_args(mode):
+    """RecBole 1.0 configurator `_set_eval_neg_sample_args` for the negative-sampled evaluation modes: 'uniN' ->
+    ('uniform', N), 'popN' -> ('popularity', N); N is parsed with int() as there, so a malformed mode raises its
+    ValueError.  Any other mode (full, labeled) is not a negative-sampled one: NotImplementedError."""
+    mode = mode or ''
+    if mode[:3] == 'uni':
+        return 'uniform', int(mode[3:])
+    if mode[:3] == 'pop':
+        return 'popularity', int(mode[3:])
+    raise NotImplementedError(f"evaluation mode [{mode}]: uniN (uniform negatives), popN (popularity-biased negatives) "
+                              "or full")
+
+
 class NegSampleEvalDataLoader:
-    """general_dataloader.py:68-158 with `eval_args.mode: uniN`: users in id order; per user its positives (dataset order
-    after a stable sort by user) followed by N sampled negatives per positive, drawn user by user from the numpy-compatible
-    device stream (fr_sample_negatives_calls: each user's re-draw rounds complete before the next user draws, exactly like
-    the reference's consecutive sample_by_user_ids calls).  Yields (interaction, row_idx, positive_u, positive_i); how many
+    """general_dataloader.py:68-158 with `eval_args.mode: uniN` or `popN`: users in id order; per user its positives
+    (dataset order after a stable sort by user) followed by N sampled negatives per positive, drawn user by user from the
+    numpy-compatible device stream with the sampler's distribution (Sampler.sample_calls -> fr_sample_negatives_calls /
+    fr_sample_negatives_pop_calls: each user's re-draw rounds complete before the next user draws, exactly like the
+    reference's consecutive sample_by_user_ids calls).  Yields (interaction, row_idx, positive_u, positive_i); how many
     users form a batch follows :100-117."""
 
     def __init__(self, config, dataset, sampler, shuffle=False):
         mode = (config['eval_args'] or {}).get('mode', '')
-        if mode[:3] != 'uni':
-            raise NotImplementedError(f"evaluation mode [{mode}]: uniN (uniform negatives) or full")
+        distribution, self.neg_sample_num = eval_neg_sample_args(mode)
+        if sampler.distribution != distribution:          # the mode decides what is drawn (a copy: `sampler` stays as it is)
+            sampler = copy.copy(sampler)
+            sampler.set_distribution(distribution)
         self.config, self.dataset, self.sampler = config, dataset, sampler
-        self.neg_sample_num = int(mode[3:])
         self.times = 1 + self.neg_sample_num
         self.uid_field, self.iid_field = dataset.uid_field, dataset.iid_field
         self.device = torch.device(config['device'])
@@ -389,8 +405,7 @@ class NegSampleEvalDataLoader:
         dev, N = self.device, self.neg_sample_num
         uids, P, st = self.uid_list[sl], self.counts[sl], self.start[sl]
         Ub = uids.numel()
-        indptr, used_items, _ = self.sampler.used_ids
-        neg = self.sampler.rs.sample_calls(1, self.dataset.item_num, uids, P * N, indptr, used_items)
+        neg = self.sampler.sample_calls(uids, P * N)
         blk = P * self.times
         blk_off = torch.cumsum(blk, 0) - blk
         rows = int(blk.sum())

@@ -80,12 +80,15 @@ def run_recbole(model=None, dataset=None, config_file_list=None, config_dict=Non
     else:
         train_data = TrainDataLoader(config, train_set.to(config['device']) if on_gpu else train_set, shuffle=True)
     eval_mode = (config['eval_args'] or {}).get('mode') or ''
-    if (eval_mode == 'full' or eval_mode[:3] == 'uni') and config['device'].type == 'cuda':
-        # ranking evaluation on the device: top-k and fairness metrics of config['metrics'] (fairrec/evaluator); `uniN`
-        # draws N negatives per positive from the numpy-compatible device stream, `full` ranks the whole catalogue
-        from .data.dataloader import FullSortEvalDataLoader, NegSampleEvalDataLoader
+    if (eval_mode == 'full' or eval_mode[:3] in ('uni', 'pop')) and config['device'].type == 'cuda':
+        # ranking evaluation on the device: top-k and fairness metrics of config['metrics'] (fairrec/evaluator); `uniN` /
+        # `popN` draw N uniform / popularity-biased negatives per positive from the numpy-compatible device stream (the
+        # reference's configurator maps them to eval_neg_sample_args distribution 'uniform' / 'popularity'), `full` ranks
+        # the whole catalogue
+        from .data.dataloader import FullSortEvalDataLoader, NegSampleEvalDataLoader, eval_neg_sample_args
         from .sampler import Sampler
-        phases = Sampler(['train', 'valid', 'test'], [train_set, valid_set, test_set], 'uniform', device=config['device'])
+        distribution = 'uniform' if eval_mode == 'full' else eval_neg_sample_args(eval_mode)[0]
+        phases = Sampler(['train', 'valid', 'test'], [train_set, valid_set, test_set], distribution, device=config['device'])
         loader = FullSortEvalDataLoader if eval_mode == 'full' else NegSampleEvalDataLoader
         valid_data = loader(config, valid_set, phases.set_phase('valid'))
         test_data = loader(config, test_set, phases.set_phase('test'))

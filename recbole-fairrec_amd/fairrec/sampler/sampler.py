@@ -79,7 +79,6 @@ class DeviceRandomState:
                                                   self.err_flag.data_ptr(), _C.current_stream()), "fr_sample_negatives")
         return out
 
-
     def sample_calls(self, low: int, high: int, call_keys: torch.Tensor, call_counts: torch.Tensor,
                      used_indptr: torch.Tensor, used_items: torch.Tensor) -> torch.Tensor:
         """Consecutive single-key calls on this stream in one launch: call c draws call_counts[c] values for key
@@ -103,6 +102,43 @@ class DeviceRandomState:
                                                         used_indptr.numel() - 1, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                         self.err_flag.data_ptr(), _C.current_stream()),
                      "fr_sample_negatives_calls")
+        return out
+
+    def sample_pop(self, table, key_ids: torch.Tensor, num: int, used_indptr: Optional[torch.Tensor],
+                   used_items: Optional[torch.Tensor], rounds_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Popularity-biased negatives (fr_sample_negatives_pop): entry j for key key_ids[j % n], drawn through the alias
+        table `table` (an _C.FrAliasTable of device arrays); used_indptr None = plain draws, no rejection."""
+        key_ids = key_ids.to(self.device, torch.int64).contiguous()
+        n = key_ids.numel()
+        out = torch.empty(n * num, dtype=torch.int64, device=self.device)
+        if n:
+            ws = self._workspace(n * num) if used_indptr is not None else None
+            _C.check(_C.lib().fr_sample_negatives_pop(self.state.data_ptr(), table, key_ids.data_ptr(), n, num,
+                                                      _C.ptr(used_indptr), _C.ptr(used_items),
+                                                      used_indptr.numel() - 1 if used_indptr is not None else 0,
+                                                      out.data_ptr(), _C.ptr(rounds_out), _C.ptr(ws),
+                                                      ws.numel() if ws is not None else 0, self.err_flag.data_ptr(),
+                                                      _C.current_stream()), "fr_sample_negatives_pop")
+        return out
+
+    def sample_calls_pop(self, table, call_keys: torch.Tensor, call_counts: torch.Tensor, used_indptr: torch.Tensor,
+                         used_items: torch.Tensor) -> torch.Tensor:
+        """`sample_calls` with popularity-biased draws (fr_sample_negatives_pop_calls): the calls one after the other in
+        one launch, each finishing its re-draw rounds before the next one draws."""
+        call_keys = call_keys.to(self.device, torch.int64).contiguous()
+        counts = call_counts.to(self.device, torch.int64)
+        offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        total, max_call = int(offsets[-1].item()), int(counts.max().item()) if counts.numel() else 0
+        out = torch.empty(total, dtype=torch.int64, device=self.device)
+        if total:
+            ws = self._workspace(max_call)
+            _C.check(_C.lib().fr_sample_negatives_pop_calls(self.state.data_ptr(), table, call_keys.data_ptr(),
+                                                            offsets.data_ptr(), call_keys.numel(), max_call,
+                                                            used_indptr.data_ptr(), used_items.data_ptr(),
+                                                            used_indptr.numel() - 1, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                            self.err_flag.data_ptr(), _C.current_stream()),
+                     "fr_sample_negatives_pop_calls")
         return out
 
 
@@ -146,8 +182,9 @@ def seed_all(seed: int):
 
 class Sampler:
     """recbole.sampler.Sampler (sampler.py:200-303): negative items per user, never one of the user's positive items
-    of the current or an earlier phase.  Distribution 'uniform' (the reference default, overall.yaml) on the device,
-    'popularity' with numpy on the shared stream."""
+    of the current or an earlier phase.  Both distributions are drawn on the device from the shared numpy-compatible
+    stream: 'uniform' (the reference default, overall.yaml) and 'popularity' (the alias method; the table is built on
+    the host in the reference's float64 arithmetic and uploaded once)."""
 
     def __init__(self, phases, datasets, distribution='uniform', device=None, random_state: Optional[DeviceRandomState] = None):
         if not isinstance(phases, list):
@@ -156,17 +193,22 @@ class Sampler:
             datasets = [datasets]
         if len(phases) != len(datasets):
             raise ValueError(f'Phases {phases} and datasets {datasets} should have the same length.')
-        if distribution not in ('uniform', 'popularity'):
-            raise NotImplementedError(f'The sampling distribution [{distribution}] is not implemented.')
+        self._check_distribution(distribution)
         self.phases, self.datasets, self.distribution = phases, datasets, distribution
         self.uid_field, self.iid_field = datasets[0].uid_field, datasets[0].iid_field
         self.user_num, self.item_num = datasets[0].user_num, datasets[0].item_num
         self.device = torch.device(device if device is not None else "cuda")
         self.rs = random_state if random_state is not None else global_random_state(self.device)
+        self._pop = None
         self.used_ids = self.get_used_ids()
         self.phase = None
         if distribution == 'popularity':
             self._build_alias_table()
+
+    @staticmethod
+    def _check_distribution(distribution):
+        if distribution not in ('uniform', 'popularity'):
+            raise NotImplementedError(f'The sampling distribution [{distribution}] is not implemented.')
 
     def get_used_ids(self):
         """Per phase a CSR (indptr int64 [user_num+1], items int32 sorted per user) of the items used up to and
@@ -182,15 +224,16 @@ class Sampler:
             np.cumsum(counts, out=indptr[1:])
             out[phase] = (torch.from_numpy(indptr).to(self.device), torch.from_numpy(items.astype(np.int32)).to(self.device),
                           int(counts.max()) if len(counts) else 0)
+            self._used_last = (users, items)       # the largest sets (every phase's), for the popularity support guard
         if out and out[self.phases[-1]][2] + 1 >= self.item_num:      # [pad] is an item (sampler.py:258-264)
             raise ValueError('Some users have interacted with all items, which we can not sample negative items for '
                              'them. Please set `user_inter_num_interval` to filter those users.')
         return out
 
-    # --- popularity-biased sampling (sampler.py:72-118): alias method over the items of all phases' interactions.  Not a
-    # device kernel: the draws are numpy's (`randint` for the slot, `random` for the coin), made inside
-    # `host_numpy_stream()` so that they sit at the reference's position of the ONE generator stream the device sampler
-    # shares with numpy -- same ids as the reference, at host speed (the uniform default runs on the device).
+    # --- popularity-biased sampling (sampler.py:72-118): the alias method over the items of all phases' interactions.
+    # The table is built here, on the host, in the reference's float64 arithmetic and dict insertion order (the ids
+    # depend on every bit of it), uploaded once per Sampler (the set_phase copies share it), and drawn from on the device
+    # by fr_sample_negatives_pop* at the reference's position of the ONE stream shared with numpy.
     def _build_alias_table(self):
         from collections import Counter
         cand = []
@@ -215,36 +258,27 @@ class Sampler:
             elif prob[l] > 1:
                 large_q.append(l)
         keys = np.array(list(prob.keys()), dtype=np.int64)
-        self._pop = (keys, np.array([prob[k] for k in keys], dtype=np.float64),
-                     np.array([alias[k] for k in keys], dtype=np.int64))
+        # support guard: a user whose used-set holds every key of the table has nothing left to draw (the reference's
+        # rejection loop never ends for that user); refused here, before any launch.  (An empty table is refused by
+        # fr_sample_negatives_pop at the first draw, where the reference's randint(0, 0) raises.)
+        users, items = self._used_last
+        cover = np.bincount(users[np.isin(items, keys)], minlength=self.user_num)
+        if len(keys) and len(cover) and int(cover.max()) >= len(keys):
+            raise ValueError(f'Some users have interacted with every item of the popularity table ({len(keys)} items), '
+                             'which we can not sample popularity-biased negative items for them. Please set '
+                             '`user_inter_num_interval` to filter those users.')
+        host = (keys, np.array([prob[k] for k in keys], dtype=np.float64), np.array([alias[k] for k in keys], dtype=np.int64))
+        self._pop = tuple(torch.from_numpy(a).to(self.device) for a in host)
+        self._pop_table = _C.FrAliasTable(self._pop[0].data_ptr(), self._pop[1].data_ptr(), self._pop[2].data_ptr(),
+                                          len(keys))
 
-    def _pop_sampling(self, n):
-        keys, prob, alias = self._pop
-        idx = np.random.randint(0, len(keys), n)
-        coin = np.random.random(n)
-        return np.where(prob[idx] > coin, keys[idx], alias[idx])
-
-    def _pop_sample_by_user_ids(self, user_ids, num):
-        indptr, items, _ = self.used_ids
-        if not hasattr(self, "_used_host") or self._used_host[0] is not indptr:
-            self._used_host = (indptr, indptr.cpu().numpy(), items.cpu().numpy().astype(np.int64))
-        _, ip, it = self._used_host
-        keys = np.tile(np.asarray(user_ids.cpu() if torch.is_tensor(user_ids) else user_ids, dtype=np.int64), num)
-        used_key = keys * self.item_num                            # membership in the user's used-set = a sorted (user, item) key
-        allk = np.repeat(np.arange(self.user_num, dtype=np.int64), np.diff(ip)) * self.item_num + it
-        value = np.zeros(len(keys), dtype=np.int64)
-        check = np.arange(len(keys))
-        np.random.set_state(self.rs.get_state())                   # numpy continues the stream where the device mirror stands ...
-        while len(check) > 0:                                      # sample_by_key_ids, sampler.py:178-195
-            value[check] = self._pop_sampling(len(check))
-            k = used_key[check] + value[check]
-            pos = np.searchsorted(allk, k)
-            hit = (pos < len(allk)) & (allk[np.minimum(pos, len(allk) - 1)] == k)
-            check = check[hit]
-        st = np.random.get_state()                                 # ... and hands it back
-        for rs in ([self.rs] if self.rs not in _GLOBAL.values() else list(_GLOBAL.values())):
-            rs.set_state(st)
-        return torch.from_numpy(value).to(self.device)
+    def set_distribution(self, distribution):
+        """sampler.py `set_distribution`: switch between 'uniform' and 'popularity' (the alias table is built on the
+        first switch to 'popularity')."""
+        self._check_distribution(distribution)
+        self.distribution = distribution
+        if distribution == 'popularity' and self._pop is None:
+            self._build_alias_table()
 
     def set_phase(self, phase):
         if phase not in self.phases:
@@ -261,7 +295,18 @@ class Sampler:
             raise ValueError('call set_phase() first')
         if not torch.is_tensor(user_ids):
             user_ids = torch.as_tensor(np.asarray(user_ids), dtype=torch.int64)
-        if self.distribution == 'popularity':
-            return self._pop_sample_by_user_ids(user_ids, int(num))
         indptr, items, _ = self.used_ids
+        if self.distribution == 'popularity':
+            return self.rs.sample_pop(self._pop_table, user_ids, int(num), indptr, items)
         return self.rs.sample_excluding(1, self.item_num, user_ids, int(num), indptr, items)
+
+    def sample_calls(self, call_keys, counts):
+        """Consecutive single-user sample_by_user_ids calls in one launch (the evaluation loader's user-by-user draws):
+        call c draws counts[c] negatives for user call_keys[c] and finishes its re-draw rounds before call c + 1 draws.
+        Returns the concatenation."""
+        if self.phase is None:
+            raise ValueError('call set_phase() first')
+        indptr, items, _ = self.used_ids
+        if self.distribution == 'popularity':
+            return self.rs.sample_calls_pop(self._pop_table, call_keys, counts, indptr, items)
+        return self.rs.sample_calls(1, self.item_num, call_keys, counts, indptr, items)
