@@ -989,6 +989,36 @@ FR_API int fr_eval_lookup_segments(const int64_t* seg_start, int64_t n_users, co
  * [n_rows, n] in host memory; idx_out int64 [n_rows, k] (val_out float [n_rows, k], optional).  For the user rows whose list
  * hangs on an exact score tie; every other row is ranked on the device (csrc/topk_host.hip says why the order can be had). */
 FR_API int fr_topk_like_torch_cpu(const float* rows, int64_t n_rows, int64_t n, int32_t k, int64_t* idx_out, float* val_out);
+/* ---- evaluation by value (`eval_args.mode: labeled`): recbole/evaluator/metrics.py MAE / RMSE / LogLoss / AUC, and GAUC -----------
+ * fr_value_metrics: one streaming pass over score / label (float [n], what `predict` returned and LABEL_FIELD, all batches back
+ *   to back) -> out[0..2] (double) = sum |score - label|, sum (score - label)^2, sum of -y log p - (1 - y) log(1 - p) with
+ *   p = clip(score, 1e-15, 1 - 1e-15) in double; counts[0..1] (int64) = n, number of rows with label == 1.  Double sums in a fixed
+ *   order (per-workgroup partials in ws, folded by a second launch): the same input gives the same bits on every call.
+ * fr_auc_sorted: score_sorted = the score column sorted ascending, label_sorted = the labels in that order (NaN scores: undefined
+ *   result, no fault) -> out[0..2] (int64) = 2U, P, Nn: P rows with label == 1, Nn = n - P, and 2U = sum over the positives of
+ *   C[s_i] + C[e_i], [s_i, e_i) = the run of rows with the positive's score, C[j] = negatives among rows [0, j).  AUC with tied
+ *   scores sharing one threshold (sklearn.metrics.roc_auc_score) = 2U / (2 P Nn), exact integers here; the caller divides.
+ * Both: 1 <= n < 2^31; ws of at least the *_workspace_bytes(n) (0 for an n out of range).  FR_EINVAL (null pointer, n out of
+ *   range, workspace too small) is returned before anything is launched or written.
+ * fr_eval_meanrank_segments: `rec.meanrank` of an evaluation batch, a wave per user (the arguments of fr_eval_topk_segments and
+ *   fr_eval_hits).  User row u's cells are the DISTINCT items among rows [seg_start[u], seg_start[u+1]) (a repeated item counts
+ *   once and carries one score); items == NULL: row j of the segment is the cell of item j (a dense `full` row: seg_start[u] =
+ *   u * n_items).  Its positives are the items of the keys u * n_items + item in pos_keys (SORTED, int64 [n_pos]; a key listed
+ *   twice is one positive; a positive that is no cell of the user is none; a positive scores above -inf).  out int64
+ *   [n_users, 3] = { 2 * pos_rank_sum, user_len, pos_len }: user_len = cells scoring above -inf, pos_len = distinct positives,
+ *   pos_rank_sum = sum over the positives of #{cells greater} + (#{cells equal} + 1) / 2 (1-based descending rank, ties share the
+ *   mean rank).  n_rows = seg_start[n_users]; ws: fr_eval_meanrank_workspace_bytes(n_rows) bytes when items != NULL (may be NULL
+ *   otherwise).  FR_EINVAL before any launch as above. */
+FR_API size_t fr_value_metrics_workspace_bytes(int64_t n);
+FR_API int fr_value_metrics(const float* score, const float* label, int64_t n, double* out, int64_t* counts, void* ws,
+                            size_t ws_bytes, void* stream);
+FR_API size_t fr_auc_sorted_workspace_bytes(int64_t n);
+FR_API int fr_auc_sorted(const float* score_sorted, const float* label_sorted, int64_t n, int64_t* out, void* ws, size_t ws_bytes,
+                         void* stream);
+FR_API size_t fr_eval_meanrank_workspace_bytes(int64_t n_rows);
+FR_API int fr_eval_meanrank_segments(const int64_t* seg_start, int64_t n_users, const int64_t* items, const float* scores,
+                                     const int64_t* pos_keys, int64_t n_pos, int64_t n_items, int64_t n_rows, int64_t* out,
+                                     void* ws, size_t ws_bytes, void* stream);
 FR_API size_t fr_topk_metrics_workspace_bytes(int64_t n_users, int32_t k);
 FR_API int fr_topk_metrics(const int32_t* rec_topk, int64_t n_users, int32_t k, double* out, void* ws, size_t ws_bytes,
                            void* stream);

@@ -277,6 +277,283 @@ __global__ __launch_bounds__(256) void eval_lookup_segments_kernel(const int64_t
     if (live && sub == 0) out[q] = bits ? got : -INFINITY;
 }
 
+// ---- evaluation by value (labeled mode): MAE / RMSE / LogLoss sums and the exact AUC counts ------------------------------------
+// Reference: recbole/evaluator/metrics.py AUC / MAE / RMSE / LogLoss over the concatenated (score, label) columns.
+constexpr int VM_THREADS = 256, VM_ROWS = 2048, VM_MAXBLOCKS = 2048;
+
+__device__ __forceinline__ long long wave_sum_ll(long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// block b walks rows b*256 + t, + blocks*256, ... in that order (a fixed assignment for a given n): part_d[b][0..2] = sum |e|, sum e^2, LogLoss
+// sum of its rows, part_i[b] = its number of rows with label == 1
+__global__ __launch_bounds__(VM_THREADS) void value_partials_kernel(const float* __restrict__ score, const float* __restrict__ label,
+                                                                    long long n, double* __restrict__ part_d,
+                                                                    long long* __restrict__ part_i) {
+    double a = 0.0, q = 0.0, l = 0.0;
+    long long pos = 0;
+    const long long stride = (long long)gridDim.x * VM_THREADS;
+    for (long long j0 = (long long)blockIdx.x * VM_THREADS + threadIdx.x; j0 < n; j0 += 4 * stride) {
+        float sv[4], yv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {                       // the four loads in flight before the first logarithm
+            const long long j = j0 + r * stride;
+            sv[r] = j < n ? score[j] : 0.f;
+            yv[r] = j < n ? label[j] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (j0 + r * stride >= n) break;
+            const double s = (double)sv[r], y = (double)yv[r];
+            const double e = s - y;
+            a += fabs(e);
+            q += e * e;
+            const double p = fmin(fmax(s, 1e-15), 1.0 - 1e-15);
+            l += -y * log(p) - (1.0 - y) * log(1.0 - p);
+            pos += y == 1.0 ? 1 : 0;
+        }
+    }
+    __shared__ double red_d[4][3];
+    __shared__ long long red_i[4];
+    a = wave_sum_d(a);
+    q = wave_sum_d(q);
+    l = wave_sum_d(l);
+    pos = wave_sum_ll(pos);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        red_d[w][0] = a;
+        red_d[w][1] = q;
+        red_d[w][2] = l;
+        red_i[w] = pos;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        part_d[(size_t)blockIdx.x * 3 + threadIdx.x] =
+            ((red_d[0][threadIdx.x] + red_d[1][threadIdx.x]) + red_d[2][threadIdx.x]) + red_d[3][threadIdx.x];
+    if (threadIdx.x == 3) part_i[blockIdx.x] = ((red_i[0] + red_i[1]) + red_i[2]) + red_i[3];
+}
+
+// one block: thread t folds partials t, t + 256, ... in that order, then the fixed butterfly; counts = n, positives
+__global__ __launch_bounds__(VM_THREADS) void value_fold_kernel(const double* __restrict__ part_d, const long long* __restrict__ part_i,
+                                                                int blocks, long long n, double* __restrict__ out,
+                                                                long long* __restrict__ counts) {
+    double v[3] = {0.0, 0.0, 0.0};
+    long long pos = 0;
+    for (int b = threadIdx.x; b < blocks; b += VM_THREADS) {
+        v[0] += part_d[(size_t)b * 3 + 0];
+        v[1] += part_d[(size_t)b * 3 + 1];
+        v[2] += part_d[(size_t)b * 3 + 2];
+        pos += part_i[b];
+    }
+    __shared__ double red_d[4][3];
+    __shared__ long long red_i[4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = wave_sum_d(v[c]);
+    pos = wave_sum_ll(pos);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        red_d[w][0] = v[0];
+        red_d[w][1] = v[1];
+        red_d[w][2] = v[2];
+        red_i[w] = pos;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) out[threadIdx.x] = ((red_d[0][threadIdx.x] + red_d[1][threadIdx.x]) + red_d[2][threadIdx.x]) + red_d[3][threadIdx.x];
+    if (threadIdx.x == 3) {
+        counts[0] = n;
+        counts[1] = ((red_i[0] + red_i[1]) + red_i[2]) + red_i[3];
+    }
+}
+
+// AUC from the sorted column.  C[j] = number of negatives (label != 1) among rows [0, j), int32 [n + 1] in the workspace: per-tile
+// counts (auc_count), their exclusive scan by one block (auc_scan_tiles), the scan inside every tile (auc_prefix).  Then the thread
+// of every row that STARTS a run of equal scores [s, e) adds p * (C[s] + C[e]), p = the run's positives = (e - s) - (C[e] - C[s]):
+// the sum over the positives of C[s_i] + C[e_i].  e comes from the neighbour for a run of one row, else from a galloping search in
+// the sorted column (log of the run length, whether or not the run leaves the tile).
+constexpr int AUC_THREADS = 256, AUC_PER = 8, AUC_TILE = AUC_THREADS * AUC_PER;
+
+// exclusive scan of one int per thread over the block; *total = the block's sum
+__device__ __forceinline__ int block_excl_scan(int v, int* total, int* lds4) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) lds4[w] = inc;
+    __syncthreads();
+    int base = 0;
+    for (int q = 0; q < w; ++q) base += lds4[q];
+    *total = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+    __syncthreads();
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(AUC_THREADS) void auc_count_kernel(const float* __restrict__ label, long long n, int32_t* __restrict__ tile_neg) {
+    const long long lo = (long long)blockIdx.x * AUC_TILE;
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < AUC_PER; ++i) {
+        const long long j = lo + i * AUC_THREADS + threadIdx.x;
+        c += (j < n && label[j] != 1.0f) ? 1 : 0;
+    }
+    __shared__ int lds4[4];
+    int total;
+    block_excl_scan(c, &total, lds4);
+    if (threadIdx.x == 0) tile_neg[blockIdx.x] = total;
+}
+
+// in place: tile_neg[b] <- sum of tile_neg[0 .. b), tile_neg[tiles] <- the total
+__global__ __launch_bounds__(AUC_THREADS) void auc_scan_tiles_kernel(int32_t* __restrict__ tile_neg, long long tiles) {
+    __shared__ int lds4[4];
+    int carry = 0;
+    for (long long base = 0; base < tiles; base += AUC_THREADS) {
+        const long long b = base + threadIdx.x;
+        const int v = b < tiles ? tile_neg[b] : 0;
+        int total;
+        const int ex = block_excl_scan(v, &total, lds4);
+        if (b < tiles) tile_neg[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) tile_neg[tiles] = carry;
+}
+
+__global__ __launch_bounds__(AUC_THREADS) void auc_prefix_kernel(const float* __restrict__ label, long long n,
+                                                                 const int32_t* __restrict__ tile_off, int32_t* __restrict__ C) {
+    const long long lo = (long long)blockIdx.x * AUC_TILE + (long long)threadIdx.x * AUC_PER;       // this thread's 8 rows in a row
+    int neg[AUC_PER];
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < AUC_PER; ++i) {
+        neg[i] = (lo + i < n && label[lo + i] != 1.0f) ? 1 : 0;
+        c += neg[i];
+    }
+    __shared__ int lds4[4];
+    int total;
+    int run = tile_off[blockIdx.x] + block_excl_scan(c, &total, lds4);
+    if (blockIdx.x == 0 && threadIdx.x == 0) C[0] = 0;
+#pragma unroll
+    for (int i = 0; i < AUC_PER; ++i) {
+        run += neg[i];
+        if (lo + i < n) C[lo + i + 1] = run;
+    }
+}
+
+__global__ __launch_bounds__(AUC_THREADS) void auc_runs_kernel(const float* __restrict__ score, long long n, const int32_t* __restrict__ C,
+                                                               long long* __restrict__ part) {
+    const long long lo = (long long)blockIdx.x * AUC_TILE;
+    long long acc = 0;
+#pragma unroll 2
+    for (int i = 0; i < AUC_PER; ++i) {
+        const long long j = lo + i * AUC_THREADS + threadIdx.x;
+        if (j >= n) continue;
+        const float v = score[j];
+        if (j > 0 && score[j - 1] == v) continue;          // not the first row of its run
+        long long e = j + 1;
+        if (e < n && score[e] == v) {
+            // gallop: rows [j, j + a] score v; the first row that does not lies in (j + a, min(j + 2a, n)]
+            long long a = 1;
+            while (j + 2 * a < n && score[j + 2 * a] == v) a *= 2;
+            long long l = j + a + 1, h = j + 2 * a < n ? j + 2 * a : n;
+            while (l < h) {
+                const long long mid = (l + h) >> 1;
+                if (score[mid] == v) l = mid + 1;
+                else h = mid;
+            }
+            e = l;
+        }
+        const long long cs = C[j], ce = C[e];
+        acc += ((e - j) - (ce - cs)) * (cs + ce);
+    }
+    __shared__ long long red[4];
+    acc = wave_sum_ll(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// out = 2U (the tiles' parts in tile order per thread, then the fixed butterfly), P, Nn
+__global__ __launch_bounds__(AUC_THREADS) void auc_fold_kernel(const long long* __restrict__ part, long long tiles, long long n,
+                                                               const int32_t* __restrict__ C, long long* __restrict__ out) {
+    long long acc = 0;
+    for (long long b = threadIdx.x; b < tiles; b += AUC_THREADS) acc += part[b];
+    __shared__ long long red[4];
+    acc = wave_sum_ll(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long long nn = C[n];
+        out[0] = ((red[0] + red[1]) + red[2]) + red[3];
+        out[1] = n - nn;
+        out[2] = nn;
+    }
+}
+
+// ---- GAUC: `rec.meanrank` of an evaluation batch, a wave per user ---------------------------------------------------------------
+// Reference: collector.py `rec.meanrank` + metrics.py GAUC on the user's row of the dense [users, n_items] -inf matrix.  The
+// user's cells are the DISTINCT items of its segment [seg_start[u], seg_start[u + 1]) (items == NULL: row j of the segment is the
+// cell of item j, the dense `full` row); its positives are the items of the keys u * n_items + item in the SORTED pos_keys (what
+// fr_eval_hits takes; a key listed twice is one positive, a positive that is no cell of the user is none).
+//   out[u] = { 2 * pos_rank_sum, user_len, pos_len },  2 * rank of a positive p = 2 #{cells > p} + #{cells == p} + 1
+// Integers, any order.  Phase 1 marks the first copy of every item (first[row], one byte, in the workspace); phase 2 finds each
+// positive's score in the segment and walks the cells 64 at a time against it.
+__global__ __launch_bounds__(256) void eval_meanrank_segments_kernel(const int64_t* __restrict__ seg_start, long long n_users,
+                                                                     const int64_t* __restrict__ items, const float* __restrict__ scores,
+                                                                     const int64_t* __restrict__ pos_keys, long long n_pos,
+                                                                     long long n_items, uint8_t* __restrict__ first,
+                                                                     int64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = u < n_users;
+    const long long s = live ? seg_start[u] : 0, e = live ? seg_start[u + 1] : 0;
+    if (items) {
+        for (long long base = s; base < e; base += 64) {
+            const long long j = base + lane;
+            const long long it = j < e ? items[j] : -1;
+            bool dup = false;
+            const long long stop = base + 64 < e ? base + 64 : e;
+            for (long long k = s; k < stop; ++k) dup |= (k < j) & (items[k] == it);
+            if (j < e) first[j] = dup ? 0 : 1;
+        }
+        __syncthreads();       // (every thread of the block arrives: no early exit above) the flags are visible to the wave's lanes
+    }
+    if (!live) return;
+    long long user_len = 0, pairs = 0, pos_len = 0;          // pos_len: wave-uniform
+    for (long long j = s + lane; j < e; j += 64) user_len += ((!items || first[j]) && scores[j] > -INFINITY) ? 1 : 0;
+    const long long p0 = lower_bound_ll(pos_keys, n_pos, u * n_items), p1 = lower_bound_ll(pos_keys, n_pos, (u + 1) * n_items);
+    for (long long p = p0; p < p1; ++p) {
+        const long long key = pos_keys[p];
+        if (p > p0 && pos_keys[p - 1] == key) continue;
+        const long long item = key - u * n_items;
+        long long at = -1;                                    // the row of the positive's cell
+        if (!items) {
+            at = item < e - s ? s + item : -1;
+        } else {
+            for (long long base = s; base < e && at < 0; base += 64) {
+                const unsigned long long m = __ballot(base + lane < e && items[base + lane] == item);
+                if (m) at = base + __builtin_ctzll(m);
+            }
+        }
+        if (at < 0) continue;
+        const float sp = scores[at];
+        ++pos_len;
+        for (long long j = s + lane; j < e; j += 64) {
+            const float sc = scores[j];
+            if ((!items || first[j]) && sc > -INFINITY) pairs += (sc > sp ? 2 : 0) + (sc == sp ? 1 : 0);
+        }
+    }
+    user_len = wave_sum_ll(user_len);
+    pairs = wave_sum_ll(pairs);
+    if (lane == 0) {
+        out[u * 3 + 0] = pairs + pos_len;
+        out[u * 3 + 1] = user_len;
+        out[u * 3 + 2] = pos_len;
+    }
+}
+
 }  // namespace fr
 
 using namespace fr;
@@ -359,6 +636,83 @@ extern "C" int fr_fair_metrics_from_stats(const double* stats, int64_t n_segment
     FR_CHECK_LAUNCH();
     hipLaunchKernelGGL(column_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, blocks, 5,
                        1.0 / (double)n_segments, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+static long long value_blocks(int64_t n) {
+    const long long b = (n + VM_ROWS - 1) / VM_ROWS;
+    return b < VM_MAXBLOCKS ? b : VM_MAXBLOCKS;
+}
+
+extern "C" size_t fr_value_metrics_workspace_bytes(int64_t n) {
+    return n < 1 || n >= (1ll << 31) ? 0 : (size_t)value_blocks(n) * 4 * sizeof(double);
+}
+
+extern "C" int fr_value_metrics(const float* score, const float* label, int64_t n, double* out, int64_t* counts, void* ws,
+                                size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    FR_CHECK_ARG(score && label && out && counts && ws, "fr_value_metrics: null pointer");
+    FR_CHECK_ARG(n >= 1 && n < (1ll << 31), "fr_value_metrics: 1 <= n < 2^31 (got %lld)", (long long)n);
+    FR_CHECK_ARG(ws_bytes >= fr_value_metrics_workspace_bytes(n), "fr_value_metrics: workspace too small");
+    const long long blocks = value_blocks(n);
+    double* part_d = (double*)ws;
+    long long* part_i = (long long*)(part_d + blocks * 3);
+    hipLaunchKernelGGL(value_partials_kernel, dim3((unsigned)blocks), dim3(VM_THREADS), 0, stream, score, label, (long long)n,
+                       part_d, part_i);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(value_fold_kernel, dim3(1), dim3(VM_THREADS), 0, stream, (const double*)part_d, (const long long*)part_i,
+                       (int)blocks, (long long)n, out, (long long*)counts);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+// workspace of fr_auc_sorted: part int64 [tiles] | C int32 [n + 1] | tile_off int32 [tiles + 1]
+extern "C" size_t fr_auc_sorted_workspace_bytes(int64_t n) {
+    if (n < 1 || n >= (1ll << 31)) return 0;
+    const size_t tiles = (size_t)((n + AUC_TILE - 1) / AUC_TILE);
+    return tiles * sizeof(long long) + align_up((size_t)(n + 1) * sizeof(int32_t), 8) + (tiles + 1) * sizeof(int32_t);
+}
+
+extern "C" int fr_auc_sorted(const float* score_sorted, const float* label_sorted, int64_t n, int64_t* out, void* ws,
+                             size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    FR_CHECK_ARG(score_sorted && label_sorted && out && ws, "fr_auc_sorted: null pointer");
+    FR_CHECK_ARG(n >= 1 && n < (1ll << 31), "fr_auc_sorted: 1 <= n < 2^31 (got %lld)", (long long)n);
+    FR_CHECK_ARG(ws_bytes >= fr_auc_sorted_workspace_bytes(n), "fr_auc_sorted: workspace too small");
+    const long long tiles = (n + AUC_TILE - 1) / AUC_TILE;
+    long long* part = (long long*)ws;
+    int32_t* C = (int32_t*)(part + tiles);
+    int32_t* tile_off = (int32_t*)((char*)C + align_up((size_t)(n + 1) * sizeof(int32_t), 8));
+    hipLaunchKernelGGL(auc_count_kernel, dim3((unsigned)tiles), dim3(AUC_THREADS), 0, stream, label_sorted, (long long)n, tile_off);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(auc_scan_tiles_kernel, dim3(1), dim3(AUC_THREADS), 0, stream, tile_off, tiles);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(auc_prefix_kernel, dim3((unsigned)tiles), dim3(AUC_THREADS), 0, stream, label_sorted, (long long)n,
+                       (const int32_t*)tile_off, C);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(auc_runs_kernel, dim3((unsigned)tiles), dim3(AUC_THREADS), 0, stream, score_sorted, (long long)n,
+                       (const int32_t*)C, part);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(auc_fold_kernel, dim3(1), dim3(AUC_THREADS), 0, stream, (const long long*)part, tiles, (long long)n,
+                       (const int32_t*)C, (long long*)out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+extern "C" size_t fr_eval_meanrank_workspace_bytes(int64_t n_rows) { return n_rows < 1 ? 0 : (size_t)n_rows; }
+
+extern "C" int fr_eval_meanrank_segments(const int64_t* seg_start, int64_t n_users, const int64_t* items, const float* scores,
+                                         const int64_t* pos_keys, int64_t n_pos, int64_t n_items, int64_t n_rows, int64_t* out,
+                                         void* ws, size_t ws_bytes, void* stream_) {
+    FR_CHECK_ARG(seg_start && scores && out && (pos_keys || n_pos == 0), "fr_eval_meanrank_segments: null pointer");
+    FR_CHECK_ARG(n_users >= 1 && n_rows >= 1 && n_pos >= 0 && n_items >= 1,
+                 "fr_eval_meanrank_segments: n_users >= 1, n_rows >= 1, n_pos >= 0 and n_items >= 1");
+    FR_CHECK_ARG(!items || (ws && ws_bytes >= fr_eval_meanrank_workspace_bytes(n_rows)),
+                 "fr_eval_meanrank_segments: workspace too small (one byte per row when items are given)");
+    hipLaunchKernelGGL(eval_meanrank_segments_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, (hipStream_t)stream_,
+                       seg_start, (long long)n_users, items, scores, pos_keys, (long long)n_pos, (long long)n_items, (uint8_t*)ws,
+                       out);
     FR_CHECK_LAUNCH();
     return FR_OK;
 }

@@ -153,6 +153,13 @@ _PROTOS = {
     "fr_group_sums": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "fr_fair_metrics_workspace_bytes": (c_size_t, [c_int64]),
     "fr_fair_metrics_from_stats": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_value_metrics_workspace_bytes": (c_size_t, [c_int64]),
+    "fr_value_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_auc_sorted_workspace_bytes": (c_size_t, [c_int64]),
+    "fr_auc_sorted": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_eval_meanrank_workspace_bytes": (c_size_t, [c_int64]),
+    "fr_eval_meanrank_segments": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
     "fr_adam_dense_multi": (c_int, [POINTER(FrDenseDesc), c_int32, POINTER(FrAdam), c_void_p]),
     "fr_sample_negatives_calls": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),

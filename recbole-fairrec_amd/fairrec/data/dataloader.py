@@ -423,3 +423,42 @@ class NegSampleEvalDataLoader:
         positive_u = row_idx[is_pos]
         positive_i = item_col[is_pos]
         return inter, row_idx, positive_u, positive_i
+
+
+class LabeledEvalDataLoader:
+    """general_dataloader.py:68-158 with `eval_args.mode: labeled` (eval_neg_sample_args strategy 'none'): the evaluation set in
+    its stored order, `eval_batch_size` rows per batch, the user feature columns joined where the dataset lives (as
+    NegSampleEvalDataLoader does); no sampling and no generator draw.  Every row carries its own `LABEL_FIELD`: evaluation by
+    value compares `model.predict` with it (fairrec/evaluator: AUC, LogLoss, MAE, RMSE)."""
+
+    def __init__(self, config, dataset, sampler=None, shuffle=False):
+        self.config, self.dataset = config, dataset
+        self.uid_field, self.iid_field = dataset.uid_field, dataset.iid_field
+        self.label_field = config['LABEL_FIELD']
+        if self.label_field not in dataset.inter_feat:
+            raise ValueError(f"eval_args.mode labeled: the evaluation set has no [{self.label_field}] column (LABEL_FIELD); "
+                             "provide it, or set `threshold: {<field>: <value>}` to derive it from a rating column")
+        self.step = int(config['eval_batch_size'] or 4096)
+        self.pr = 0
+        uf = dataset.user_feat
+        dev = dataset.inter_feat[self.uid_field].device
+        self._user_cols = ({k: uf[k].to(dev) for k in uf.columns if k != self.uid_field} if uf is not None else {})
+
+    def __len__(self):
+        return math.ceil(len(self.dataset) / self.step)
+
+    def __iter__(self):
+        self.pr = 0
+        return self
+
+    def __next__(self):
+        if self.pr >= len(self.dataset):
+            self.pr = 0
+            raise StopIteration()
+        cur = self.dataset[self.pr:self.pr + self.step]
+        self.pr += self.step
+        ucol = cur[self.uid_field]
+        for k, col in self._user_cols.items():
+            if k not in cur:
+                cur[k] = col[ucol.to(torch.int64)]
+        return cur

@@ -5,6 +5,11 @@ trainer.py:435-437), the batch's positives and the batch Interaction, and keeps 
 need: `rec.topk` (hit flags of the top-max(topk) items | number of positives), `rec.positive_score`, `data.positive_i`
 and `data.<sst>`.  The reference builds a dense [users, items] 0/1 matrix per batch to mark the positives; here the hit
 flags come from binary searches in the sorted positive keys (fr_eval_hits).
+
+With 'gauc' among the metrics the three ranking branches also gather `rec.meanrank`, int64 [users, 3] =
+[2 * pos_rank_sum, user_len, pos_len] per user (fr_eval_meanrank_segments; exact integers, the first column doubled because a
+tied rank is a half); without it they collect and launch what they did before.  `eval_args.mode: labeled` keeps `rec.score`
+and `data.label` per batch (eval_batch_collect_labeled).
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ class Collector:
         self.topk = [topk] if isinstance(topk, int) else list(topk)
         self.sst = list(config['sst_attr_list'] or [])
         self.full = 'full' in (config['eval_args'] or {}).get('mode', 'full')
+        self.meanrank = 'gauc' in [m.lower() for m in (config['metrics'] or [])]
         self._parts: Dict[str, List[torch.Tensor]] = {}
         self._data: Dict[str, object] = {}
 
@@ -49,6 +55,27 @@ class Collector:
                  "fr_topk_like_torch_cpu")
         return out
 
+    def eval_batch_collect_labeled(self, scores: torch.Tensor, interaction):
+        """collector.py:176-181 (`rec.score`, `data.label`): the batch's predictions as they are and its LABEL_FIELD column."""
+        scores = scores.reshape(-1)
+        self._add('rec.score', scores.to(torch.float32))
+        self._add('data.label', interaction[self.config['LABEL_FIELD']].to(scores.device, torch.float32).reshape(-1))
+
+    def _meanrank(self, seg, items, scores, pos_keys, n_items):
+        """`rec.meanrank` of a batch: one launch, a wave per user (items None: dense rows); pos_keys = the sorted keys
+        row * n_items + item of the batch's positives, as fr_eval_hits takes them."""
+        lib = _C.lib()
+        U, n_rows = seg.numel() - 1, scores.numel()
+        pos_keys = pos_keys.contiguous()
+        out = torch.empty((U, 3), dtype=torch.int64, device=scores.device)
+        ws = None if items is None else torch.empty(lib.fr_eval_meanrank_workspace_bytes(n_rows), dtype=torch.uint8,
+                                                    device=scores.device)
+        _C.check(lib.fr_eval_meanrank_segments(seg.data_ptr(), U, _C.ptr(items), scores.data_ptr(), pos_keys.data_ptr(),
+                                               pos_keys.numel(), n_items, n_rows, out.data_ptr(), _C.ptr(ws),
+                                               0 if ws is None else ws.numel(), _C.current_stream()),
+                 "fr_eval_meanrank_segments")
+        self._add('rec.meanrank', out)
+
     def eval_batch_collect(self, scores: torch.Tensor, interaction, positive_u: torch.Tensor, positive_i: torch.Tensor):
         lib = _C.lib()
         U, n_items = scores.shape
@@ -64,6 +91,10 @@ class Collector:
         rec = torch.empty((U, K + 1), dtype=torch.int32, device=scores.device)
         _C.check(lib.fr_eval_hits(topk_idx.data_ptr(), U, K, n_items, keys.data_ptr(), keys.numel(), rec.data_ptr(),
                                   _C.current_stream()), "fr_eval_hits")
+        if self.meanrank:
+            # the dense masked rows as they are: row u * n_items + i is the cell of item i
+            seg = torch.arange(U + 1, device=scores.device, dtype=torch.int64) * n_items
+            self._meanrank(seg, None, scores.to(torch.float32).contiguous().view(-1), keys, n_items)
         self._add('rec.topk', rec)
         self._add('rec.items', topk_idx)
         self._add('rec.positive_score', scores[positive_u, positive_i])
@@ -119,6 +150,8 @@ class Collector:
                 _C.check(lib.fr_eval_lookup_segments(seg.data_ptr(), U, items.data_ptr(), sc.data_ptr(), rows.data_ptr(),
                                                      its.data_ptr(), rows.numel(), out.data_ptr(), st), "fr_eval_lookup_segments")
                 return out.to(origin_scores.dtype)
+            if self.meanrank:
+                self._meanrank(seg, items, sc, torch.sort(positive_u * n_items + positive_i).values, n_items)
             return self._finish_candidates(topk_idx, lookup, interaction, items, positive_u, positive_i, n_items, U, K, dev)
         keys, order = torch.sort(row_idx * n_items + items, stable=True)
         first = torch.ones_like(keys, dtype=torch.bool)
@@ -156,7 +189,33 @@ class Collector:
             dense = torch.full((tied.numel(), n_items), -float('inf'), dtype=torch.float32, device=dev)
             dense[slot[crow[sel]], (ckeys % n_items)[sel]] = cscore[sel].to(torch.float32)
             topk_idx[tied] = self._host_topk(dense, K).to(dev)
+        if self.meanrank:
+            self._add('rec.meanrank', self._meanrank_general(ckeys, cscore, positive_u * n_items + positive_i, n_items, U))
         return self._finish_candidates(topk_idx, lookup, interaction, items, positive_u, positive_i, n_items, U, K, dev)
+
+    @staticmethod
+    def _meanrank_general(ckeys, cscore, pos_keys, n_items, U):
+        """`rec.meanrank` of the general form above from its distinct cells (ckeys sorted, cscore): index arithmetic over the
+        cells ordered by (row, score); a run of equal scores in a row shares the mean rank."""
+        dev = ckeys.device
+        live = cscore > -float('inf')
+        ck, cs = ckeys[live], cscore[live].to(torch.float32)
+        o1 = torch.sort(cs, stable=True).indices
+        order = o1[torch.sort((ck // n_items)[o1], stable=True).indices]                  # cells by (row asc, score asc)
+        r, sc, n = (ck // n_items)[order], cs[order], ck.numel()
+        head = torch.ones(n, dtype=torch.bool, device=dev)
+        head[1:] = (r[1:] != r[:-1]) | (sc[1:] != sc[:-1])
+        run_id = torch.cumsum(head, 0) - 1
+        run_start = head.nonzero().view(-1)
+        run_end = torch.cat([run_start[1:], torch.tensor([n], device=dev)])
+        row_end = torch.searchsorted(r, torch.arange(U, device=dev), right=True)
+        pos = torch.isin(ck[order], pos_keys)
+        greater, equal = row_end[r] - run_end[run_id], run_end[run_id] - run_start[run_id]
+        out = torch.zeros((U, 3), dtype=torch.int64, device=dev)
+        out[:, 0].index_add_(0, r[pos], (2 * greater + equal + 1)[pos])
+        out[:, 1] = torch.bincount(r, minlength=U)
+        out[:, 2] = torch.bincount(r[pos], minlength=U)
+        return out
 
     def _finish_candidates(self, topk_idx, lookup, interaction, items, positive_u, positive_i, n_items, U, K, dev):
         lib = _C.lib()

@@ -9,9 +9,14 @@ Inputs are the arrays the reference's Collector gathers (collector.py:131-205), 
   sst[<name>]                             the user's attribute value per positive pair
 The torch ops here are index plumbing (sort / unique of the id columns); every reduction is a HIP kernel
 (csrc/metrics.hip: fr_topk_metrics, fr_group_sums, fr_fair_metrics_from_stats).
+
+`eval_args.mode: labeled` is evaluation by value: 'auc', 'logloss', 'mae', 'rmse' of `rec.score` (what `predict` returned)
+against `data.label` (LABEL_FIELD), every row of the evaluation set (fr_value_metrics, fr_auc_sorted).  'gauc' is a ranking
+metric: it reads `rec.meanrank` (fr_eval_meanrank_segments) in the full / uniN / popN modes.
 """
 from __future__ import annotations
 
+from logging import getLogger
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -178,6 +183,67 @@ def tail_percentage(rec_items, count_items, topk, tail_ratio=None) -> Dict[str, 
     return _mean_at_k(tail[rec_items], 'tailpercentage', topk)
 
 
+def value_metrics(score: torch.Tensor, label: torch.Tensor, names: Iterable[str]) -> Dict[str, float]:
+    """metrics.py AUC / LogLoss / MAE / RMSE over the concatenated (score, label) columns.  The sums and the AUC's integer
+    counts come from the device (one pass each; the AUC after ONE torch.sort of the score column), the last division and
+    square root are float64 on the host.  AUC without a positive or without a negative row: nan and a warning."""
+    lib = _C.lib()
+    names = [n.lower() for n in names]
+    score = score.reshape(-1).to(torch.float32).contiguous()
+    label = label.reshape(-1).to(torch.float32).contiguous()
+    n, dev, st = score.numel(), score.device, _C.current_stream()
+    if label.numel() != n or n < 1:
+        raise ValueError(f'value metrics need as many labels as scores and at least one row (got {n} scores, {label.numel()} labels)')
+    if n >= 2 ** 31:
+        raise ValueError(f'value metrics: {n} rows; the device path takes fewer than 2^31')
+    res = {}
+    if {'logloss', 'mae', 'rmse'} & set(names):
+        out = torch.empty(3, dtype=torch.float64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        ws = torch.empty(lib.fr_value_metrics_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        _C.check(lib.fr_value_metrics(score.data_ptr(), label.data_ptr(), n, out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), st), "fr_value_metrics")
+        sums = out.cpu().tolist()
+        res['mae'] = sums[0] / n
+        res['rmse'] = (sums[1] / n) ** 0.5
+        res['logloss'] = sums[2] / n
+    if 'auc' in names:
+        srt, order = torch.sort(score)
+        out = torch.empty(3, dtype=torch.int64, device=dev)
+        ws = torch.empty(lib.fr_auc_sorted_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        _C.check(lib.fr_auc_sorted(srt.data_ptr(), label[order].contiguous().data_ptr(), n, out.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), st), "fr_auc_sorted")
+        two_u, P, Nn = out.cpu().tolist()
+        if P == 0 or Nn == 0:
+            getLogger().warning('AUC: the evaluation set has no %s row (label %s 1); the result is nan',
+                                'positive' if P == 0 else 'negative', '==' if P == 0 else '!=')
+            res['auc'] = float('nan')
+        else:
+            res['auc'] = two_u / (2 * P * Nn)          # Python integers: the one division is exact-to-rounding float64
+    return {m: res[m] for m in names}
+
+
+def gauc(meanrank: torch.Tensor) -> float:
+    """metrics.py GAUC from `rec.meanrank` int64 [users, 3] = [2 * pos_rank_sum, user_len, pos_len]: users without a positive
+    or without a negative are dropped (a warning each kind), the rest averaged weighted by pos_len, in float64."""
+    t = meanrank.cpu()
+    two_rank, user_len, pos_len = t[:, 0].to(torch.float64), t[:, 1].to(torch.float64), t[:, 2].to(torch.float64)
+    no_pos, no_neg = pos_len == 0, (user_len == pos_len) & (pos_len != 0)
+    if bool(no_pos.any()):
+        getLogger().warning('No positive samples in some users, true positive value should be meaningless, '
+                            'these users have been removed from GAUC calculation')
+    if bool(no_neg.any()):
+        getLogger().warning('No negative samples in some users, false positive value should be meaningless, '
+                            'these users have been removed from GAUC calculation')
+    keep = ~(no_pos | no_neg)
+    two_rank, user_len, pos_len = two_rank[keep], user_len[keep], pos_len[keep]
+    if not pos_len.numel():
+        return float('nan')
+    pair = (user_len + 1) * pos_len - pos_len * (pos_len + 1) / 2 - two_rank / 2
+    auc_u = pair / ((user_len - pos_len) * pos_len)
+    return float((auc_u * pos_len).sum() / pos_len.sum())
+
+
 class Evaluator:
     """recbole/evaluator/evaluator.py: metric names from `config['metrics']` -> one result dict."""
 
@@ -185,6 +251,8 @@ class Evaluator:
     EXPOSURE = {"giniindex", "popularitypercentage", "itemcoverage", "averagepopularity", "shannonentropy", "tailpercentage"}
     FAIR = {"nonparityunfairness", "valueunfairness", "absoluteunfairness", "underunfairness", "overunfairness",
             "differentialfairness"}
+    RANKING = {"gauc"}                                   # reads `rec.meanrank`; a ranking-type metric in the reference too
+    VALUE = {"auc", "logloss", "mae", "rmse"}            # evaluation by value: `eval_args.mode: labeled` only
 
     def __init__(self, config):
         self.config = config
@@ -194,12 +262,25 @@ class Evaluator:
             self.topk = [self.topk]
         self.decimal_place = config['metric_decimal_place'] if config['metric_decimal_place'] is not None else 4
         self.mode = (config['eval_args'] or {}).get('mode', 'full')
-        unknown = [m for m in self.metrics if m not in self.TOPK | self.FAIR | self.EXPOSURE]
+        unknown = [m for m in self.metrics if m not in self.TOPK | self.FAIR | self.EXPOSURE | self.RANKING | self.VALUE]
         if unknown:
             raise NotImplementedError(f'metrics {unknown} are not on the device path')
+        value = [m for m in self.metrics if m in self.VALUE]
+        ranking = [m for m in self.metrics if m not in self.VALUE]
+        if value and ranking:
+            raise RuntimeError('Ranking metrics and value metrics can not be used at the same time.')
+        if value and self.mode != 'labeled':
+            raise ValueError(f"value metrics {value} need eval_args.mode 'labeled', not '{self.mode}'")
+        if ranking and self.mode == 'labeled':
+            raise ValueError(f"ranking metrics {ranking} need eval_args.mode full / uniN / popN, not 'labeled'")
 
     def evaluate(self, collected: Dict[str, torch.Tensor]) -> Dict[str, float]:
         res = {}
+        if self.VALUE & set(self.metrics):
+            res.update(value_metrics(collected['rec.score'], collected['data.label'],
+                                     [m for m in self.metrics if m in self.VALUE]))
+        if "gauc" in self.metrics:
+            res['gauc'] = gauc(collected['rec.meanrank'])
         if self.TOPK & set(self.metrics):
             allk = topk_metrics(collected['rec.topk'], self.topk)
             res.update({k: v for k, v in allk.items() if k.split('@')[0] in self.metrics})

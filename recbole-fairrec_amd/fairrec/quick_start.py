@@ -35,6 +35,22 @@ def worst_item_complete_batch(config, train_set) -> int:
     return int(torch.bincount(items.reshape(-1).to(torch.int64)).max().item()) + int(config['train_batch_size']) - 1
 
 
+def set_label_by_threshold(config, dataset):
+    """The reference's `_set_label_by_threshold` (dataset.py) for one evaluation split: `threshold: {field: t}` derives
+    LABEL_FIELD = (field >= t) when the split has no such column.  The source column is kept (the reference drops it): FOCF
+    and FairGo train on it.  Training splits are left alone -- TrainDataLoader writes its own 1/0 LABEL_FIELD next to the
+    negatives it samples."""
+    threshold, label = config['threshold'], config['LABEL_FIELD']
+    if not threshold or label in dataset.inter_feat:
+        return
+    if not isinstance(threshold, dict) or len(threshold) != 1:
+        raise ValueError('threshold: exactly one {field: value} pair')
+    field, value = next(iter(threshold.items()))
+    if field not in dataset.inter_feat:
+        raise ValueError(f'threshold: field [{field}] is not in the interaction columns')
+    dataset.inter_feat[label] = (dataset.inter_feat[field] >= value).to(torch.float32)
+
+
 def run_recbole(model=None, dataset=None, config_file_list=None, config_dict=None, saved=True, splits=None,
                 before_fit=None):
     """`dataset` is an InteractionDataset, or None for a synthetic one sized by config keys
@@ -92,6 +108,14 @@ def run_recbole(model=None, dataset=None, config_file_list=None, config_dict=Non
         loader = FullSortEvalDataLoader if eval_mode == 'full' else NegSampleEvalDataLoader
         valid_data = loader(config, valid_set, phases.set_phase('valid'))
         test_data = loader(config, test_set, phases.set_phase('test'))
+    elif eval_mode == 'labeled' and config['device'].type == 'cuda':
+        # evaluation by value on the device (AUC / LogLoss / MAE / RMSE of `predict` against LABEL_FIELD): the two sets in
+        # their stored order, resident where the model is
+        from .data.dataloader import LabeledEvalDataLoader
+        for part in (valid_set, test_set):
+            set_label_by_threshold(config, part)
+        valid_data = LabeledEvalDataLoader(config, valid_set.to(config['device']))
+        test_data = LabeledEvalDataLoader(config, test_set.to(config['device']))
     else:
         valid_data = TrainDataLoader(config, valid_set)
         test_data = TrainDataLoader(config, test_set)

@@ -431,6 +431,20 @@ class Trainer(AbstractTrainer):
                 collector.eval_batch_collect(scores, user_df, positive_u, positive_i)
         return OrderedDict(evaluator.evaluate(collector.get_data_struct()))
 
+    def _labeled_evaluate(self, eval_data, sst_lists=(None,)):
+        """Evaluation by value (`eval_args.mode: labeled`, trainer.py:458-515 with a labeled loader): `predict` on every
+        batch of `eval_batch_size` rows, once per entry of `sst_lists`; the Collector keeps the scores and the batch's
+        LABEL_FIELD on the device, the Evaluator reduces them there (AUC / LogLoss / MAE / RMSE).  The Evaluator is built
+        first: a metric list that does not fit the mode raises before any device work."""
+        from ..evaluator import Collector, Evaluator
+        evaluator, collector = Evaluator(self.config), Collector(self.config)
+        for interaction in eval_data:
+            interaction = interaction.to(self.device)
+            for sst_list in sst_lists:
+                extra = () if sst_list is None else (sst_list,)
+                collector.eval_batch_collect_labeled(self.model.predict(interaction, *extra), interaction)
+        return OrderedDict(evaluator.evaluate(collector.get_data_struct()))
+
     def _load_for_eval(self, load_best_model, model_file):
         if load_best_model:
             checkpoint = torch.load(model_file or self.saved_model_file, weights_only=False)
@@ -441,14 +455,18 @@ class Trainer(AbstractTrainer):
     @torch.no_grad()
     def evaluate(self, eval_data, load_best_model=False, model_file=None, show_progress=False):
         """A FullSortEvalDataLoader / NegSampleEvalDataLoader gets the reference's ranking evaluation (top-k and
-        fairness metrics named in `config['metrics']`, fairrec/evaluator); a plain loader of (user, item, rating)
-        batches the value-type RMSE / MAE of `model.predict`."""
+        fairness metrics named in `config['metrics']`, fairrec/evaluator); a LabeledEvalDataLoader the reference's
+        evaluation by value (AUC / LogLoss / MAE / RMSE of `predict` against LABEL_FIELD); a plain loader of
+        (user, item, rating) batches the RMSE / MAE of `model.predict * max_rating` against RATING_FIELD."""
         if not eval_data:
             return None
-        from ..data.dataloader import FullSortEvalDataLoader, NegSampleEvalDataLoader
+        from ..data.dataloader import FullSortEvalDataLoader, LabeledEvalDataLoader, NegSampleEvalDataLoader
         if isinstance(eval_data, (FullSortEvalDataLoader, NegSampleEvalDataLoader)):
             self._load_for_eval(load_best_model, model_file)
             return self._ranking_evaluate(eval_data)
+        if isinstance(eval_data, LabeledEvalDataLoader):
+            self._load_for_eval(load_best_model, model_file)
+            return self._labeled_evaluate(eval_data)
         if load_best_model:
             checkpoint = torch.load(model_file or self.saved_model_file, weights_only=False)
             self.model.load_state_dict(checkpoint['state_dict'])
@@ -589,13 +607,17 @@ class PFCNTrainer(Trainer):
     @torch.no_grad()
     def pfcn_evaluate(self, eval_data, load_best_model=False, model_file=None, show_progress=False):
         """trainer.py:968-1027 (validation during training): ONE result over the batches of every attribute subset."""
-        from ..data.dataloader import FullSortEvalDataLoader, NegSampleEvalDataLoader
+        from ..data.dataloader import FullSortEvalDataLoader, LabeledEvalDataLoader, NegSampleEvalDataLoader
         if not eval_data:
             return None
+        sst_lists = self._subsets() if self.filter_mode != 'none' else (None,)
+        if isinstance(eval_data, LabeledEvalDataLoader):
+            self._load_for_eval(load_best_model, model_file)
+            return self._labeled_evaluate(eval_data, sst_lists)
         if not isinstance(eval_data, (FullSortEvalDataLoader, NegSampleEvalDataLoader)):
             raise NotImplementedError("evaluation of the filtered models needs a ranking evaluation loader")
         self._load_for_eval(load_best_model, model_file)
-        return self._ranking_evaluate(eval_data, self._subsets() if self.filter_mode != 'none' else (None,))
+        return self._ranking_evaluate(eval_data, sst_lists)
 
     def _valid_epoch(self, valid_data, show_progress=False):
         valid_result = self.pfcn_evaluate(valid_data, load_best_model=False, show_progress=show_progress)
@@ -605,19 +627,19 @@ class PFCNTrainer(Trainer):
     def evaluate(self, eval_data, load_best_model=False, model_file=None, show_progress=False):
         """trainer.py:1047-1106: one result per non-empty subset of the sensitive attributes, keyed
         '<filter_mode>-<subset>' (filters on), or {'<filter_mode>': result}."""
-        from ..data.dataloader import FullSortEvalDataLoader, NegSampleEvalDataLoader
-        if eval_data and isinstance(eval_data, (FullSortEvalDataLoader, NegSampleEvalDataLoader)):
+        from ..data.dataloader import FullSortEvalDataLoader, LabeledEvalDataLoader, NegSampleEvalDataLoader
+        if eval_data and isinstance(eval_data, (FullSortEvalDataLoader, NegSampleEvalDataLoader, LabeledEvalDataLoader)):
+            run = self._labeled_evaluate if isinstance(eval_data, LabeledEvalDataLoader) else self._ranking_evaluate
             self._load_for_eval(load_best_model, model_file)
             final = {}
             if self.filter_mode != 'none':
                 for sub in self._subsets():
-                    final['{}-{}'.format(self.config['filter_mode'] or self.filter_mode, sub)] = \
-                        self._ranking_evaluate(eval_data, (sub,))
+                    final['{}-{}'.format(self.config['filter_mode'] or self.filter_mode, sub)] = run(eval_data, (sub,))
             else:
-                final[self.config['filter_mode']] = self._ranking_evaluate(eval_data)
+                final[self.config['filter_mode']] = run(eval_data)
             return final
-        raise NotImplementedError("evaluation of the filtered models needs a ranking evaluation loader "
-                                  "(FullSortEvalDataLoader / NegSampleEvalDataLoader)")
+        raise NotImplementedError("evaluation of the filtered models needs an evaluation loader "
+                                  "(FullSortEvalDataLoader / NegSampleEvalDataLoader / LabeledEvalDataLoader)")
 
 
 class PFCN_PMFTrainer(PFCNTrainer):
@@ -753,6 +775,10 @@ class FairGoTrainer(PFCNTrainer):
         pretrain checkpoint ('pretrain-<metric>') and the finetuned one ('finetune-<metric>')."""
         if not eval_data:
             return None
+        from ..data.dataloader import LabeledEvalDataLoader
+        if isinstance(eval_data, LabeledEvalDataLoader):
+            raise NotImplementedError("FairGo is evaluated by ranking (eval_args.mode full / uniN / popN); evaluation by value "
+                                      "(eval_args.mode labeled, LabeledEvalDataLoader) is not served for it")
         if not load_best_model:
             return Trainer.evaluate(self, eval_data, False, None, show_progress)
         result = OrderedDict()
