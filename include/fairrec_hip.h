@@ -1069,6 +1069,60 @@ FR_API int fr_dyn_neg_dot_scores(const fr_table* item_t, const fr_adam* item_ada
                                  const float* global_bias, const int64_t* cand, int64_t n, int32_t num, int32_t M,
                                  float* scores, uint32_t* err_flag, void* stream);
 
+/*
+ * Recommendation: the k best cells of every row, ranked by ONE total order -- higher score first, NaN above +inf, and among
+ * equal scores (-0 == +0, all NaNs equal) the lower column / item id first -- so a result does not depend on how the work
+ * is split.  Masked cells have score -inf and take part like any other cell: a row with fewer than k unmasked cells is
+ * completed by -inf entries in ascending id.  k must be in 1..min(FR_TOPK_MAX, n_cols); anything else, a null pointer or a
+ * short workspace is FR_EINVAL before anything is launched or written.
+ *
+ * `slices`: into how many ranges the columns / items are cut (one workgroup each, merged by a second kernel); 0 = chosen
+ * from the shape so that the chip is filled (or FAIRREC_REC_SLICES when that is set).  At most 64, and slices * k <= 8192.
+ * The workspace holds the slices' lists: rows * slices * k * 8 bytes; it does not grow with rows * n_cols.
+ *
+ * fr_topk_rows: from a dense fp32 [n_rows, n_cols] matrix with leading dimension ld >= n_cols; val_out [n_rows, k] are the
+ *   selected cells' own bits, idx_out [n_rows, k] their columns.
+ */
+#define FR_TOPK_MAX 256
+FR_API size_t fr_topk_rows_workspace_bytes(int64_t n_rows, int64_t n_cols, int32_t k, int32_t slices);
+FR_API int fr_topk_rows(const float* scores, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t k, int32_t slices,
+                        float* val_out, int64_t* idx_out, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * fr_recommend_topk: the same selection over scores computed in the kernel and never stored,
+ *     score(u, i) = epilogue(((dot(X[u,:], W[i,:]) + user_bias[u]) + item_bias[i]) + bias0)
+ * dot = one ascending-column fp32 fmaf chain from 0 (v_mfma_f32_32x32x2_f32); a bias term is skipped when its pointer is
+ * NULL.  epilogue 0: none; 1: clamp(x, 0, scale) / scale (IEEE division; a NaN stays a NaN); 2: 1 / (1 + expf(-x)), the form
+ * of fr_dyn_neg_dot_select.  A zero score is +0.  mask_pad: item 0 scores -inf.  hist_indptr [n_users + 1] / hist_items
+ * [hist_len] (either both or hist_indptr NULL): items of user u, hist_items[hist_indptr[u] .. hist_indptr[u+1]), score -inf;
+ * they must ascend within a user, which the caller states with hist_sorted = 1 (anything else is FR_EINVAL).
+ * W is read as it lies in memory, row stride dim; 1 <= dim <= 256, no alignment asked of it.
+ * scores_out (optional): also receives the dense masked [n_users, n_items] matrix of exactly the scores that were ranked.
+ * val_out of a NaN score is the canonical quiet NaN.
+ */
+typedef struct fr_rec_args {
+    const float* X;             /* [n_users, dim] the users' final embeddings */
+    const float* W;             /* [n_items, dim] the item table */
+    const float* user_bias;     /* [n_users] or NULL */
+    const float* item_bias;     /* [n_items] or NULL */
+    const int64_t* hist_indptr; /* [n_users + 1] or NULL */
+    const int64_t* hist_items;  /* [hist_len] */
+    float* scores_out;          /* [n_users, n_items] or NULL */
+    int64_t n_users;
+    int64_t n_items;
+    int64_t hist_len;
+    int32_t dim;
+    int32_t k;
+    int32_t epilogue;
+    int32_t mask_pad;
+    int32_t hist_sorted;
+    int32_t slices;
+    float bias0;
+    float scale;                /* epilogue 1 */
+} fr_rec_args;
+FR_API size_t fr_recommend_topk_workspace_bytes(const fr_rec_args* a);
+FR_API int fr_recommend_topk(const fr_rec_args* a, float* val_out, int64_t* idx_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

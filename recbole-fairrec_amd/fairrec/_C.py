@@ -21,6 +21,7 @@ DEV_ERR_PIPE_WAIT = 8
 DEV_ERR_SAMPLE_ROUNDS = 16
 EUNSUPPORTED = -3      # FR_EUNSUPPORTED
 WGRAD_MAX = 8          # FR_WGRAD_MAX
+FR_TOPK_MAX = 256
 
 FOCF_OBJECTIVES = {"none": 0, "value": 1, "absolute": 2, "under": 3, "over": 4, "nonparity": 5}
 
@@ -58,6 +59,13 @@ class FrAliasTable(Structure):  # include/fairrec_hip.h: fr_alias_table
 class FrFocfBatch(Structure):
     _fields_ = [("user", c_void_p), ("item", c_void_p), ("sst", c_void_p), ("B", c_int64), ("ws", c_void_p),
                 ("ws_bytes", c_size_t), ("rating", c_void_p)]
+
+
+class FrRecArgs(Structure):     # include/fairrec_hip.h: fr_rec_args
+    _fields_ = [("X", c_void_p), ("W", c_void_p), ("user_bias", c_void_p), ("item_bias", c_void_p), ("hist_indptr", c_void_p),
+                ("hist_items", c_void_p), ("scores_out", c_void_p), ("n_users", c_int64), ("n_items", c_int64),
+                ("hist_len", c_int64), ("dim", c_int32), ("k", c_int32), ("epilogue", c_int32), ("mask_pad", c_int32),
+                ("hist_sorted", c_int32), ("slices", c_int32), ("bias0", c_float), ("scale", c_float)]
 
 
 class FairrecError(RuntimeError):
@@ -269,6 +277,11 @@ _PROTOS = {
                                        c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_dyn_neg_dot_scores": (c_int, [POINTER(FrTable), POINTER(FrAdam), POINTER(FrTable), POINTER(FrAdam), c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "fr_topk_rows_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "fr_topk_rows": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                             c_void_p]),
+    "fr_recommend_topk_workspace_bytes": (c_size_t, [POINTER(FrRecArgs)]),
+    "fr_recommend_topk": (c_int, [POINTER(FrRecArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_rowdot_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_bpr_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "fr_bpr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -527,3 +527,68 @@ def dyn_neg_dot_select(item_table, item_hyper, user_rows, cand, num, M, err_flag
                 ctypes.byref(bh) if bh is not None else None, user_rows.data_ptr(), _C.ptr(ub), _C.ptr(gb), cand.data_ptr(),
                 n, int(num), int(M), out.data_ptr(), _C.ptr(err_flag), _C.current_stream()), name)
     return out
+
+
+# ---- recommendation: top-k without the dense score matrix (csrc/recommend.hip) ------------------------------------------
+def _check_k(k, n_cols):
+    k = int(k)
+    if k > _C.FR_TOPK_MAX:
+        raise ValueError(f'k = {k} is above FR_TOPK_MAX = {_C.FR_TOPK_MAX}, the most the top-k kernels select')
+    if k < 1 or k > n_cols:
+        raise ValueError(f'k = {k} not in 1..{n_cols}')
+    return k
+
+
+def topk_rows(scores, k, slices=0):
+    """fr_topk_rows: (values, indices) of the k best cells of every row of a dense fp32 matrix (rows may be strided), in the
+    library's total order: higher score first, NaN above +inf, the lower column first among equal scores."""
+    if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_cuda or scores.stride(1) != 1:
+        raise _C.FairrecError('topk_rows: a [rows, cols] fp32 matrix with unit column stride on a ROCm device')
+    R, N = scores.shape
+    k = _check_k(k, N)
+    ld = scores.stride(0) if R > 1 else max(scores.stride(0), N)
+    lib = _C.lib()
+    ws = torch.empty(lib.fr_topk_rows_workspace_bytes(R, N, k, int(slices)) // 8, dtype=torch.int64, device=scores.device)
+    val = torch.empty((R, k), dtype=torch.float32, device=scores.device)
+    idx = torch.empty((R, k), dtype=torch.int64, device=scores.device)
+    _C.check(lib.fr_topk_rows(scores.data_ptr(), R, N, ld, k, int(slices), val.data_ptr(), idx.data_ptr(), _C.ptr(ws),
+                              ws.numel() * 8, _C.current_stream()), "fr_topk_rows")
+    return val, idx
+
+
+def recommend_topk(X, W, k, user_bias=None, item_bias=None, bias0=0.0, epilogue=0, scale=1.0, mask_pad=False,
+                   hist_indptr=None, hist_items=None, want_scores=False, slices=0):
+    """fr_recommend_topk: (values, indices[, scores]) of the k best items of every row of X against the item table W, score
+    = epilogue(((X[u] . W[i] + user_bias[u]) + item_bias[i]) + bias0), the pad item and the history CSR (ascending within a
+    user) scored -inf.  Nothing of size [users, items] is stored unless `want_scores` asks for the dense masked matrix."""
+    if not X.is_cuda:
+        raise _C.FairrecError('recommend_topk: ROCm device tensors only')
+    X = X.detach().to(torch.float32).contiguous()
+    W = W.detach().to(torch.float32).contiguous()
+    U, D = X.shape
+    N = W.shape[0]
+    if W.dim() != 2 or W.shape[1] != D:
+        raise ValueError('recommend_topk: X [U, D] against W [n_items, D]')
+    k = _check_k(k, N)
+    dev = X.device
+    ub = user_bias.detach().to(torch.float32).contiguous().view(-1) if user_bias is not None else None
+    ib = item_bias.detach().to(torch.float32).contiguous().view(-1) if item_bias is not None else None
+    if (ub is not None and ub.numel() != U) or (ib is not None and ib.numel() != N):
+        raise ValueError('recommend_topk: user_bias [U], item_bias [n_items]')
+    ip = hi = None
+    if hist_indptr is not None:
+        ip = hist_indptr.to(dev, torch.int64).contiguous()
+        hi = hist_items.to(dev, torch.int64).contiguous()
+        if ip.numel() != U + 1:
+            raise ValueError('recommend_topk: hist_indptr [U + 1]')
+    scores = torch.empty((U, N), dtype=torch.float32, device=dev) if want_scores else None
+    a = _C.FrRecArgs(X.data_ptr(), W.data_ptr(), _C.ptr(ub), _C.ptr(ib), _C.ptr(ip), _C.ptr(hi), _C.ptr(scores), U, N,
+                     hi.numel() if hi is not None else 0, D, k, int(epilogue), int(bool(mask_pad)), 1, int(slices),
+                     float(bias0), float(scale))
+    lib = _C.lib()
+    ws = torch.empty(lib.fr_recommend_topk_workspace_bytes(ctypes.byref(a)) // 8, dtype=torch.int64, device=dev)
+    val = torch.empty((U, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((U, k), dtype=torch.int64, device=dev)
+    _C.check(lib.fr_recommend_topk(ctypes.byref(a), val.data_ptr(), idx.data_ptr(), _C.ptr(ws), ws.numel() * 8,
+                                   _C.current_stream()), "fr_recommend_topk")
+    return (val, idx, scores) if want_scores else (val, idx)

@@ -28,6 +28,16 @@ class AbstractRecommender(nn.Module):
     def full_sort_predict(self, interaction):
         raise NotImplementedError
 
+    def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
+        """Optional hook of utils/case_study.py: a model whose score of (user, item) is
+        epilogue(((X[u] . W[i] + user_bias[u]) + item_bias[i]) + bias0) returns those pieces -- a dict with X [users, D] (the
+        users' final embeddings, already gathered / filtered), W [n_items, D] (the item table as it lies in memory) and,
+        where it has them, user_bias [users], item_bias [n_items], bias0, epilogue (fr_recommend_topk: 0 none, 1 clamp to
+        [0, scale] / scale, 2 sigmoid) and scale -- and is ranked without its dense score matrix.  None (the default): the
+        model is scored through full_sort_predict / predict.  `users_per_batch`: how many users the full-sort evaluation
+        scores per `predict` call, for models whose user side depends on its batch."""
+        return None
+
     def other_parameter(self):
         names = getattr(self, 'other_parameter_name', None)
         return {k: getattr(self, k) for k in names} if names else dict()

@@ -470,6 +470,16 @@ class FairGo_PMF(FairRecommender):
             pred = torch.matmul(ua[user], ia.transpose(0, 1))
             return torch.clamp(pred.view(-1), min=0., max=float(self.max_rating)) / float(self.max_rating)
 
+    def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
+        """The pieces of full_sort_predict for fr_recommend_topk: the users' rows of the propagated table, its item rows (a
+        view: they lie behind the user rows), and the clamp to [0, max_rating] / max_rating as the kernel's epilogue."""
+        if type(self).full_sort_predict is not FairGo_PMF.full_sort_predict:
+            return None
+        user = interaction[self.USER_ID].to(self.hip_engine().device)
+        with torch.no_grad():
+            ua, ia = self.forward()
+            return {'X': ua[user], 'W': ia, 'epilogue': 1, 'scale': float(self.max_rating)}
+
     def get_sst_embed(self, user_data, sst_list=None):
         ret = {}
         idx = torch.arange(1, self.n_users)

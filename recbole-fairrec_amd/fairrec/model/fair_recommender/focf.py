@@ -900,6 +900,16 @@ class FOCF(FairRecommender):
                                         W.shape[0], 0, scores.data_ptr(), _C.current_stream()), "fr_linear_fwd")
         return (torch.clamp(scores, min=0., max=eng.max_rating) / eng.max_rating).view(-1)
 
+    def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
+        """The pieces of full_sort_predict for fr_recommend_topk: the users' rows caught up, the item table flushed, and the
+        clamp to [0, max_rating] / max_rating as the kernel's epilogue."""
+        eng = self.hip_engine()
+        eng.finish()
+        eng.I.flush(eng.hyper)
+        user = interaction[self.USER_ID].to(eng.device, torch.int64).contiguous()
+        return {'X': eng.U.gather(eng.hyper, user, eng.err_flag), 'W': self.item_embedding_layer.weight.data, 'epilogue': 1,
+                'scale': float(eng.max_rating)}
+
     def state_dict(self, *args, **kwargs):
         if self._engine is not None:
             self._engine.flush()   # checkpoints must see every row at the current optimizer step

@@ -292,6 +292,37 @@ class PFCNBase(FairRecommender):
             return dyn_neg_dot_select(eng._tables[self._itab], eng._hyper(self._itab), ue, cand, num, M, eng.err_flag,
                                       item_bias=ib, user_bias=ub, global_bias=gb)
 
+    def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
+        """The pieces of predict() for fr_recommend_topk (PFCN_PMF / PFCN_BiasedMF; a model with a scorer or towers of its own
+        answers None): the filtered user embeddings, the flushed item table, the biases, and the sigmoid as the kernel's
+        epilogue.  The filters' BatchNorm layers normalise by the statistics of the batch they are given, so the users go
+        through them `users_per_batch` at a time -- the users of one predict() batch of the full-sort evaluation, whose
+        statistics over the repeated rows are those of the rows themselves."""
+        cls = type(self)
+        if (self.shard is not None or cls._predict_score is not PFCNBase._predict_score or cls._score is not PFCNBase._score
+                or cls._item_tower is not PFCNBase._item_tower or cls._user_tower is not PFCNBase._user_tower
+                or cls.predict is not PFCNBase.predict):
+            return None
+        eng = self.hip_engine()
+        if type(eng) is not GenericEngine:      # row-sharded / replicated engines: the generic path
+            return None
+        user = interaction[self.USER_ID]
+        with torch.no_grad():
+            ue = eng.lookup(self._utab, user)
+            if self.filter_mode != 'none':
+                per = int(users_per_batch) if users_per_batch else ue.shape[0]
+                ue = torch.cat([self._filter(ue[lo:lo + per], sst_list) for lo in range(0, ue.shape[0], per)]) \
+                    if ue.shape[0] else ue
+            it = eng._tables[self._itab]
+            it.flush(eng._hyper(self._itab))
+            out = {'X': ue, 'W': it.weight, 'epilogue': 2}
+            if self.biased:
+                ib = eng._tables["item_bias.weight"]
+                ib.flush(eng._hyper("item_bias.weight"))
+                out.update(user_bias=eng.lookup("user_bias.weight", user).view(-1), item_bias=ib.weight.view(-1),
+                           bias0=float(self.global_bias))
+            return out
+
     def get_sst_embed(self, user_data, sst_list=None):
         ret = {}
         idx = torch.arange(1, self.n_users)

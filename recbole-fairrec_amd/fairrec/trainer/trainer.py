@@ -385,24 +385,10 @@ class Trainer(AbstractTrainer):
     # --- full-sort ranking evaluation on the device (trainer.py:420-438, :458-515) ----------------------------
     def _full_sort_scores(self, interaction, n_items, sst_list=None):
         """[users, n_items] scores of a batch of users: `model.full_sort_predict`, or -- as the reference does when a
-        model has none (trainer.py:425-433) -- `predict` on every (user, item) pair, in chunks."""
-        extra = () if sst_list is None else (sst_list,)
-        from ..model.abstract_recommender import AbstractRecommender
-        if type(self.model).full_sort_predict is not AbstractRecommender.full_sort_predict:
-            try:
-                return self.model.full_sort_predict(interaction, *extra).view(-1, n_items)
-            except NotImplementedError:
-                pass
-        U = len(interaction)
-        items = torch.arange(n_items, device=self.device)
-        out = torch.empty((U, n_items), dtype=torch.float32, device=self.device)
-        per = max(int(self.config['eval_batch_size'] or 4096) // n_items, 1)
-        iid = self.config['ITEM_ID_FIELD']
-        for lo in range(0, U, per):
-            part = interaction[lo:lo + per].repeat_interleave(n_items)
-            part.update(type(part)({iid: items.repeat(min(per, U - lo))}))
-            out[lo:lo + per] = self.model.predict(part, *extra).view(-1, n_items)
-        return out
+        model has none (trainer.py:425-433) -- `predict` on every (user, item) pair, in chunks (shared with utils/case_study.py)."""
+        from ..utils.case_study import dense_full_sort_scores, users_per_batch
+        return dense_full_sort_scores(self.model, interaction, n_items, users_per_batch(self.config, n_items),
+                                      self.config['ITEM_ID_FIELD'], self.device, sst_list)
 
     def _ranking_evaluate(self, eval_data, sst_lists=(None,)):
         """One result over everything collected: every batch scored once per entry of `sst_lists` (None = no filter
