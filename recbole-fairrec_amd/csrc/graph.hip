@@ -98,11 +98,16 @@ __global__ __launch_bounds__(256) void spmm_csr_sel_kernel(const long long* __re
     if constexpr (V == 0) {
         for (int d = lane; d < D; d += 64) {
             float acc = 0.f;
+            bool touched = false;      // (wave-uniform) the row has had a term: only then is src read
             for (long long j = j0; j < j1; ++j) {
                 const int c = map ? map[col[j]] : col[j];
-                if (c >= 0) acc = fmaf(val[j], X[(size_t)c * D + d], acc);
+                if (c >= 0) {
+                    acc = fmaf(val[j], X[(size_t)c * D + d], acc);
+                    touched = true;
+                }
             }
-            if (ACT && !(ra.skip && ((ra.skip[i >> 5] >> (i & 31)) & 1u))) acc = acc * act_bwd(ra.src[(size_t)i * D + d], ra.act);
+            if (ACT && touched && !(ra.skip && ((ra.skip[i >> 5] >> (i & 31)) & 1u)))
+                acc = acc * act_bwd(ra.src[(size_t)i * D + d], ra.act);
             Y[(size_t)i * D + d] = acc;
         }
     } else {

@@ -17,13 +17,15 @@ __device__ __forceinline__ float act_fwd(float x, int act) {
     }
 }
 
-// derivative expressed through the OUTPUT y = act(x)
+// derivative expressed through the OUTPUT y = act(x).  tanh: 1 - y * y as ONE fused operation, written out -- left to the
+// compiler's contraction the same expression came out fused in one kernel and as a packed multiply and a subtraction in
+// another (spmm_csr_sel_runs_kernel<2, ., true>), and the fused passes no longer gave the bits of fr_act_bwd.
 __device__ __forceinline__ float act_bwd(float y, int act) {
     switch (act) {
         case ACT_RELU: return y > 0.f ? 1.f : 0.f;
         case ACT_LEAKY: return y > 0.f ? 1.f : 0.01f;
         case ACT_SIGMOID: return y * (1.f - y);
-        case ACT_TANH: return 1.f - y * y;
+        case ACT_TANH: return fmaf(-y, y, 1.f);
         default: return 1.f;
     }
 }
