@@ -1042,7 +1042,7 @@ FR_API int fr_prof_kernel_count(void);
 FR_API const char* fr_prof_kernel_name(int kind);
 FR_API int fr_prof_read(int kind, double* total_ms, int64_t* count);
 /* Algorithmic work the launches of `kind` stood for since the last reset: FLOP (2 M N K per product) for linear_fwd /
- * linear_bwd_input / linear_bwd_weight, bytes (12 nnz + 8 n_rows dim) for spmm_csr, 0 for the kinds that do not account.
+ * linear_bwd_input / linear_bwd_weight / mlp_infer, bytes (12 nnz + 8 n_rows dim) for spmm_csr, 0 for the kinds that do not account.
  * work / total_ms is the rate bench.py holds against the MFMA / HBM peak. */
 FR_API int fr_prof_read_work(int kind, double* work);
 
@@ -1122,6 +1122,48 @@ typedef struct fr_rec_args {
 } fr_rec_args;
 FR_API size_t fr_recommend_topk_workspace_bytes(const fr_rec_args* a);
 FR_API int fr_recommend_topk(const fr_rec_args* a, float* val_out, int64_t* idx_out, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * fr_mlp_infer: a whole MLP in one launch, for inference.  Each layer is Linear, then (optionally) BatchNorm1d on its RUNNING
+ * statistics, then the activation (the codes of fr_linear_fwd: 0 none, 1 relu, 2 leakyrelu 0.01, 3 sigmoid, 4 tanh);
+ *     Y[M, n_out_last] = (net_0(X) + net_1(X) + ...  in list order, fp32 adds from the first) / out_div      (IEEE division,
+ * also when out_div is 1).  Nothing is kept for a backward pass; there is no workspace and no atomic; no argument but Y is
+ * written -- the running statistics are read and never advanced, and there is no num_batches_tracked.
+ *
+ * Shapes: every width (k_in and each n_out) in 1..FR_MLP_INFER_MAX_WIDTH with no multiple asked of it, pointers float-aligned,
+ * 1..FR_MLP_INFER_MAX_LAYERS layers, 1..FR_MLP_INFER_MAX_NETS nets that share k_in and the last n_out.  M >= 0; M == 0 is
+ * success with nothing launched.  Anything else, a null pointer, an act outside 0..4, a partly-null BatchNorm quadruple or
+ * out_div == 0 is FR_EINVAL before anything is launched or written, and fr_last_error names the argument.
+ *
+ * Row independence: the bits of output row r depend on row r of X and on the parameters only -- not on M, on r's position, on
+ * the tile r falls in or on any other row's content (a NaN or Inf elsewhere does not reach it).  Row r of one layer, for
+ * output column j, in fp32 with every operation rounded to nearest:
+ *     acc = 0;  for k = 0, 2, 4, ... < n_in:  acc = (acc + x[k] W[j,k]) + x[k+1] W[j,k+1]     one v_mfma_f32_32x32x2_f32 per k
+ *               pair, ascending, the two products of a pair accumulated as the instruction does (x[n_in] = W[j,n_in] = 0
+ *               closes an odd n_in)
+ *     z   = acc + bias[j]
+ *     y   = fmaf(z - bn_mean[j], sc, bn_bias[j]),   sc = bn_weight[j] * (1 / sqrtf(bn_var[j] + bn_eps))     (BatchNorm layers;
+ *               sqrtf and the division correctly rounded)
+ *     out = act(y):  relu  y < 0 ? 0 : y;  leakyrelu  y < 0 ? 0.01f * y : y  (both keep a NaN);  sigmoid  1 / (1 + expf(-y));
+ *               tanh  tanhf(y)
+ * The order is the same for every shape: the kernel always cuts rows into tiles of 32, input columns into chunks of 32 and
+ * output columns into groups of 128, and a cell's chain does not see the cuts.
+ */
+#define FR_MLP_INFER_MAX_LAYERS 8
+#define FR_MLP_INFER_MAX_WIDTH  512
+#define FR_MLP_INFER_MAX_NETS   8
+typedef struct fr_mlp_layer {
+    const float *W, *bias;                 /* nn.Linear layout [n_out, n_in], [n_out] */
+    const float *bn_weight, *bn_bias, *bn_mean, *bn_var;   /* all four, or all NULL = no BatchNorm in this layer */
+    float bn_eps;
+    int32_t n_out;
+    int32_t act;                           /* the codes of fr_linear_fwd, 0..4 */
+} fr_mlp_layer;
+typedef struct fr_mlp_net {
+    int32_t n_layers, k_in;
+    fr_mlp_layer layer[FR_MLP_INFER_MAX_LAYERS];
+} fr_mlp_net;
+FR_API int fr_mlp_infer(const fr_mlp_net* nets, int32_t n_nets, float out_div, const float* X, int64_t M, float* Y, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,9 @@ DEV_ERR_SAMPLE_ROUNDS = 16
 EUNSUPPORTED = -3      # FR_EUNSUPPORTED
 WGRAD_MAX = 8          # FR_WGRAD_MAX
 FR_TOPK_MAX = 256
+MLP_INFER_MAX_LAYERS = 8   # FR_MLP_INFER_MAX_LAYERS
+MLP_INFER_MAX_WIDTH = 512  # FR_MLP_INFER_MAX_WIDTH
+MLP_INFER_MAX_NETS = 8     # FR_MLP_INFER_MAX_NETS
 
 FOCF_OBJECTIVES = {"none": 0, "value": 1, "absolute": 2, "under": 3, "over": 4, "nonparity": 5}
 
@@ -66,6 +69,15 @@ class FrRecArgs(Structure):     # include/fairrec_hip.h: fr_rec_args
                 ("hist_items", c_void_p), ("scores_out", c_void_p), ("n_users", c_int64), ("n_items", c_int64),
                 ("hist_len", c_int64), ("dim", c_int32), ("k", c_int32), ("epilogue", c_int32), ("mask_pad", c_int32),
                 ("hist_sorted", c_int32), ("slices", c_int32), ("bias0", c_float), ("scale", c_float)]
+
+
+class FrMlpLayer(Structure):   # include/fairrec_hip.h: fr_mlp_layer
+    _fields_ = [("W", c_void_p), ("bias", c_void_p), ("bn_weight", c_void_p), ("bn_bias", c_void_p), ("bn_mean", c_void_p),
+                ("bn_var", c_void_p), ("bn_eps", c_float), ("n_out", c_int32), ("act", c_int32)]
+
+
+class FrMlpNet(Structure):     # include/fairrec_hip.h: fr_mlp_net
+    _fields_ = [("n_layers", c_int32), ("k_in", c_int32), ("layer", FrMlpLayer * MLP_INFER_MAX_LAYERS)]
 
 
 class FairrecError(RuntimeError):
@@ -282,6 +294,7 @@ _PROTOS = {
                              c_void_p]),
     "fr_recommend_topk_workspace_bytes": (c_size_t, [POINTER(FrRecArgs)]),
     "fr_recommend_topk": (c_int, [POINTER(FrRecArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_mlp_infer": (c_int, [POINTER(FrMlpNet), c_int32, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "fr_rowdot_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_bpr_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "fr_bpr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -592,3 +592,51 @@ def recommend_topk(X, W, k, user_bias=None, item_bias=None, bias0=0.0, epilogue=
     _C.check(lib.fr_recommend_topk(ctypes.byref(a), val.data_ptr(), idx.data_ptr(), _C.ptr(ws), ws.numel() * 8,
                                    _C.current_stream()), "fr_recommend_topk")
     return (val, idx, scores) if want_scores else (val, idx)
+
+
+# ---- inference through whole MLPs in one launch (csrc/mlp_infer.hip) ----------------------------------------------------
+def mlp_net(module) -> "_C.FrMlpNet":
+    """The fr_mlp_net of an `MLPLayers` module: its Linear layers, its BatchNorm layers' RUNNING statistics, its activation.
+    The struct holds raw pointers: the module's tensors must outlive the launch it is handed to."""
+    from .model.layers import ACT_CODES
+    lins, bns = module.linears(), module.batchnorms()
+    if not 1 <= len(lins) <= _C.MLP_INFER_MAX_LAYERS:
+        raise ValueError(f'mlp_infer: {len(lins)} layers, not in 1..{_C.MLP_INFER_MAX_LAYERS}')
+    name = module.activation.lower() if isinstance(module.activation, str) else module.activation
+    net = _C.FrMlpNet()
+    net.n_layers, net.k_in = len(lins), lins[0].in_features
+    for l, lin in enumerate(lins):
+        bn = bns[l] if module.use_bn else None
+        tensors = [lin.weight, lin.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+        for t in tensors:
+            if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise _C.FairrecError('mlp_infer: every weight, bias and running statistic is a contiguous fp32 tensor on a ROCm '
+                                      'device (a Linear without bias or a BatchNorm without affine / running statistics is not served)')
+        net.layer[l] = _C.FrMlpLayer(*[t.data_ptr() for t in tensors], *([None] * (6 - len(tensors))),
+                                     float(bn.eps) if bn is not None else 0.0, lin.out_features, ACT_CODES[name])
+    return net
+
+
+def mlp_infer(nets, X, out_div=1.0):
+    """fr_mlp_infer: (nets[0](X) + nets[1](X) + ...) / out_div for `MLPLayers` modules (or prepared `mlp_net` structs) in ONE
+    launch -- Linear, BatchNorm1d on the running statistics, activation -- with every output row a function of its input row
+    alone.  Inference only: no autograd graph, no buffer of the modules is touched, dropout is not applied."""
+    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    if not 1 <= len(nets) <= _C.MLP_INFER_MAX_NETS:
+        raise ValueError(f'mlp_infer: {len(nets)} nets, not in 1..{_C.MLP_INFER_MAX_NETS}')
+    if not X.is_cuda:
+        raise _C.FairrecError('mlp_infer: ROCm device tensors only; there is no CPU fallback')
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise _C.FairrecError('mlp_infer: X is a [rows, k_in] fp32 matrix')
+    X = X.detach().contiguous()
+    structs = [n if isinstance(n, _C.FrMlpNet) else mlp_net(n) for n in nets]
+    if X.shape[1] != structs[0].k_in:
+        raise ValueError(f'mlp_infer: X has {X.shape[1]} columns, the nets take {structs[0].k_in}')
+    arr = (_C.FrMlpNet * len(structs))(*structs)
+    last = structs[0].layer[structs[0].n_layers - 1].n_out
+    Y = torch.empty((X.shape[0], last), dtype=torch.float32, device=X.device)
+    if X.shape[0] == 0:
+        return Y
+    _C.check(_C.lib().fr_mlp_infer(arr, len(structs), float(out_div), X.data_ptr(), X.shape[0], Y.data_ptr(),
+                                   _C.current_stream()), "fr_mlp_infer")
+    return Y

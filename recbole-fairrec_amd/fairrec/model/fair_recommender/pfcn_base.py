@@ -7,7 +7,11 @@ Plugin surface of recbole/model/fair_recommender/pfcn_biasedmf.py:24-242 / pfcn_
 get_sst_embed`; config keys `embedding_size, sst_attr_list, filter_mode, dis_dropout, dis_weight,
 dis_hidden_size_list, activation`.  As in the reference the filter / discriminator MLPs live in plain dicts: they are
 not in `parameters()` / `state_dict()`, and `model.eval()` never reaches them (BatchNorm keeps using batch statistics,
-SURVEY.md App. B-3).  Embedding rows come from lazy-Adam tables, MLPs run on the fp32-MFMA kernels, dot products /
+SURVEY.md App. B-3).  The config key `filter_eval_statistics: running` (default `batch` = the reference) lets
+`model.eval()` / `model.train()` reach the FILTERS (never the discriminators): evaluation and recommendation then filter
+through the BatchNorm running statistics in one fused launch (fr_mlp_infer), a user's filtered embedding is a function of
+that user alone, and scoring moves no buffer.  Training-mode forwards never read the running statistics, so the key does
+not change what is learnt.  Embedding rows come from lazy-Adam tables, MLPs run on the fp32-MFMA kernels, dot products /
 BPR / BCE / CE on csrc/pfcn.hip.
 """
 from __future__ import annotations
@@ -39,6 +43,10 @@ class PFCNBase(FairRecommender):
             assert self.filter_mode in ('cm', 'sm', 'none')
         except AssertionError:
             raise AssertionError('filter_mode must be cm, sm or none')
+        stats = config['filter_eval_statistics']
+        self.filter_eval_statistics = 'batch' if stats is None else str(stats).lower()
+        if self.filter_eval_statistics not in ('batch', 'running'):
+            raise ValueError(f'filter_eval_statistics must be batch or running, not [{stats}]')
         self.filter_num, self.sst_dict = self._get_filter_info()
         self.sst_size = self._get_sst_size(dataset.get_user_feature())
         if self.filter_mode != 'none':
@@ -154,12 +162,41 @@ class PFCNBase(FairRecommender):
             self._engine = eng
         return self._engine
 
+    def train(self, mode: bool = True):
+        """`filter_eval_statistics: running`: the mode also reaches the dict-held filters (not the discriminators, which
+        `predict` never calls and which keep the reference's behaviour); `batch`: nn.Module.train alone, as in the reference."""
+        super().train(mode)
+        if getattr(self, 'filter_eval_statistics', 'batch') == 'running' and getattr(self, 'filter_layer', None):
+            for mlp in self.filter_layer.values():
+                mlp.train(mode)
+        return self
+
     # --- forward pieces -------------------------------------------------------------------------------------------
+    def _filter_infer(self, user_embed, mlps, out_div):
+        """Filters in eval mode: (sum of `mlps` in list order) / out_div on the running statistics, ONE fr_mlp_infer launch per
+        FR_MLP_INFER_MAX_NETS filters; more than that are composed in the same order and division (the partial sums of the
+        launches added left to right, then the quotient)."""
+        from ...functional import mlp_infer
+        from ... import _C
+        n = _C.MLP_INFER_MAX_NETS
+        if len(mlps) <= n:
+            return mlp_infer(mlps, user_embed, out_div=out_div)
+        tmp = None
+        for lo in range(0, len(mlps), n):
+            e = mlp_infer(mlps[lo:lo + n], user_embed)
+            tmp = e if tmp is None else tmp + e
+        return tmp / out_div
+
     def _filter(self, user_embed, sst_list, passes=1):
         """pfcn_biasedmf.py:149-164: sm = ONE filter picked by the bit-mask sum of the selected attributes;
         cm = sum of the selected attributes' filters divided by the number of ALL filters."""
         if self.filter_mode == 'none':
             return user_embed
+        if self.filter_eval_statistics == 'running' and not torch.is_grad_enabled():
+            keys = [sum(self.sst_dict[s] for s in sst_list)] if self.filter_mode == 'sm' else [self.sst_dict[s] for s in sst_list]
+            mlps = [self.filter_layer[k] for k in keys]
+            if mlps and not any(m.training for m in mlps):
+                return self._filter_infer(user_embed, mlps, 1.0 if self.filter_mode == 'sm' else float(len(self.filter_layer)))
         if self.filter_mode == 'sm':
             return self.filter_layer[sum(self.sst_dict[s] for s in sst_list)](user_embed, passes=passes)
         tmp = None
@@ -297,7 +334,8 @@ class PFCNBase(FairRecommender):
         answers None): the filtered user embeddings, the flushed item table, the biases, and the sigmoid as the kernel's
         epilogue.  The filters' BatchNorm layers normalise by the statistics of the batch they are given, so the users go
         through them `users_per_batch` at a time -- the users of one predict() batch of the full-sort evaluation, whose
-        statistics over the repeated rows are those of the rows themselves."""
+        statistics over the repeated rows are those of the rows themselves.  (`filter_eval_statistics: running`, model in
+        eval mode: a row's filtered embedding does not depend on its group, and any `users_per_batch` gives the same bits.)"""
         cls = type(self)
         if (self.shard is not None or cls._predict_score is not PFCNBase._predict_score or cls._score is not PFCNBase._score
                 or cls._item_tower is not PFCNBase._item_tower or cls._user_tower is not PFCNBase._user_tower

@@ -1,7 +1,8 @@
 """`MLPLayers` with the constructor, module structure and parameter names of recbole/model/layers.py:30-85
 (per layer: Dropout -> Linear -> [BatchNorm1d] -> activation, the last layer included), so state_dict keys
 (`mlp_layers.<3l+1>.weight` ...) interchange with the reference.  The arithmetic runs on the fp32-MFMA kernels of
-csrc/mlp.hip through one autograd Function; there is no torch fallback for CUDA tensors and no CPU path.
+csrc/mlp.hip through one autograd Function; there is no torch fallback for CUDA tensors and no CPU path.  A module with
+BatchNorm in eval mode is served for inference (under no_grad) by the one-launch kernel of csrc/mlp_infer.hip.
 """
 from __future__ import annotations
 
@@ -432,12 +433,21 @@ class MLPLayers(nn.Module):
         returns the gradient at the top layer's PRE-activation (it has multiplied by act'(output) itself): the backward then
         skips its own pass through the top activation's derivative (a whole-table pass for FairGo's filters).
         BatchNorm layers always use batch statistics while `self.training` (and the reference's dict-held PFCN MLPs are
-        never switched to eval mode); eval-mode BatchNorm (running statistics) is not on this path."""
+        never switched to eval mode unless `filter_eval_statistics: running` asks for it).  In eval mode a
+        module with BatchNorm is inference only: under `torch.no_grad()` the whole module is ONE launch on the running
+        statistics (functional.mlp_infer / fr_mlp_infer) that touches no buffer and applies no dropout, every output row a
+        function of its input row alone; `passes`, `frozen` and `grad_at_z` mean nothing there, and a `second_block` is
+        concatenated on the host (the filters and discriminators never pass one).  With autograd enabled the call raises."""
         if input_feature.device.type != "cuda":
             raise _C.FairrecError("MLPLayers runs only on a ROCm device; there is no CPU fallback")
         lins, bns = self.linears(), self.batchnorms()
         if self.use_bn and not self.training:
-            raise NotImplementedError("eval-mode BatchNorm (running statistics) is not on the HIP path")
+            if torch.is_grad_enabled():
+                raise NotImplementedError("eval-mode BatchNorm (running statistics) is inference only on the HIP path: call the "
+                                          "module under torch.no_grad() (there is no backward through running statistics)")
+            from ..functional import mlp_infer
+            x = input_feature if second_block is None else torch.cat([input_feature, second_block], dim=1)
+            return mlp_infer(self, x.to(torch.float32))
         if self.use_bn:
             params = [t for lin, bn in zip(lins, bns) for t in (lin.weight, lin.bias, bn.weight, bn.bias)]
             if passes != 1 and (self.training and float(self.dropout) > 0.0):
