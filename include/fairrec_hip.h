@@ -1165,6 +1165,58 @@ typedef struct fr_mlp_net {
 } fr_mlp_net;
 FR_API int fr_mlp_infer(const fr_mlp_net* nets, int32_t n_nets, float out_div, const float* X, int64_t M, float* Y, void* stream);
 
+/*
+ * fr_pair_mlp_scores: every (user, item) score of an MLP scorer over cat(user, item) whose first Linear the caller has split,
+ *     z1(u, i) = (W1[:, :D] x_u + b1) + W1[:, D:] w_i = P[u] + Q[i]
+ * (P [n_users, n1] carries b1, Q [n_items, n1] carries no bias: two fr_linear_fwd products).  With the remaining n_linears - 1
+ * layers (W[l] [n_out[l], n_out[l-1]], bias[l]) in nn.Linear layout, the last with ONE output,
+ *     score(u, i) = sigmoid(act(w_L . act(... act(W[0] act(P[u] + Q[i]) + bias[0]) ...) + bias_L))
+ * the activation after every layer, the last included (MLPLayers.forward in eval mode), the sigmoid as 1 / (1 + expf(-x)) with
+ * the IEEE quotient (epilogue 2 of fr_recommend_topk).  act: the codes of fr_linear_fwd; only relu (1) is served.
+ * scores_out [n_users, ld], ld >= n_items: columns n_items .. ld-1 are not touched.  mask_pad: item 0 scores -inf; hist_indptr
+ * [n_users + 1] / hist_items [hist_len] as in fr_rec_args (either both or hist_indptr NULL), -inf at every listed cell, ascending
+ * within a user, which the caller states with hist_sorted = 1.  No workspace, no atomic; nothing but scores_out is written.
+ *
+ * Shapes: n1 and every n_out[l] in 1..FR_PAIR_MLP_MAX_WIDTH with no multiple asked of them, 2..FR_PAIR_MLP_MAX_LINEARS linears in
+ * the whole MLP (the split first layer counts), n_users, n_items >= 0 (zero: success, nothing launched).  Anything else, a null
+ * pointer, an act other than relu or hist_sorted != 1 with a history is FR_EINVAL before any device work, and fr_last_error
+ * names the argument.  fr_pair_mlp_supported: 1 when widths, layer count and activation are served (a host query).
+ *
+ * A cell's bits depend on P[u], Q[i] and the parameters alone -- not on n_users, n_items, ld, the tile or slice the cell falls
+ * in, or any other cell's content (a NaN elsewhere does not reach it).  Cell (u, i), in fp32, every operation rounded to nearest:
+ *     h[c] = relu(P[u, c] + Q[i, c])                                                  one add per column
+ *     each further layer, output column j:  acc = 0;  for k = 0, 2, 4, ... < n_in:  acc = (acc + h[k] W[j,k]) + h[k+1] W[j,k+1]
+ *               one v_mfma_f32_32x32x2_f32 per k pair: an ascending-column fmaf chain from 0 (h[n_in] = W[j,n_in] = 0 closes
+ *               an odd n_in);  z = acc + bias[j], the bias added last;  h'[j] = relu(z)
+ *     score = 1 / (1 + expf(-relu(z_L)))
+ * relu(x) is x < 0 ? 0 : x: it KEEPS a NaN, as every relu of fr_linear_fwd does (x <= 0 ? 0 : x, or v > 0 ? v : v * 0 in its
+ * fast forms; fmaxf would return the other operand), so a NaN in P[u] or Q[i] reaches every unmasked score of that user or
+ * item, as it does through predict.
+ */
+#define FR_PAIR_MLP_MAX_LINEARS 6
+#define FR_PAIR_MLP_MAX_WIDTH   256
+typedef struct fr_pair_mlp_args {
+    const float* P;                                   /* [n_users, n1], b1 added */
+    const float* Q;                                   /* [n_items, n1] */
+    const float* W[FR_PAIR_MLP_MAX_LINEARS - 1];      /* linears 2 .. n_linears */
+    const float* bias[FR_PAIR_MLP_MAX_LINEARS - 1];
+    const int64_t* hist_indptr;                       /* [n_users + 1] or NULL */
+    const int64_t* hist_items;                        /* [hist_len] */
+    float* scores_out;                                /* [n_users, ld] */
+    int64_t n_users;
+    int64_t n_items;
+    int64_t ld;
+    int64_t hist_len;
+    int32_t n_out[FR_PAIR_MLP_MAX_LINEARS - 1];       /* the last used entry is 1 */
+    int32_t n1;
+    int32_t n_linears;                                /* of the whole MLP: 2..FR_PAIR_MLP_MAX_LINEARS */
+    int32_t act;
+    int32_t mask_pad;
+    int32_t hist_sorted;
+} fr_pair_mlp_args;
+FR_API int fr_pair_mlp_supported(int32_t n1, int32_t n_linears, const int32_t* n_out, int32_t act);
+FR_API int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

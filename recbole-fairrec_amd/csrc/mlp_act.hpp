@@ -9,7 +9,7 @@ enum { ACT_NONE = 0, ACT_RELU = 1, ACT_LEAKY = 2, ACT_SIGMOID = 3, ACT_TANH = 4 
 
 __device__ __forceinline__ float act_fwd(float x, int act) {
     switch (act) {
-        case ACT_RELU: return x > 0.f ? x : 0.f;
+        case ACT_RELU: return x <= 0.f ? 0.f : x;      // keeps a NaN, as torch.relu and the fast forms' v > 0 ? v : v * 0 do
         case ACT_LEAKY: return x > 0.f ? x : 0.01f * x;
         case ACT_SIGMOID: return 1.f / (1.f + __expf(-x));
         case ACT_TANH: return tanhf(x);

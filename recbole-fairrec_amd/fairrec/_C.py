@@ -25,6 +25,8 @@ FR_TOPK_MAX = 256
 MLP_INFER_MAX_LAYERS = 8   # FR_MLP_INFER_MAX_LAYERS
 MLP_INFER_MAX_WIDTH = 512  # FR_MLP_INFER_MAX_WIDTH
 MLP_INFER_MAX_NETS = 8     # FR_MLP_INFER_MAX_NETS
+PAIR_MLP_MAX_LINEARS = 6   # FR_PAIR_MLP_MAX_LINEARS
+PAIR_MLP_MAX_WIDTH = 256   # FR_PAIR_MLP_MAX_WIDTH
 
 FOCF_OBJECTIVES = {"none": 0, "value": 1, "absolute": 2, "under": 3, "over": 4, "nonparity": 5}
 
@@ -78,6 +80,14 @@ class FrMlpLayer(Structure):   # include/fairrec_hip.h: fr_mlp_layer
 
 class FrMlpNet(Structure):     # include/fairrec_hip.h: fr_mlp_net
     _fields_ = [("n_layers", c_int32), ("k_in", c_int32), ("layer", FrMlpLayer * MLP_INFER_MAX_LAYERS)]
+
+
+class FrPairMlpArgs(Structure):     # include/fairrec_hip.h: fr_pair_mlp_args
+    _fields_ = [("P", c_void_p), ("Q", c_void_p), ("W", c_void_p * (PAIR_MLP_MAX_LINEARS - 1)),
+                ("bias", c_void_p * (PAIR_MLP_MAX_LINEARS - 1)), ("hist_indptr", c_void_p), ("hist_items", c_void_p),
+                ("scores_out", c_void_p), ("n_users", c_int64), ("n_items", c_int64), ("ld", c_int64), ("hist_len", c_int64),
+                ("n_out", c_int32 * (PAIR_MLP_MAX_LINEARS - 1)), ("n1", c_int32), ("n_linears", c_int32), ("act", c_int32),
+                ("mask_pad", c_int32), ("hist_sorted", c_int32)]
 
 
 class FairrecError(RuntimeError):
@@ -295,6 +305,8 @@ _PROTOS = {
     "fr_recommend_topk_workspace_bytes": (c_size_t, [POINTER(FrRecArgs)]),
     "fr_recommend_topk": (c_int, [POINTER(FrRecArgs), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_mlp_infer": (c_int, [POINTER(FrMlpNet), c_int32, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    "fr_pair_mlp_supported": (c_int, [c_int32, c_int32, POINTER(c_int32), c_int32]),
+    "fr_pair_mlp_scores": (c_int, [POINTER(FrPairMlpArgs), c_void_p]),
     "fr_rowdot_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_bpr_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "fr_bpr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

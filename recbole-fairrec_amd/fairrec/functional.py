@@ -640,3 +640,89 @@ def mlp_infer(nets, X, out_div=1.0):
     _C.check(_C.lib().fr_mlp_infer(arr, len(structs), float(out_div), X.data_ptr(), X.shape[0], Y.data_ptr(),
                                    _C.current_stream()), "fr_mlp_infer")
     return Y
+
+
+# ---- all-item scores of an MLP scorer over cat(user, item), first layer split (csrc/pair_mlp.hip) ------------------------
+def pair_mlp_supported(mlp, n_first=None) -> bool:
+    """Does fr_pair_mlp_scores serve this `MLPLayers` scorer?  ReLU, no BatchNorm, no recorded dropout masks, 2..6 linears with
+    biases, one output, the first layer's and every hidden width in 1..256."""
+    from .model.layers import ACT_CODES
+    name = mlp.activation.lower() if isinstance(mlp.activation, str) else mlp.activation
+    lins = mlp.linears()
+    if mlp.use_bn or mlp.forced_masks is not None or any(lin.bias is None for lin in lins):
+        return False
+    if not 2 <= len(lins) <= _C.PAIR_MLP_MAX_LINEARS:
+        return False
+    n_out = (ctypes.c_int32 * (len(lins) - 1))(*[lin.out_features for lin in lins[1:]])
+    return bool(_C.lib().fr_pair_mlp_supported(lins[0].out_features if n_first is None else n_first, len(lins), n_out,
+                                               ACT_CODES[name]))
+
+
+def pair_mlp_pieces(mlp, user_rows, item_rows):
+    """The pieces fr_pair_mlp_scores takes, of an `MLPLayers` scorer over cat(user_rows[u], item_rows[i]): P = user_rows
+    W1[:, :D]^T + b1 and Q = item_rows W1[:, D:]^T (two fr_linear_fwd products), and the remaining layers' parameters.  Nothing
+    is kept between calls: the parameters may move."""
+    lins = mlp.linears()
+    x = user_rows.detach().to(torch.float32).contiguous()
+    w = item_rows.detach().to(torch.float32).contiguous()
+    D, Di = x.shape[1], w.shape[1]
+    W1 = lins[0].weight.detach()
+    if W1.shape[1] != D + Di:
+        raise ValueError(f'pair_mlp_pieces: the first layer takes {W1.shape[1]} columns, the rows have {D} + {Di}')
+    n1 = W1.shape[0]
+    lib, st = _C.lib(), _C.current_stream()
+
+    def product(rows, Wpart, bias):
+        out = torch.empty((rows.shape[0], n1), dtype=torch.float32, device=rows.device)
+        if rows.shape[0]:
+            _C.check(lib.fr_linear_fwd(rows.data_ptr(), rows.shape[1], None, 0, None, 1.0, Wpart.data_ptr(), _C.ptr(bias),
+                                       rows.shape[0], n1, 0, out.data_ptr(), st), "fr_linear_fwd")
+        return out
+
+    P = product(x, W1[:, :D].contiguous(), lins[0].bias.detach().contiguous())
+    Q = product(w, W1[:, D:].contiguous(), None)
+    return {'P': P, 'Q': Q, 'layers': [(lin.weight.detach().contiguous(), lin.bias.detach().contiguous()) for lin in lins[1:]]}
+
+
+def pair_mlp_scores(pieces, mask_pad=False, hist_indptr=None, hist_items=None, out=None, act=1):
+    """fr_pair_mlp_scores: the dense [users, items] matrix sigmoid(act(upper layers(act(P[u] + Q[i])))) of `pair_mlp_pieces`,
+    the pad item and the history CSR (ascending within a user) scored -inf.  `out`: a [users, >= items] fp32 buffer with unit
+    column stride to write into (its columns beyond the items are left alone)."""
+    P, Q, layers = pieces['P'], pieces['Q'], pieces['layers']
+    if not P.is_cuda:
+        raise _C.FairrecError('pair_mlp_scores: ROCm device tensors only; there is no CPU fallback')
+    P, Q = P.contiguous(), Q.contiguous()
+    U, N, dev = P.shape[0], Q.shape[0], P.device
+    if not 1 <= len(layers) <= _C.PAIR_MLP_MAX_LINEARS - 1:
+        raise ValueError(f'pair_mlp_scores: {len(layers) + 1} linears, not in 2..{_C.PAIR_MLP_MAX_LINEARS}')
+    if P.dim() != 2 or Q.dim() != 2 or Q.shape[1] != P.shape[1] or P.dtype != torch.float32 or Q.dtype != torch.float32 \
+            or Q.device != dev:
+        raise ValueError('pair_mlp_scores: P [users, n1] and Q [items, n1], fp32, on one device')
+    n_in = P.shape[1]
+    for W, b in layers:
+        if tuple(W.shape[1:]) != (n_in,) or tuple(b.shape) != (W.shape[0],) or W.dtype != torch.float32 or b.dtype != torch.float32 \
+                or W.device != dev or b.device != dev or not W.is_contiguous() or not b.is_contiguous():
+            raise ValueError('pair_mlp_scores: each layer is (W [n_out, n_in], bias [n_out]), contiguous fp32 on the device of P')
+        n_in = W.shape[0]
+    if out is None:
+        out = torch.empty((U, N), dtype=torch.float32, device=dev)
+    if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != U or out.shape[1] < N or (N and out.stride(1) != 1):
+        raise _C.FairrecError('pair_mlp_scores: out is a [users, >= items] fp32 matrix with unit column stride')
+    if U == 0 or N == 0:
+        return out
+    ld = out.stride(0) if U > 1 else max(out.stride(0), out.shape[1])
+    ip = hi = None
+    if hist_indptr is not None:
+        ip = hist_indptr.to(dev, torch.int64).contiguous()
+        hi = hist_items.to(dev, torch.int64).contiguous()
+        if ip.numel() != U + 1:
+            raise ValueError('pair_mlp_scores: hist_indptr [users + 1]')
+    a = _C.FrPairMlpArgs()
+    a.P, a.Q = P.data_ptr(), Q.data_ptr()
+    for l, (W, b) in enumerate(layers):
+        a.W[l], a.bias[l], a.n_out[l] = W.data_ptr(), b.data_ptr(), W.shape[0]
+    a.hist_indptr, a.hist_items, a.scores_out = _C.ptr(ip), _C.ptr(hi), out.data_ptr()
+    a.n_users, a.n_items, a.ld, a.hist_len = U, N, ld, hi.numel() if hi is not None else 0
+    a.n1, a.n_linears, a.act, a.mask_pad, a.hist_sorted = P.shape[1], len(layers) + 1, int(act), int(bool(mask_pad)), 1
+    _C.check(_C.lib().fr_pair_mlp_scores(ctypes.byref(a), _C.current_stream()), "fr_pair_mlp_scores")
+    return out

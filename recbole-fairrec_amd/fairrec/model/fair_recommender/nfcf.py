@@ -17,7 +17,7 @@ from ... import _C
 from ...engine import GenericEngine
 from ...utils.enum_type import InputType
 from ..abstract_recommender import FairRecommender
-from ..layers import MLPLayers
+from ..layers import MLPLayers, full_sort_pair_mlp_pieces, full_sort_scorer_of
 
 
 class _NfcfLoss(torch.autograd.Function):
@@ -169,6 +169,7 @@ class NFCF(FairRecommender):
         self.sst_attr = config['sst_attr_list'][0]
         self.fair_weight = config['fair_weight']
         self.load_pretrain_path = config['load_pretrain_path']
+        self.full_sort_scorer = full_sort_scorer_of(config)
 
         self.user_embedding = nn.Embedding(self._table_rows(self.n_users), self.embedding_size)   # default N(0,1) init, as nfcf.py:38-39
         self.item_embedding = nn.Embedding(self._table_rows(self.n_items), self.embedding_size)
@@ -283,6 +284,16 @@ class NFCF(FairRecommender):
 
     def predict(self, interaction):
         return self.forward(interaction[self.USER_ID], interaction[self.ITEM_ID])
+
+    def full_sort_pair_mlp(self, interaction, sst_list=None, users_per_batch=None):
+        """The pieces of predict() on every item for fr_pair_mlp_scores (`full_sort_scorer: split`), or None: the dense path
+        then serves the call (fairrec/model/layers.py: full_sort_pair_mlp_pieces)."""
+        if self.shard is not None:
+            return None
+        eng = self.hip_engine()
+        return full_sort_pair_mlp_pieces(self.full_sort_scorer, self.mlp_layers, eng,
+                                         lambda: eng.lookup("user_embedding.weight", interaction[self.USER_ID]),
+                                         "item_embedding.weight", self.n_items)
 
     def state_dict(self, *args, **kwargs):
         if self._engine is not None:

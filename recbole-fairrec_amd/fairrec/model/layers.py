@@ -497,3 +497,28 @@ class MLPLayers(nn.Module):
         if st is None or st.device != device:
             st = self._dstate = torch.zeros(2, dtype=torch.int64, device=device)     # {call counter, ticket}
         return st
+
+
+def full_sort_scorer_of(config) -> str:
+    """The config key `full_sort_scorer` of the MLP-scored models (NFCF, PFCN_MLP): `pairs` (default: `predict` on every
+    (user, item) pair, the reference) or `split` (first layer split, the rest per pair in one kernel: fr_pair_mlp_scores)."""
+    value = config['full_sort_scorer']
+    name = 'pairs' if value is None else str(value).lower()
+    if name not in ('pairs', 'split'):
+        raise ValueError(f'full_sort_scorer must be pairs or split, not [{value}]')
+    return name
+
+
+def full_sort_pair_mlp_pieces(scorer, mlp, engine, user_rows, item_table_name, n_items):
+    """What a model's `full_sort_pair_mlp` hook answers: the pieces of fr_pair_mlp_scores for the scorer `mlp` over
+    cat(user_rows[u], item table row i), or None -- the dense path then serves the call -- when the key is `pairs`, the
+    scorer has BatchNorm, an activation other than ReLU, recorded dropout masks or a shape outside fr_pair_mlp_supported, or
+    the engine is not the single-device GenericEngine.  `user_rows`: a callable, so that nothing is looked up for a None."""
+    from ..engine import GenericEngine
+    from ..functional import pair_mlp_pieces, pair_mlp_supported
+    if scorer != 'split' or type(engine) is not GenericEngine or not pair_mlp_supported(mlp):
+        return None
+    with torch.no_grad():
+        table = engine._tables[item_table_name]
+        table.flush(engine._hyper(item_table_name))
+        return pair_mlp_pieces(mlp, user_rows(), table.weight[:n_items])

@@ -385,8 +385,12 @@ class Trainer(AbstractTrainer):
     # --- full-sort ranking evaluation on the device (trainer.py:420-438, :458-515) ----------------------------
     def _full_sort_scores(self, interaction, n_items, sst_list=None):
         """[users, n_items] scores of a batch of users: `model.full_sort_predict`, or -- as the reference does when a
-        model has none (trainer.py:425-433) -- `predict` on every (user, item) pair, in chunks (shared with utils/case_study.py)."""
-        from ..utils.case_study import dense_full_sort_scores, users_per_batch
+        model has none (trainer.py:425-433) -- `predict` on every (user, item) pair, in chunks (shared with utils/case_study.py).
+        A model whose `full_sort_pair_mlp` hook answers (`full_sort_scorer: split`) is scored by fr_pair_mlp_scores instead."""
+        from ..utils.case_study import dense_full_sort_scores, split_full_sort_scores, users_per_batch
+        scores = split_full_sort_scores(self.model, interaction, users_per_batch(self.config, n_items), sst_list)
+        if scores is not None:
+            return scores
         return dense_full_sort_scores(self.model, interaction, n_items, users_per_batch(self.config, n_items),
                                       self.config['ITEM_ID_FIELD'], self.device, sst_list)
 

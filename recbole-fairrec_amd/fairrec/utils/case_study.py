@@ -2,8 +2,11 @@
 
 `full_sort_scores` / `full_sort_topk` (reference case_study.py:20-91) for a list of users, on the device, plus the optional
 attribute subset the filtered models take.  A dot-product model answers `full_sort_factors` and is ranked by
-fr_recommend_topk, which never stores the [users, n_items] matrix; every other model is scored densely (the scores the
-Trainer's full-sort evaluation ranks: `dense_full_sort_scores`) and ranked by fr_topk_rows.  Both rank by the library's
+fr_recommend_topk, which never stores the [users, n_items] matrix; a model whose MLP scorer over cat(user, item) answers
+`full_sort_pair_mlp` (NFCF, PFCN_MLP with `full_sort_scorer: split`) is scored by fr_pair_mlp_scores -- the first layer
+split into a user half and an item half, the rest per pair in one kernel -- and ranked by fr_topk_rows; every other model
+is scored densely (the scores the Trainer's full-sort evaluation ranks: `dense_full_sort_scores`) and ranked by
+fr_topk_rows.  All rank by the library's
 total order -- higher score first, NaN first of all, the lower item id among equal scores -- where torch.topk leaves the
 order of equal scores open.  The pad item and each user's history (the items of earlier phases, as the reference's
 `uid2history_item`) score -inf.  Single device; there is no CPU path.
@@ -36,6 +39,17 @@ def dense_full_sort_scores(model, interaction, n_items, users_per_batch, iid_fie
         part.update(type(part)({iid_field: items.repeat(min(per, U - lo))}))
         out[lo:lo + per] = model.predict(part, *extra).view(-1, n_items)
     return out
+
+
+def split_full_sort_scores(model, interaction, users_per_batch, sst_list=None):
+    """The [users, n_items] scores of `model.full_sort_pair_mlp`'s pieces, unmasked, or None when the model has no such hook
+    or the hook declines (the dense path then serves the call)."""
+    hook = getattr(model, 'full_sort_pair_mlp', None)
+    pieces = hook(interaction, sst_list, users_per_batch=users_per_batch) if hook is not None else None
+    if pieces is None:
+        return None
+    from ..functional import pair_mlp_scores
+    return pair_mlp_scores(pieces)
 
 
 def users_per_batch(config, n_items):
@@ -85,6 +99,17 @@ class _Request:
         hook = getattr(self.model, 'full_sort_factors', None)
         return hook(self.interaction, sst_list, users_per_batch=self.per) if hook is not None else None
 
+    def pair_mlp(self, sst_list):
+        hook = getattr(self.model, 'full_sort_pair_mlp', None)
+        return hook(self.interaction, sst_list, users_per_batch=self.per) if hook is not None else None
+
+    def split(self, pieces, lo, hi, out=None):
+        """Rows lo..hi of the split scorer's masked matrix (fr_pair_mlp_scores)."""
+        from ..functional import pair_mlp_scores
+        a, b = int(self.indptr[lo]), int(self.indptr[hi])
+        return pair_mlp_scores(dict(pieces, P=pieces['P'][lo:hi]), mask_pad=True, hist_indptr=self.indptr[lo:hi + 1] - a,
+                               hist_items=self.items[a:b], out=out)
+
     def dense(self, lo, hi, sst_list):
         """Rows lo..hi of the dense scores, masked as the Trainer masks them."""
         scores = dense_full_sort_scores(self.model, self.interaction[lo:hi], self.n_items, self.per, self.iid_field,
@@ -123,7 +148,8 @@ DENSE_ROWS_BYTES = 1 << 30      # dense path of full_sort_topk: users are ranked
 def full_sort_scores(uid_series, model, test_data, device=None, sst_list=None):
     """[len(uid_series), n_items] scores of every item for the given (internal) user ids, in the order given; the pad item
     and each user's history are -inf.  For a model with `full_sort_factors` these are exactly the scores `full_sort_topk`
-    ranks (one kernel writes them and selects from them)."""
+    ranks (one kernel writes them and selects from them); so they are with `full_sort_pair_mlp` (a cell's bits depend on its
+    user, its item and the parameters alone)."""
     req = _Request(uid_series, model, test_data, device)
     with _EvalMode(model):
         f = req.factors(sst_list)
@@ -131,6 +157,9 @@ def full_sort_scores(uid_series, model, test_data, device=None, sst_list=None):
             if req.uids.numel() == 0:
                 return torch.empty((0, req.n_items), dtype=torch.float32, device=req.device)
             return req.fused(f, 1, True)[2]
+        pieces = req.pair_mlp(sst_list)
+        if pieces is not None:
+            return req.split(pieces, 0, req.uids.numel())
         return req.dense(0, req.uids.numel(), sst_list)
 
 
@@ -150,10 +179,16 @@ def full_sort_topk(uid_series, model, test_data, k, device=None, sst_list=None):
         if f is not None:
             return req.fused(f, k, False)
         U = req.uids.numel()
-        group = max(DENSE_ROWS_BYTES // (4 * req.n_items) // req.per, 1) * req.per      # whole predict batches
+        pieces = req.pair_mlp(sst_list)
+        if pieces is not None:      # (the users' halves are formed already: any grouping gives the same bits)
+            group = max(DENSE_ROWS_BYTES // (4 * req.n_items), 1)
+            buf = torch.empty((min(group, U), req.n_items), dtype=torch.float32, device=req.device)
+        else:
+            group = max(DENSE_ROWS_BYTES // (4 * req.n_items) // req.per, 1) * req.per      # whole predict batches
         vals, idxs = [], []
         for lo in range(0, U, group):
-            v, i = topk_rows(req.dense(lo, min(lo + group, U), sst_list), k)
+            hi = min(lo + group, U)
+            v, i = topk_rows(req.split(pieces, lo, hi, buf[:hi - lo]) if pieces is not None else req.dense(lo, hi, sst_list), k)
             vals.append(v)
             idxs.append(i)
         if not vals:
