@@ -1217,6 +1217,57 @@ typedef struct fr_pair_mlp_args {
 FR_API int fr_pair_mlp_supported(int32_t n1, int32_t n_linears, const int32_t* n_out, int32_t act);
 FR_API int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream);
 
+/*
+ * fr_dyn_neg_mlp_select: the pick of dynamic negative sampling (fr_dyn_neg_select) for an MLP scorer over cat(user, item),
+ * scores computed in the kernel with the first Linear split as fr_pair_mlp_scores splits it,
+ *     z1 = (W1[:, :D] x_u + b1) + W1[:, D:] w_c = P[i] + q(c)
+ * P [n, n1] (leading dimension ldp >= n1) is the caller's one product over the n batch rows and carries b1; q(c) is formed in
+ * the kernel from the candidate's item row, which is never materialised.  W1_item points INTO the [n1, 2 D] first weight
+ * (W1 + D) and ldw1 is that weight's row stride (2 D): nothing is copied.  W[l], bias[l], n_out[l], n_linears, act: the
+ * remaining linears, as in fr_pair_mlp_args.  Candidate r of output column c = j*n + i (j < num) is cand[(r*num + j)*n + i],
+ * its user row is row i of P: the layout of fr_dyn_neg_dot_select.  out [num*n].
+ * fr_dyn_neg_mlp_scores: the [M*num*n] scores the pick is taken from, in cand's order (for checking them); the same kernel,
+ * so the same bits.
+ *
+ * Shapes: fr_pair_mlp_supported(n1, n_linears, n_out, act) and 1 <= D = item_t->dim <= 256; n >= 0, num >= 1, M >= 1.  Anything
+ * else, a null pointer (err_flag included) or an unknown learner is FR_EINVAL before any device work, and fr_last_error names
+ * the argument.  n == 0 is success with nothing launched.
+ *
+ * Candidate (r, c), in fp32, every operation rounded to nearest:
+ *     w       = the item row cand[...] as of the table's step: the replay fr_table_gather and fr_dyn_neg_dot_select do
+ *     q[j]    = acc,  acc = 0;  for k = 0, 2, 4, ... < D:  acc = (acc + w[k] W1[j, D+k]) + w[k+1] W1[j, D+k+1]
+ *               one v_mfma_f32_32x32x2_f32 per k pair: an ascending-column fmaf chain from 0 (w[D] = W1[j, 2 D] = 0 closes an
+ *               odd D)
+ *     h[j]    = relu(P[i, j] + q[j])                                                  one add per column
+ *     every further layer, the one-output layer, relu (x < 0 ? 0 : x: it KEEPS a NaN) and score = 1 / (1 + expf(-relu(z_L))):
+ *               exactly as fr_pair_mlp_scores states them
+ * The pick of a column follows torch.max(dim=0): the lowest r among equal maxima, a NaN beats every number, the first NaN
+ * wins.  A candidate's score bits depend on its row as of the step, its P row and the parameters alone -- not on n, num, M,
+ * its position or any other candidate (a NaN elsewhere does not reach it).  An id outside the item table sets
+ * FR_DEV_ERR_INDEX_RANGE in *err_flag; its loads stay on a clamped index (row 0) and the id itself is what a pick of it
+ * returns.  No workspace, no atomic but the flag's; nothing but out / scores and the flag is written, the table never.
+ */
+typedef struct fr_dyn_neg_mlp_args {
+    const fr_table* item_t;
+    const fr_optim* item_optim;
+    const float* P;                                   /* [n, ldp], b1 added */
+    const float* W1_item;                             /* W1 + D: row j at W1_item + j*ldw1, D columns */
+    const float* W[FR_PAIR_MLP_MAX_LINEARS - 1];      /* linears 2 .. n_linears */
+    const float* bias[FR_PAIR_MLP_MAX_LINEARS - 1];
+    const int64_t* cand;                              /* [M*num*n] */
+    int64_t ldp;
+    int64_t ldw1;
+    int64_t n;
+    int32_t n_out[FR_PAIR_MLP_MAX_LINEARS - 1];       /* the last used entry is 1 */
+    int32_t n1;
+    int32_t n_linears;                                /* of the whole MLP: 2..FR_PAIR_MLP_MAX_LINEARS */
+    int32_t act;
+    int32_t num;
+    int32_t M;
+} fr_dyn_neg_mlp_args;
+FR_API int fr_dyn_neg_mlp_select(const fr_dyn_neg_mlp_args* a, int64_t* out, uint32_t* err_flag, void* stream);
+FR_API int fr_dyn_neg_mlp_scores(const fr_dyn_neg_mlp_args* a, float* scores, uint32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

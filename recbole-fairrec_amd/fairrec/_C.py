@@ -90,6 +90,14 @@ class FrPairMlpArgs(Structure):     # include/fairrec_hip.h: fr_pair_mlp_args
                 ("mask_pad", c_int32), ("hist_sorted", c_int32)]
 
 
+class FrDynNegMlpArgs(Structure):   # include/fairrec_hip.h: fr_dyn_neg_mlp_args
+    _fields_ = [("item_t", POINTER(FrTable)), ("item_optim", POINTER(FrAdam)), ("P", c_void_p), ("W1_item", c_void_p),
+                ("W", c_void_p * (PAIR_MLP_MAX_LINEARS - 1)), ("bias", c_void_p * (PAIR_MLP_MAX_LINEARS - 1)),
+                ("cand", c_void_p), ("ldp", c_int64), ("ldw1", c_int64), ("n", c_int64),
+                ("n_out", c_int32 * (PAIR_MLP_MAX_LINEARS - 1)), ("n1", c_int32), ("n_linears", c_int32), ("act", c_int32),
+                ("num", c_int32), ("M", c_int32)]
+
+
 class FairrecError(RuntimeError):
     pass
 
@@ -307,6 +315,8 @@ _PROTOS = {
     "fr_mlp_infer": (c_int, [POINTER(FrMlpNet), c_int32, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "fr_pair_mlp_supported": (c_int, [c_int32, c_int32, POINTER(c_int32), c_int32]),
     "fr_pair_mlp_scores": (c_int, [POINTER(FrPairMlpArgs), c_void_p]),
+    "fr_dyn_neg_mlp_select": (c_int, [POINTER(FrDynNegMlpArgs), c_void_p, c_void_p, c_void_p]),
+    "fr_dyn_neg_mlp_scores": (c_int, [POINTER(FrDynNegMlpArgs), c_void_p, c_void_p, c_void_p]),
     "fr_rowdot_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "fr_bpr_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "fr_bpr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

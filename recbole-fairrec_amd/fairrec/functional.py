@@ -726,3 +726,69 @@ def pair_mlp_scores(pieces, mask_pad=False, hist_indptr=None, hist_items=None, o
     a.n1, a.n_linears, a.act, a.mask_pad, a.hist_sorted = P.shape[1], len(layers) + 1, int(act), int(bool(mask_pad)), 1
     _C.check(_C.lib().fr_pair_mlp_scores(ctypes.byref(a), _C.current_stream()), "fr_pair_mlp_scores")
     return out
+
+
+# ---- dynamic negatives of an MLP scorer over cat(user, item), first layer split (csrc/dyn_neg_mlp.hip) --------------------
+def dyn_neg_mlp_pieces(mlp, user_rows):
+    """The pieces fr_dyn_neg_mlp_select takes, of an `MLPLayers` scorer over cat(user_rows[i], item row): P = user_rows
+    W1[:, :D]^T + b1 (one fr_linear_fwd product over the batch rows), the first weight itself -- its item half is read in place
+    -- and the remaining layers' parameters.  Nothing is kept between calls: the parameters may move."""
+    lins = mlp.linears()
+    x = user_rows.detach().to(torch.float32).contiguous()
+    D = x.shape[1]
+    W1 = lins[0].weight.detach().contiguous()
+    if W1.shape[1] <= D:
+        raise ValueError(f'dyn_neg_mlp_pieces: the first layer takes {W1.shape[1]} columns, the user rows alone have {D}')
+    n1 = W1.shape[0]
+    P = torch.empty((x.shape[0], n1), dtype=torch.float32, device=x.device)
+    if x.shape[0]:
+        _C.check(_C.lib().fr_linear_fwd(x.data_ptr(), D, None, 0, None, 1.0, W1[:, :D].contiguous().data_ptr(),
+                                        lins[0].bias.detach().contiguous().data_ptr(), x.shape[0], n1, 0, P.data_ptr(),
+                                        _C.current_stream()), "fr_linear_fwd")
+    return {'P': P, 'W1': W1, 'layers': [(lin.weight.detach().contiguous(), lin.bias.detach().contiguous()) for lin in lins[1:]]}
+
+
+def dyn_neg_mlp_select(pieces, item_table, item_hyper, cand, num, M, err_flag, want_scores=False):
+    """fr_dyn_neg_mlp_select: of the M candidates cand[(r*num + j)*n + i] of column j*n + i keep the one the scorer rates
+    highest, sigmoid(relu(upper layers(relu(P[i] + W1[:, D_user:] w_c)))) with w_c the candidate's row of the lazy item table as
+    of its step, never materialised.  `pieces`: {'P': [n, n1] (the user half of the first layer, bias added), 'W1': the first
+    layer's whole [n1, D_user + D] weight (its item half is read in place), 'layers': the remaining (W, bias)}.
+    `want_scores`: (ids, the [M*num*n] scores in cand's order they were picked from) -- fr_dyn_neg_mlp_scores, a second launch."""
+    P, W1, layers = pieces['P'], pieces['W1'], pieces['layers']
+    if not P.is_cuda:
+        raise _C.FairrecError('dyn_neg_mlp_select: ROCm device tensors only; there is no CPU fallback')
+    dev, D = P.device, item_table.dim
+    num, M = int(num), int(M)
+    if P.dim() != 2 or P.dtype != torch.float32 or P.stride(1) != 1 or (P.shape[0] > 1 and P.stride(0) < P.shape[1]):
+        raise ValueError('dyn_neg_mlp_select: P is an fp32 [n, n1] matrix with unit column stride')
+    n, n1 = P.shape
+    if W1.dim() != 2 or W1.dtype != torch.float32 or W1.device != dev or not W1.is_contiguous() or W1.shape[0] != n1 \
+            or W1.shape[1] <= D:
+        raise ValueError(f'dyn_neg_mlp_select: W1 is the contiguous fp32 [n1 = {n1}, D_user + {D}] first weight on the device of P')
+    if not 1 <= len(layers) <= _C.PAIR_MLP_MAX_LINEARS - 1:
+        raise ValueError(f'dyn_neg_mlp_select: {len(layers) + 1} linears, not in 2..{_C.PAIR_MLP_MAX_LINEARS}')
+    n_in = n1
+    for W, b in layers:
+        if tuple(W.shape[1:]) != (n_in,) or tuple(b.shape) != (W.shape[0],) or W.dtype != torch.float32 or b.dtype != torch.float32 \
+                or W.device != dev or b.device != dev or not W.is_contiguous() or not b.is_contiguous():
+            raise ValueError('dyn_neg_mlp_select: each layer is (W [n_out, n_in], bias [n_out]), contiguous fp32 on the device of P')
+        n_in = W.shape[0]
+    if num < 1 or M < 1 or cand.numel() != n * num * M:
+        raise ValueError(f'dyn_neg_mlp_select: {cand.numel()} candidates, not M * num * n = {M} * {num} * {n}')
+    cand = cand.to(dev, torch.int64).contiguous()
+    it, hy = item_table.c(), item_hyper.c()
+    a = _C.FrDynNegMlpArgs()
+    a.item_t, a.item_optim = ctypes.pointer(it), ctypes.pointer(hy)
+    a.P, a.W1_item = P.data_ptr(), W1.data_ptr() + 4 * (W1.shape[1] - D)
+    for l, (W, b) in enumerate(layers):
+        a.W[l], a.bias[l], a.n_out[l] = W.data_ptr(), b.data_ptr(), W.shape[0]
+    a.cand, a.ldp, a.ldw1, a.n = cand.data_ptr(), (P.stride(0) if n > 1 else n1), W1.shape[1], n
+    a.n1, a.n_linears, a.act, a.num, a.M = n1, len(layers) + 1, 1, num, M
+    lib, st = _C.lib(), _C.current_stream()
+    out = torch.empty(n * num, dtype=torch.int64, device=dev)
+    _C.check(lib.fr_dyn_neg_mlp_select(ctypes.byref(a), out.data_ptr(), _C.ptr(err_flag), st), "fr_dyn_neg_mlp_select")
+    if not want_scores:
+        return out
+    scores = torch.empty(n * num * M, dtype=torch.float32, device=dev)
+    _C.check(lib.fr_dyn_neg_mlp_scores(ctypes.byref(a), scores.data_ptr(), _C.ptr(err_flag), st), "fr_dyn_neg_mlp_scores")
+    return out, scores

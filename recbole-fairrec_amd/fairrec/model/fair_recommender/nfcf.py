@@ -17,7 +17,8 @@ from ... import _C
 from ...engine import GenericEngine
 from ...utils.enum_type import InputType
 from ..abstract_recommender import FairRecommender
-from ..layers import MLPLayers, full_sort_pair_mlp_pieces, full_sort_scorer_of
+from ..layers import (MLPLayers, dyn_neg_pair_mlp_pieces, dynamic_neg_scorer_of, full_sort_pair_mlp_pieces,
+                      full_sort_scorer_of)
 
 
 class _NfcfLoss(torch.autograd.Function):
@@ -170,6 +171,7 @@ class NFCF(FairRecommender):
         self.fair_weight = config['fair_weight']
         self.load_pretrain_path = config['load_pretrain_path']
         self.full_sort_scorer = full_sort_scorer_of(config)
+        self.dynamic_neg_scorer = dynamic_neg_scorer_of(config)
 
         self.user_embedding = nn.Embedding(self._table_rows(self.n_users), self.embedding_size)   # default N(0,1) init, as nfcf.py:38-39
         self.item_embedding = nn.Embedding(self._table_rows(self.n_items), self.embedding_size)
@@ -294,6 +296,29 @@ class NFCF(FairRecommender):
         return full_sort_pair_mlp_pieces(self.full_sort_scorer, self.mlp_layers, eng,
                                          lambda: eng.lookup("user_embedding.weight", interaction[self.USER_ID]),
                                          "item_embedding.weight", self.n_items)
+
+    def dyn_neg_select(self, interaction, cand, num, M):
+        """Dynamic negative sampling (TrainDataLoader._dynamic_negatives) with `dynamic_neg_scorer: split`: of the M
+        candidates of each negative slot the id the scorer rates highest, in one launch (fr_dyn_neg_mlp_select) -- the user rows
+        are looked up once and go through the user half of the first layer once, the candidates' rows are read in the kernel.
+        predict() is sigmoid(mlp_layers(cat(user row, item row))) and nothing else, which is what the kernel computes up to the
+        first layer's summation order; a model that drops out at this point (training mode), a subclass with a predict or
+        forward of its own, row-sharded tables and every scorer outside dyn_neg_pair_mlp_pieces answer None, and the loader goes
+        through predict().  None as well under the default `pairs`."""
+        cls, mlp = type(self), self.mlp_layers
+        if (self.dynamic_neg_scorer != 'split' or self.shard is not None or cls.predict is not NFCF.predict
+                or cls.forward is not NFCF.forward or cls._score_logits is not NFCF._score_logits
+                or (mlp.training and float(mlp.dropout) > 0.0)):
+            return None
+        from ...functional import dyn_neg_mlp_select
+        eng = self.hip_engine()
+        pieces = dyn_neg_pair_mlp_pieces(self.dynamic_neg_scorer, mlp, eng,
+                                         lambda: eng.lookup("user_embedding.weight", interaction[self.USER_ID]))
+        if pieces is None:
+            return None
+        with torch.no_grad():
+            return dyn_neg_mlp_select(pieces, eng._tables["item_embedding.weight"], eng._hyper("item_embedding.weight"), cand,
+                                      num, M, eng.err_flag)
 
     def state_dict(self, *args, **kwargs):
         if self._engine is not None:

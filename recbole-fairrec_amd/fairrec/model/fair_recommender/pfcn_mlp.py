@@ -2,7 +2,8 @@
 Tables are named `user_embedding` / `item_embedding`, the scorer `mlp_layer` (registered, trained by optimizer_filter)."""
 import torch
 
-from ..layers import MLPLayers, full_sort_pair_mlp_pieces, full_sort_scorer_of
+from ..layers import (MLPLayers, dyn_neg_pair_mlp_pieces, dynamic_neg_scorer_of, full_sort_pair_mlp_pieces,
+                      full_sort_scorer_of)
 from .pfcn_base import PFCNBase
 
 
@@ -13,6 +14,7 @@ class PFCN_MLP(PFCNBase):
 
     def _build_base_layers(self, config):
         self.full_sort_scorer = full_sort_scorer_of(config)
+        self.dynamic_neg_scorer = dynamic_neg_scorer_of(config)
         self.dropout = config['dropout']
         self.mlp_hidden_size_list = config['mlp_hidden_size_list']
         self.mlp_layer = MLPLayers([self.embedding_size * 2] + list(self.mlp_hidden_size_list) + [1], dropout=self.dropout)
@@ -25,6 +27,26 @@ class PFCN_MLP(PFCNBase):
 
     def _predict_score(self, ue, ie):
         return self.mlp_layer(ue, ie)
+
+    def dyn_neg_select(self, interaction, cand, num, M):
+        """Dynamic negative sampling with `dynamic_neg_scorer: split`: the pick of fr_dyn_neg_mlp_select over this scorer (see
+        NFCF.dyn_neg_select).  A filtered model keeps raising the base class's NotImplementedError; `pairs`, a scorer or engine
+        the kernel does not serve, a model in training mode with dropout and subclasses with towers of their own answer None."""
+        fused = super().dyn_neg_select(interaction, cand, num, M)      # (raises for a filtered model; None: the scorer is an MLP)
+        cls, mlp = type(self), self.mlp_layer
+        if (fused is not None or self.dynamic_neg_scorer != 'split' or self.shard is not None
+                or cls._predict_score is not PFCN_MLP._predict_score or cls._item_tower is not PFCNBase._item_tower
+                or cls._user_tower is not PFCNBase._user_tower or cls.predict is not PFCNBase.predict
+                or cls.forward is not PFCNBase.forward or (mlp.training and float(mlp.dropout) > 0.0)):
+            return fused
+        from ...functional import dyn_neg_mlp_select
+        eng = self.hip_engine()
+        pieces = dyn_neg_pair_mlp_pieces(self.dynamic_neg_scorer, mlp, eng,
+                                         lambda: eng.lookup(self._utab, interaction[self.USER_ID]))
+        if pieces is None:
+            return None
+        with torch.no_grad():
+            return dyn_neg_mlp_select(pieces, eng._tables[self._itab], eng._hyper(self._itab), cand, num, M, eng.err_flag)
 
     def full_sort_pair_mlp(self, interaction, sst_list=None, users_per_batch=None):
         """The pieces of predict() on every item for fr_pair_mlp_scores (`full_sort_scorer: split`), or None: the dense path

@@ -522,3 +522,28 @@ def full_sort_pair_mlp_pieces(scorer, mlp, engine, user_rows, item_table_name, n
         table = engine._tables[item_table_name]
         table.flush(engine._hyper(item_table_name))
         return pair_mlp_pieces(mlp, user_rows(), table.weight[:n_items])
+
+
+def dynamic_neg_scorer_of(config) -> str:
+    """The config key `dynamic_neg_scorer` of the MLP-scored models (NFCF, PFCN_MLP): how dynamic negative sampling rates its
+    candidates -- `pairs` (default: `predict` on the repeated interaction, the reference) or `split` (first layer split, the
+    rest per candidate and the pick in one kernel: fr_dyn_neg_mlp_select)."""
+    value = config['dynamic_neg_scorer']
+    name = 'pairs' if value is None else str(value).lower()
+    if name not in ('pairs', 'split'):
+        raise ValueError(f'dynamic_neg_scorer must be pairs or split, not [{value}]')
+    return name
+
+
+def dyn_neg_pair_mlp_pieces(scorer, mlp, engine, user_rows):
+    """What a model's `dyn_neg_select` hook hands to fr_dyn_neg_mlp_select for the scorer `mlp` over cat(user_rows[i], item
+    table row): P over the batch rows and the layer list, or None -- the loader then goes through `predict` -- when the key is
+    `pairs`, the scorer has BatchNorm, an activation other than ReLU, recorded dropout masks or a shape outside
+    fr_pair_mlp_supported, or the engine is not the single-device GenericEngine.  `user_rows`: a callable, so that nothing is
+    looked up for a None."""
+    from ..engine import GenericEngine
+    from ..functional import dyn_neg_mlp_pieces, pair_mlp_supported
+    if scorer != 'split' or type(engine) is not GenericEngine or not pair_mlp_supported(mlp):
+        return None
+    with torch.no_grad():
+        return dyn_neg_mlp_pieces(mlp, user_rows())
