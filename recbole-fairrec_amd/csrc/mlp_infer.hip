@@ -2,31 +2,24 @@
 // for rows that stay in LDS between the layers.  Inference only: nothing is kept for a backward pass, there is no workspace
 // and no atomic, and no argument but Y is written (the running statistics are read, never advanced).
 //
-// A workgroup of four waves owns a tile of 32 rows.  The layer's input lies in LDS as [32][S], S odd (the 32 lanes of one
-// MFMA operand read hit 32 banks); the layer's weights go through LDS 128 output columns x 32 input columns at a time,
-// fetched into registers one chunk ahead; wave w multiplies the 32 rows with output columns 32w..32w+31 of the chunk's
-// group on v_mfma_f32_32x32x2_f32.  A lane then holds 16 rows of ONE output column, so the column's bias and BatchNorm
-// constants are per-lane scalars.  A hidden layer writes its activations to the other LDS buffer; the last layer goes to Y.
+// A workgroup of four waves owns a tile of 32 rows and runs every layer on the tile machine mlp_tile.hpp describes, the
+// weights streamed; the column's bias and BatchNorm constants are per-lane scalars there.  A hidden layer writes its
+// activations to the other LDS buffer; the last layer goes to Y.  The layer loop is this kernel's own copy of the streamed
+// branch of mt_layer (mlp_tile.hpp): built on the template it computed the same bits from near-identical code, and measured
+// 1.2 % slower at a million rows.
 //
-// Row r's arithmetic (include/fairrec_hip.h states it as the contract) involves row r of the tile and the parameters only:
-// the MFMA's cells do not mix rows, rows at or beyond M are zeros in LDS and are never stored, and the chunking (32 input
-// columns, 128 output columns) is the same for every shape, so a row's bits do not depend on M, on its place in the tile
-// or on what the other rows hold.
+// Row r's arithmetic (include/fairrec_hip.h states it as the contract) involves row r of the tile and the parameters only
+// (mlp_tile.hpp has the argument): rows at or beyond M are zeros in LDS and are never stored.
 //
 // Several nets: each is evaluated in turn on the resident input tile (reloaded only after a net of three or more layers,
 // whose second layer overwrote it); the sum is carried in Y itself -- the thread that wrote a cell for net 0 is the one
 // that reads it back, adds and rewrites it for net 1, 2, ... -- and the last net's store divides.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mlp_tile.hpp"
 
 namespace fr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int MI_RT = 32;              // rows of a workgroup: one 32x32 MFMA tile
-constexpr int MI_CG = 128;             // output columns of a step: 32 per wave
-constexpr int MI_DK = 32;              // input columns of W staged in LDS at a time
-constexpr int MI_WST = MI_DK + 1;      // LDS row stride of the W image (odd: the lanes of one read hit 32 banks)
 constexpr int MI_LAYERS = FR_MLP_INFER_MAX_LAYERS * FR_MLP_INFER_MAX_NETS;
 
 struct MlpLayerK {
@@ -47,10 +40,6 @@ struct MlpK {
     MlpLayerK layer[MI_LAYERS];        // layer l of net n at [n * FR_MLP_INFER_MAX_LAYERS + l]
 };
 
-// LDS row stride of an activation tile of width n: odd, and with one column of zeros behind an odd width (the MFMA takes
-// the input columns two at a time)
-__host__ __device__ __forceinline__ int mi_stride(int n) { return (n + 1) | 1; }
-
 // The activations of this entry (the codes of fr_linear_fwd).  relu and leakyrelu keep a NaN; sigmoid is the IEEE quotient
 // over expf, tanh is tanhf (OCML).  The two library calls stay out of line: inlined into the 16 cells of the epilogue they
 // cost the kernel a workgroup of occupancy.
@@ -70,16 +59,16 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(MlpK a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
     const int li = lane & 31, h = lane >> 5;
     float* buf0 = mi_smem;                                  // [32][s0]: the input tile; outputs of layers 1, 3, 5
-    float* buf1 = buf0 + MI_RT * a.s0;                      // [32][s1]: outputs of layers 0, 2, 4, 6
-    float* Ws = buf1 + MI_RT * a.s1;                        // [128][MI_WST]
-    const long long row0 = (long long)blockIdx.x * MI_RT;
-    const int k_in = a.k_in, sx = mi_stride(k_in);
+    float* buf1 = buf0 + MT_RT * a.s0;                      // [32][s1]: outputs of layers 0, 2, 4, 6
+    float* Ws = buf1 + MT_RT * a.s1;                        // [128][MT_WST]
+    const long long row0 = (long long)blockIdx.x * MT_RT;
+    const int k_in = a.k_in, sx = mt_stride(k_in);
 
     for (int net = 0; net < a.n_nets; ++net) {
         const int L = a.n_layers[net];
         if (net == 0 || a.n_layers[net - 1] >= 3) {
             __syncthreads();          // the net before has read its last activations
-            for (int e = tid; e < MI_RT * sx; e += 256) {
+            for (int e = tid; e < MT_RT * sx; e += 256) {
                 const int r = e / sx, c = e - r * sx;
                 buf0[e] = (c < k_in && row0 + r < a.M) ? a.X[(size_t)(row0 + r) * k_in + c] : 0.f;
             }
@@ -91,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(MlpK a) {
             const bool last = l == L - 1, bn = lay.g != nullptr;
             const float* in = (l & 1) ? buf1 : buf0;
             float* out = (l & 1) ? buf0 : buf1;
-            const int s_in = mi_stride(n_in), s_out = mi_stride(n_out);
+            const int s_in = mt_stride(n_in), s_out = mt_stride(n_out);
             const float* W = lay.W;
             float pre[16];
             auto fetch = [&](int col0, int c0) {
@@ -102,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(MlpK a) {
                 }
             };
             fetch(0, 0);
-            for (int col0 = 0; col0 < n_out; col0 += MI_CG) {
+            for (int col0 = 0; col0 < n_out; col0 += MT_CG) {
                 const int col = col0 + wave * 32 + li;
                 const bool ok = col < n_out;
                 // the column's constants: bias, and BatchNorm as y = fmaf(z - mean, sc, beta), sc = gamma * (1 / sqrtf(var + eps))
@@ -116,27 +105,27 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(MlpK a) {
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                for (int c0 = 0; c0 < n_in; c0 += MI_DK) {
+                for (int c0 = 0; c0 < n_in; c0 += MT_DK) {
                     __syncthreads();      // the image is free; the layer's input is written
 #pragma unroll
                     for (int j = 0; j < 16; ++j) {
                         const int e = tid + 256 * j;
-                        Ws[(e >> 5) * MI_WST + (e & 31)] = pre[j];
+                        Ws[(e >> 5) * MT_WST + (e & 31)] = pre[j];
                     }
                     __syncthreads();
-                    if (c0 + MI_DK < n_in) fetch(col0, c0 + MI_DK);
-                    else if (col0 + MI_CG < n_out) fetch(col0 + MI_CG, 0);
+                    if (c0 + MT_DK < n_in) fetch(col0, c0 + MT_DK);
+                    else if (col0 + MT_CG < n_out) fetch(col0 + MT_CG, 0);
                     if (wave * 32 < n_out - col0) {      // (a wave whose 32 columns lie beyond the layer only stages)
-                        const int left = (n_in - c0 + 1) >> 1, steps = left < MI_DK / 2 ? left : MI_DK / 2;
+                        const int left = (n_in - c0 + 1) >> 1, steps = left < MT_DK / 2 ? left : MT_DK / 2;
                         const float* xp = in + li * s_in + c0 + h;
-                        const float* wp = Ws + (wave * 32 + li) * MI_WST + h;
+                        const float* wp = Ws + (wave * 32 + li) * MT_WST + h;
                         for (int s = 0; s < steps; ++s)
                             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xp[2 * s], wp[2 * s], acc, 0, 0, 0);
                     }
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int row = mt_row(r, h);
                     float y = __fadd_rn(acc[r], bias);
                     if (bn) y = fmaf(__fsub_rn(y, mu), sc, be);
                     y = act >= 3 ? mi_act_libm(y, act) : mi_act_cheap(y, act);
@@ -150,13 +139,13 @@ __global__ __launch_bounds__(256, 2) void mlp_infer_kernel(MlpK a) {
                     }
                 }
             }
-            if (!last && (n_out & 1) && tid < MI_RT) out[tid * s_out + n_out] = 0.f;
+            if (!last && (n_out & 1) && tid < MT_RT) out[tid * s_out + n_out] = 0.f;
             n_in = n_out;
         }
     }
 }
 
-static size_t mi_lds_bytes(int s0, int s1) { return ((size_t)MI_RT * (s0 + s1) + (size_t)MI_CG * MI_WST) * sizeof(float); }
+static size_t mi_lds_bytes(int s0, int s1) { return ((size_t)MT_RT * (s0 + s1) + (size_t)MT_CG * MT_WST) * sizeof(float); }
 
 }  // namespace fr
 
@@ -169,7 +158,7 @@ extern "C" int fr_mlp_infer(const fr_mlp_net* nets, int32_t n_nets, float out_di
                  FR_MLP_INFER_MAX_NETS);
     FR_CHECK_ARG(X, "fr_mlp_infer: X is null");
     FR_CHECK_ARG(Y, "fr_mlp_infer: Y is null");
-    FR_CHECK_ARG(M >= 0 && (M + MI_RT - 1) / MI_RT <= 0x7fffffffLL, "fr_mlp_infer: M %lld out of range", (long long)M);
+    FR_CHECK_ARG(M >= 0 && (M + MT_RT - 1) / MT_RT <= 0x7fffffffLL, "fr_mlp_infer: M %lld out of range", (long long)M);
     FR_CHECK_ARG(out_div != 0.f, "fr_mlp_infer: out_div is 0");
     MlpK p;
     p.X = X;
@@ -222,19 +211,14 @@ extern "C" int fr_mlp_infer(const fr_mlp_net* nets, int32_t n_nets, float out_di
         FR_CHECK_ARG(n_in == n_last, "fr_mlp_infer: nets[%d] ends in %d columns, nets[0] in %d", n, n_in, n_last);
     }
     if (M == 0) return FR_OK;
-    p.s0 = mi_stride(w0);
-    p.s1 = w1 ? mi_stride(w1) : 0;
+    p.s0 = mt_stride(w0);
+    p.s1 = w1 ? mt_stride(w1) : 0;
     const size_t ldsb = mi_lds_bytes(p.s0, p.s1);
-    static size_t have = 0;
-    if (ldsb > have) {
-        FR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_infer_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-        have = ldsb;
-    }
+    FR_CHECK_HIP(mt_allow_lds<mlp_infer_kernel>(ldsb));
     hipStream_t stream = (hipStream_t)stream_;
     ProfScope prof(K_MLP_INFER, stream);
     prof_work(K_MLP_INFER, flop);
-    FR_LAUNCH(prof, mlp_infer_kernel, dim3((unsigned)((M + MI_RT - 1) / MI_RT)), dim3(256), ldsb, stream, p);
+    FR_LAUNCH(prof, mlp_infer_kernel, dim3((unsigned)((M + MT_RT - 1) / MT_RT)), dim3(256), ldsb, stream, p);
     FR_CHECK_LAUNCH();
     return FR_OK;
 }

@@ -5,63 +5,53 @@
 // the narrow upper layers.  This kernel does that part and writes the dense masked [n_users, ld] matrix.
 //
 // A workgroup of four waves owns a tile of 32 users and a slice of the items, which it walks 32 items at a time.  A tile of
-// Q goes to LDS once and serves the 32 users in turn: h1 = act(P[u] + Q[tile]) is built in LDS as [32][S], S odd (the 32
-// lanes of one MFMA operand read hit 32 banks), and the upper layers run on v_mfma_f32_32x32x2_f32 exactly as the layer loop
-// of mlp_infer.hip does -- wave w takes output columns 32w..32w+31 of a group of 128, a lane holds 16 rows of ONE column --
-// with the 32 rows being the 32 items.  The upper layers' weights stay in LDS for the whole launch when they fit (the usual
-// scorer); otherwise they go through LDS 128 x 32 at a time, one chunk fetched ahead, per user and tile (correct, and slow:
-// the wide shapes are served, not tuned).  The one-output layer is the same MFMA chain with one live column; its 32
+// Q goes to LDS once and serves the 32 users in turn: h1 = act(P[u] + Q[tile]) is built in LDS as [32][S] and the upper
+// layers run on the tile machine mlp_tile.hpp describes, the 32 rows being the 32 items.  The upper layers' weights stay in
+// LDS for the whole launch when they fit (the usual scorer); otherwise they are streamed per user and tile (correct, and
+// slow: the wide shapes are served, not tuned).  The one-output layer is the same MFMA chain with one live column; its 32
 // pre-activations pass through LDS so that 32 lanes do the epilogue and one 128-byte store.  No atomics, no workspace.
 //
-// A cell's arithmetic (include/fairrec_hip.h states it as the contract) involves P[u], Q[i] and the parameters only: the
-// MFMA's cells do not mix rows, rows beyond the slice are zeros in LDS and are never stored, both weight paths run the same
-// ascending chain, and the cuts (32 users, 32 items, the slices) do not enter a chain.  Loads are unconditional on clamped
-// indices; what lies beyond a width or a count is replaced by zero after the load.
+// A cell's arithmetic (include/fairrec_hip.h states it as the contract) involves P[u], Q[i] and the parameters only: rows
+// beyond the slice are zeros in LDS and are never stored, and the cuts (32 users, 32 items, the slices) do not enter a chain
+// (mlp_tile.hpp has the rest of the argument).
+//
+// The staging of the resident images and the layer loop are this kernel's own copy of mt_stage_image / mt_upper_layers
+// (mlp_tile.hpp): built on them it computed the same bits and measured 0.8 % slower.  The copy still fetches the streamed
+// weights by a load on clamped indices with a select behind it, the slow form mlp_tile.hpp names; the streamed path is not
+// tuned, and changing the fetch moves the resident path's code as well.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mlp_tile.hpp"
 
 namespace fr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int PM_UT = 32;              // users of a workgroup
-constexpr int PM_IT = 32;              // items of a step: the rows of one 32x32 MFMA tile
-constexpr int PM_CG = 128;             // output columns of a step: 32 per wave
-constexpr int PM_DK = 32;              // input columns of W staged in LDS at a time (streamed weights)
-constexpr int PM_WST = PM_DK + 1;
+constexpr int PM_IT = MT_RT;           // items of a step: the rows of a tile
 constexpr int PM_PC = (FR_PAIR_MLP_MAX_WIDTH + 2 + 31) / 32;      // columns of a [32][S] tile per thread: S <= 257
-constexpr int PM_UP = FR_PAIR_MLP_MAX_LINEARS - 1;      // linears above the first
-constexpr size_t PM_LDS_MAX = 156 * 1024;
 constexpr int PM_WG_WANT = 1024;       // workgroups that fill the chip: the items are cut into slices until there are as many
 
 struct PairK {
     const float *P, *Q;
-    const float* W[PM_UP];
-    const float* bias[PM_UP];
+    const float* W[MT_UP];
+    const float* bias[MT_UP];
     float* scores;
     long long U, N, ld, slice_len;
     int n1, n_up, resident;
     int s0, s1;                        // row strides (floats) of the two activation buffers
-    int n_out[PM_UP];
-    int w_off[PM_UP];                  // resident weights: float offset of layer l's image [round32(n_out)][pm_stride(n_in)]
+    int n_out[MT_UP];
+    int w_off[MT_UP];                  // resident weights: float offset of layer l's image [round32(n_out)][mt_stride(n_in)]
 };
-
-// LDS row stride of a tile of width n: odd, with one column of zeros behind an odd width (the MFMA takes columns in pairs)
-__host__ __device__ __forceinline__ int pm_stride(int n) { return (n + 1) | 1; }
-
-// relu that keeps a NaN (fmaxf would return the other operand)
-__device__ __forceinline__ float pm_relu(float x) { return x < 0.f ? 0.f : x; }
 
 __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
     extern __shared__ __align__(16) float pm_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
     const int li = lane & 31, h = lane >> 5;
-    const int n1 = a.n1, sq = pm_stride(n1);
+    const int n1 = a.n1, sq = mt_stride(n1);
     float* Qs = pm_smem;                                    // [32][sq]: the item tile's rows of Q
     float* buf0 = Qs + PM_IT * sq;                          // [32][s0]: h1; outputs of upper layers 1, 3
     float* buf1 = buf0 + PM_IT * a.s0;                      // [32][s1]: outputs of upper layers 0, 2
     float* zs = buf1 + PM_IT * a.s1;                        // [32]: the last layer's pre-activations
-    float* Ws = zs + PM_IT;                                 // resident images, or the [128][PM_WST] staging image
+    float* Ws = zs + PM_IT;                                 // resident images, or the [128][MT_WST] staging image
     const long long u0 = (long long)blockIdx.x * PM_UT;
     const long long lo = (long long)blockIdx.y * a.slice_len;
     const long long hi = lo + a.slice_len < a.N ? lo + a.slice_len : a.N;
@@ -71,7 +61,7 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
     if (a.resident) {
         int n_in = n1;
         for (int l = 0; l < a.n_up; ++l) {
-            const int n_out = a.n_out[l], s = pm_stride(n_in), rows = (n_out + 31) & ~31;
+            const int n_out = a.n_out[l], s = mt_stride(n_in), rows = (n_out + 31) & ~31;
             float* img = Ws + a.w_off[l];
             const float* W = a.W[l];
             for (int r = r8; r < rows; r += 8) {
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = r8 + 8 * i;
-                        buf0[r * a.s0 + c] = c < n1 ? pm_relu(__fadd_rn(pv[j], Qs[r * sq + c])) : 0.f;
+                        buf0[r * a.s0 + c] = c < n1 ? mt_relu(__fadd_rn(pv[j], Qs[r * sq + c])) : 0.f;
                     }
                 }
             }
@@ -128,7 +118,7 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
                 const float* in = (l & 1) ? buf1 : buf0;
                 float* out = (l & 1) ? buf0 : buf1;
                 const int s_in = (l & 1) ? a.s1 : a.s0, s_out = (l & 1) ? a.s0 : a.s1;
-                const int sw = pm_stride(n_in);
+                const int sw = mt_stride(n_in);
                 const float* W = a.W[l];
                 __syncthreads();  // the layer's input is written
                 float pre[16];
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
                     }
                 };
                 if (!a.resident) fetch(0, 0);
-                for (int col0 = 0; col0 < n_out; col0 += PM_CG) {
+                for (int col0 = 0; col0 < n_out; col0 += MT_CG) {
                     const int col = col0 + wave * 32 + li;
                     const bool ok = col < n_out;
                     const float bias = a.bias[l][ok ? col : n_out - 1];
@@ -157,20 +147,20 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
                                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xp[2 * s], wp[2 * s], acc, 0, 0, 0);
                         }
                     } else {
-                        for (int c0 = 0; c0 < n_in; c0 += PM_DK) {
+                        for (int c0 = 0; c0 < n_in; c0 += MT_DK) {
                             __syncthreads();      // the image is free
 #pragma unroll
                             for (int j = 0; j < 16; ++j) {
                                 const int e = tid + 256 * j;
-                                Ws[(e >> 5) * PM_WST + (e & 31)] = pre[j];
+                                Ws[(e >> 5) * MT_WST + (e & 31)] = pre[j];
                             }
                             __syncthreads();
-                            if (c0 + PM_DK < n_in) fetch(col0, c0 + PM_DK);
-                            else if (col0 + PM_CG < n_out) fetch(col0 + PM_CG, 0);
+                            if (c0 + MT_DK < n_in) fetch(col0, c0 + MT_DK);
+                            else if (col0 + MT_CG < n_out) fetch(col0 + MT_CG, 0);
                             if (wave * 32 < n_out - col0) {
-                                const int left = (n_in - c0 + 1) >> 1, steps = left < PM_DK / 2 ? left : PM_DK / 2;
+                                const int left = (n_in - c0 + 1) >> 1, steps = left < MT_DK / 2 ? left : MT_DK / 2;
                                 const float* xp = in + li * s_in + c0 + h;
-                                const float* wp = Ws + (wave * 32 + li) * PM_WST + h;
+                                const float* wp = Ws + (wave * 32 + li) * MT_WST + h;
                                 for (int s = 0; s < steps; ++s)
                                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xp[2 * s], wp[2 * s], acc, 0, 0, 0);
                             }
@@ -179,10 +169,10 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
                     if (ok) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                            const int row = mt_row(r, h);
                             const float z = __fadd_rn(acc[r], bias);
                             if (last) zs[row] = z;          // (n_out is 1: lanes 0 and 32 of wave 0)
-                            else out[row * s_out + col] = pm_relu(z);
+                            else out[row * s_out + col] = mt_relu(z);
                         }
                     }
                 }
@@ -192,10 +182,7 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
             // (LDS operations of a wave execute in order: zs was written by this wave)
             if (wave == 0) {
                 __builtin_amdgcn_wave_barrier();
-                if (lane < PM_IT && i0 + lane < hi) {
-                    const float y = pm_relu(zs[lane]);
-                    a.scores[(size_t)(u0 + uu) * a.ld + i0 + lane] = __fdiv_rn(1.f, __fadd_rn(1.f, expf(-y)));
-                }
+                if (lane < PM_IT && i0 + lane < hi) a.scores[(size_t)(u0 + uu) * a.ld + i0 + lane] = mt_score(zs[lane]);
             }
         }
     }
@@ -250,8 +237,9 @@ extern "C" int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream_) {
     if ((rc = pm_shape_check(a->n1, a->n_linears, a->n_out, a->act, who))) return rc;
     FR_CHECK_ARG(a->P, "%s: P is null", who);
     FR_CHECK_ARG(a->Q, "%s: Q is null", who);
-    const int n_up = a->n_linears - 1;
-    for (int l = 0; l < n_up; ++l) FR_CHECK_ARG(a->W[l] && a->bias[l], "%s: W[%d] or bias[%d] is null", who, l, l);
+    PairK p;
+    MlpUpperPlan pl;
+    if ((rc = mt_plan_upper(who, a->n1, a->n_linears, a->W, a->bias, a->n_out, p, pl))) return rc;
     FR_CHECK_ARG(a->scores_out, "%s: scores_out is null", who);
     FR_CHECK_ARG(a->n_users >= 0 && (a->n_users + PM_UT - 1) / PM_UT <= 0x7fffffffLL, "%s: n_users %lld out of range", who,
                  (long long)a->n_users);
@@ -263,7 +251,6 @@ extern "C" int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream_) {
     }
     if (a->n_users == 0 || a->n_items == 0) return FR_OK;
 
-    PairK p;
     p.P = a->P;
     p.Q = a->Q;
     p.scores = a->scores_out;
@@ -271,35 +258,12 @@ extern "C" int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream_) {
     p.N = a->n_items;
     p.ld = a->ld;
     p.n1 = a->n1;
-    p.n_up = n_up;
-    int w0 = a->n1, w1 = 1, n_in = a->n1;
-    size_t w_floats = 0;
-    double flop = (double)a->n1;
-    for (int l = 0; l < PM_UP; ++l) {
-        p.W[l] = l < n_up ? a->W[l] : nullptr;
-        p.bias[l] = l < n_up ? a->bias[l] : nullptr;
-        p.n_out[l] = l < n_up ? a->n_out[l] : 0;
-        p.w_off[l] = (int)w_floats;
-        if (l >= n_up) continue;
-        w_floats += (size_t)((a->n_out[l] + 31) & ~31) * pm_stride(n_in);
-        if (l < n_up - 1) {
-            int& w = (l & 1) ? w0 : w1;
-            w = a->n_out[l] > w ? a->n_out[l] : w;
-        }
-        flop += 2.0 * n_in * a->n_out[l];
-        n_in = a->n_out[l];
-    }
-    p.s0 = pm_stride(w0);
-    p.s1 = pm_stride(w1);
-    const size_t fixed = ((size_t)PM_IT * (pm_stride(a->n1) + p.s0 + p.s1) + PM_IT) * sizeof(float);
-    p.resident = fixed + w_floats * sizeof(float) <= PM_LDS_MAX ? 1 : 0;
-    const size_t ldsb = fixed + (p.resident ? w_floats : (size_t)PM_CG * PM_WST) * sizeof(float);
-    static size_t have = 0;
-    if (ldsb > have) {
-        FR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pair_mlp_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-        have = ldsb;
-    }
+    p.s0 = mt_stride(pl.w0);
+    p.s1 = mt_stride(pl.w1);
+    const size_t fixed = ((size_t)PM_IT * (mt_stride(a->n1) + p.s0 + p.s1) + PM_IT) * sizeof(float);
+    p.resident = mt_resident(fixed, pl.w_floats);
+    const size_t ldsb = fixed + (p.resident ? pl.w_floats : (size_t)MT_CG * MT_WST) * sizeof(float);
+    FR_CHECK_HIP(mt_allow_lds<pair_mlp_kernel>(ldsb));
     const long long tiles = (a->n_users + PM_UT - 1) / PM_UT, steps = (a->n_items + PM_IT - 1) / PM_IT;
     long long S = PM_WG_WANT / tiles;
     S = S < 1 ? 1 : (S > steps ? steps : S);
@@ -308,7 +272,7 @@ extern "C" int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream_) {
     S = (a->n_items + p.slice_len - 1) / p.slice_len;
     hipStream_t stream = (hipStream_t)stream_;
     ProfScope prof(K_PAIR_MLP, stream);
-    prof_work(K_PAIR_MLP, flop * (double)a->n_users * (double)a->n_items);
+    prof_work(K_PAIR_MLP, pl.flop * (double)a->n_users * (double)a->n_items);
     FR_LAUNCH(prof, pair_mlp_kernel, dim3((unsigned)tiles, (unsigned)S), dim3(256), ldsb, stream, p);
     FR_CHECK_LAUNCH();
     if (a->mask_pad || a->hist_indptr) {

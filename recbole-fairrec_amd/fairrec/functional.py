@@ -642,6 +642,22 @@ def mlp_infer(nets, X, out_div=1.0):
     return Y
 
 
+def _check_upper_layers(who, layers, n_in, dev):
+    """The (W, bias) of the linears above a split first one of n_in outputs, as the fused scorers take them on device `dev`."""
+    if not 1 <= len(layers) <= _C.PAIR_MLP_MAX_LINEARS - 1:
+        raise ValueError(f'{who}: {len(layers) + 1} linears, not in 2..{_C.PAIR_MLP_MAX_LINEARS}')
+    for W, b in layers:
+        if tuple(W.shape[1:]) != (n_in,) or tuple(b.shape) != (W.shape[0],) or W.dtype != torch.float32 or b.dtype != torch.float32 \
+                or W.device != dev or b.device != dev or not W.is_contiguous() or not b.is_contiguous():
+            raise ValueError(f'{who}: each layer is (W [n_out, n_in], bias [n_out]), contiguous fp32 on the device of P')
+        n_in = W.shape[0]
+
+
+def _set_upper_layers(a, layers):
+    for l, (W, b) in enumerate(layers):
+        a.W[l], a.bias[l], a.n_out[l] = W.data_ptr(), b.data_ptr(), W.shape[0]
+
+
 # ---- all-item scores of an MLP scorer over cat(user, item), first layer split (csrc/pair_mlp.hip) ------------------------
 def pair_mlp_supported(mlp, n_first=None) -> bool:
     """Does fr_pair_mlp_scores serve this `MLPLayers` scorer?  ReLU, no BatchNorm, no recorded dropout masks, 2..6 linears with
@@ -693,17 +709,10 @@ def pair_mlp_scores(pieces, mask_pad=False, hist_indptr=None, hist_items=None, o
         raise _C.FairrecError('pair_mlp_scores: ROCm device tensors only; there is no CPU fallback')
     P, Q = P.contiguous(), Q.contiguous()
     U, N, dev = P.shape[0], Q.shape[0], P.device
-    if not 1 <= len(layers) <= _C.PAIR_MLP_MAX_LINEARS - 1:
-        raise ValueError(f'pair_mlp_scores: {len(layers) + 1} linears, not in 2..{_C.PAIR_MLP_MAX_LINEARS}')
     if P.dim() != 2 or Q.dim() != 2 or Q.shape[1] != P.shape[1] or P.dtype != torch.float32 or Q.dtype != torch.float32 \
             or Q.device != dev:
         raise ValueError('pair_mlp_scores: P [users, n1] and Q [items, n1], fp32, on one device')
-    n_in = P.shape[1]
-    for W, b in layers:
-        if tuple(W.shape[1:]) != (n_in,) or tuple(b.shape) != (W.shape[0],) or W.dtype != torch.float32 or b.dtype != torch.float32 \
-                or W.device != dev or b.device != dev or not W.is_contiguous() or not b.is_contiguous():
-            raise ValueError('pair_mlp_scores: each layer is (W [n_out, n_in], bias [n_out]), contiguous fp32 on the device of P')
-        n_in = W.shape[0]
+    _check_upper_layers('pair_mlp_scores', layers, P.shape[1], dev)
     if out is None:
         out = torch.empty((U, N), dtype=torch.float32, device=dev)
     if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != U or out.shape[1] < N or (N and out.stride(1) != 1):
@@ -719,8 +728,7 @@ def pair_mlp_scores(pieces, mask_pad=False, hist_indptr=None, hist_items=None, o
             raise ValueError('pair_mlp_scores: hist_indptr [users + 1]')
     a = _C.FrPairMlpArgs()
     a.P, a.Q = P.data_ptr(), Q.data_ptr()
-    for l, (W, b) in enumerate(layers):
-        a.W[l], a.bias[l], a.n_out[l] = W.data_ptr(), b.data_ptr(), W.shape[0]
+    _set_upper_layers(a, layers)
     a.hist_indptr, a.hist_items, a.scores_out = _C.ptr(ip), _C.ptr(hi), out.data_ptr()
     a.n_users, a.n_items, a.ld, a.hist_len = U, N, ld, hi.numel() if hi is not None else 0
     a.n1, a.n_linears, a.act, a.mask_pad, a.hist_sorted = P.shape[1], len(layers) + 1, int(act), int(bool(mask_pad)), 1
@@ -765,14 +773,7 @@ def dyn_neg_mlp_select(pieces, item_table, item_hyper, cand, num, M, err_flag, w
     if W1.dim() != 2 or W1.dtype != torch.float32 or W1.device != dev or not W1.is_contiguous() or W1.shape[0] != n1 \
             or W1.shape[1] <= D:
         raise ValueError(f'dyn_neg_mlp_select: W1 is the contiguous fp32 [n1 = {n1}, D_user + {D}] first weight on the device of P')
-    if not 1 <= len(layers) <= _C.PAIR_MLP_MAX_LINEARS - 1:
-        raise ValueError(f'dyn_neg_mlp_select: {len(layers) + 1} linears, not in 2..{_C.PAIR_MLP_MAX_LINEARS}')
-    n_in = n1
-    for W, b in layers:
-        if tuple(W.shape[1:]) != (n_in,) or tuple(b.shape) != (W.shape[0],) or W.dtype != torch.float32 or b.dtype != torch.float32 \
-                or W.device != dev or b.device != dev or not W.is_contiguous() or not b.is_contiguous():
-            raise ValueError('dyn_neg_mlp_select: each layer is (W [n_out, n_in], bias [n_out]), contiguous fp32 on the device of P')
-        n_in = W.shape[0]
+    _check_upper_layers('dyn_neg_mlp_select', layers, n1, dev)
     if num < 1 or M < 1 or cand.numel() != n * num * M:
         raise ValueError(f'dyn_neg_mlp_select: {cand.numel()} candidates, not M * num * n = {M} * {num} * {n}')
     cand = cand.to(dev, torch.int64).contiguous()
@@ -780,8 +781,7 @@ def dyn_neg_mlp_select(pieces, item_table, item_hyper, cand, num, M, err_flag, w
     a = _C.FrDynNegMlpArgs()
     a.item_t, a.item_optim = ctypes.pointer(it), ctypes.pointer(hy)
     a.P, a.W1_item = P.data_ptr(), W1.data_ptr() + 4 * (W1.shape[1] - D)
-    for l, (W, b) in enumerate(layers):
-        a.W[l], a.bias[l], a.n_out[l] = W.data_ptr(), b.data_ptr(), W.shape[0]
+    _set_upper_layers(a, layers)
     a.cand, a.ldp, a.ldw1, a.n = cand.data_ptr(), (P.stride(0) if n > 1 else n1), W1.shape[1], n
     a.n1, a.n_linears, a.act, a.num, a.M = n1, len(layers) + 1, 1, num, M
     lib, st = _C.lib(), _C.current_stream()

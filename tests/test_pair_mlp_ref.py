@@ -131,6 +131,33 @@ def test_wrapper_refuses_cpu_tensors():
         pair_mlp_scores({"P": torch.zeros(2, 4), "Q": torch.zeros(3, 4), "layers": [(torch.zeros(1, 4), torch.zeros(1))]})
 
 
+@pytest.mark.parametrize("who", ["pair_mlp_scores", "dyn_neg_mlp_select"])
+def test_upper_layer_checks_keep_each_caller_s_wording(who):
+    """The (W, bias) checks both wrappers share: the caller's name leads, the texts are the ones each wrapper raised itself."""
+    import torch
+
+    from fairrec import _C
+    from fairrec.functional import _check_upper_layers
+    cpu, ok = torch.device("cpu"), [(torch.zeros(3, 4), torch.zeros(3)), (torch.zeros(1, 3), torch.zeros(1))]
+    _check_upper_layers(who, ok, 4, cpu)
+    one = (torch.zeros(1, 1), torch.zeros(1))
+    _check_upper_layers(who, [one] * (_C.PAIR_MLP_MAX_LINEARS - 1), 1, cpu)
+    for layers in ([], [one] * _C.PAIR_MLP_MAX_LINEARS):
+        with pytest.raises(ValueError, match=f"^{who}: {len(layers) + 1} linears, not in 2..{_C.PAIR_MLP_MAX_LINEARS}$"):
+            _check_upper_layers(who, layers, 1, cpu)
+    bad = [[(torch.zeros(3, 5), torch.zeros(3))],                               # the width of the layer below
+           [ok[0], (torch.zeros(1, 4), torch.zeros(1))],                        # ... of the layer before
+           [(torch.zeros(3, 4), torch.zeros(2))],                               # bias length
+           [(torch.zeros(3, 4, dtype=torch.float64), torch.zeros(3))],
+           [(torch.zeros(3, 4), torch.zeros(3, dtype=torch.float64))],
+           [(torch.zeros(4, 3).t(), torch.zeros(3))],                           # not contiguous
+           [(torch.zeros(3, 4), torch.zeros(6)[::2])],
+           [(torch.zeros(3, 4, device="meta"), torch.zeros(3))]]                # another device
+    for layers in bad:
+        with pytest.raises(ValueError, match=f"^{who}: each layer is \\(W \\[n_out, n_in\\], bias \\[n_out\\]\\), contiguous fp32"):
+            _check_upper_layers(who, layers, 4, cpu)
+
+
 @pytest.mark.parametrize("model", ["NFCF", "PFCN_MLP"])
 def test_full_sort_scorer_key(model):
     from fairrec.model.layers import full_sort_scorer_of
