@@ -1124,6 +1124,39 @@ FR_API size_t fr_recommend_topk_workspace_bytes(const fr_rec_args* a);
 FR_API int fr_recommend_topk(const fr_rec_args* a, float* val_out, int64_t* idx_out, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * Full-sort evaluation without the matrix (`full_sort_eval: fused`).  Both entries read an fr_rec_args as fr_recommend_topk
+ * does and ignore its k, slices and scores_out; they speak of the matrix scores_out WOULD hold for the same arguments.
+ *
+ * fr_recommend_cells: score_out[c] = the bits of scores_out[cell_user[c], cell_item[c]], c < n_cells -- -inf for the pad item
+ *   (mask_pad) and for a cell of the user's history.  The dot is the one ascending-column fp32 fmaf chain from 0 of
+ *   fr_recommend_topk, run on the same instruction (v_mfma_f32_32x32x2_f32 over the cells' 32 user rows and 32 item rows, of
+ *   which the diagonal is kept), then the bias adds, the epilogue and the mask in that entry's order.  A cell_user outside
+ *   [0, n_users) or a cell_item outside [0, n_items) sets FR_DEV_ERR_INDEX_RANGE in *err_flag; its score_out is a quiet NaN.
+ *
+ * fr_recommend_meanrank: out int64 [n_users, 3] = what fr_eval_meanrank_segments(items = NULL, seg_start[u] = u * n_items)
+ *   returns on that matrix for the same pos_keys (SORTED keys user * n_items + item, int64 [n_pos]): { 2 * pos_rank_sum,
+ *   user_len, pos_len }.  As there, a key listed twice is one positive, a key outside the matrix is none, a positive that is a
+ *   masked cell scores -inf (every live cell ranks above it), and a user without positives gets { 0, user_len, 0 }.  A NaN cell
+ *   is no live cell; a NaN positive counts in pos_len and adds 1 to the first column, as it does there.
+ *   The tiling, staging and MFMA chain are fr_recommend_topk's, so a counted cell has the ranked cell's bits; the positives'
+ *   own scores (fr_recommend_cells' kernel) are the thresholds the live cells are counted against.  Integer atomics only: the
+ *   same output on every call.  Nothing of size n_users * n_items is stored: ws holds 4 bytes per key,
+ *   fr_recommend_meanrank_workspace_bytes(a, n_pos) (0 for arguments that are refused).  The items are cut into slices by the
+ *   shape (or FAIRREC_REC_SLICES); a tile of 32 users whose longest list has more than 128 positives goes over its slice once
+ *   per 128 of them.  err_flag is not written (no key is an error).
+ *
+ * FR_EINVAL before anything is launched or written: a null pointer (the struct, X, W, an output, err_flag, the lists of a
+ * positive count, a short or misaligned workspace), dim outside 1..256, n_users outside 0..2^31-1, n_items outside 1..2^31-1,
+ * an unknown epilogue, epilogue 1 without a positive scale, a history with hist_sorted != 1, a negative count, cells with
+ * n_users == 0.  n_cells == 0 and n_pos == 0 are FR_OK; with n_pos == 0, out still gets user_len.
+ */
+FR_API int fr_recommend_cells(const fr_rec_args* a, const int64_t* cell_user, const int64_t* cell_item, int64_t n_cells,
+                              float* score_out, uint32_t* err_flag, void* stream);
+FR_API size_t fr_recommend_meanrank_workspace_bytes(const fr_rec_args* a, int64_t n_pos);
+FR_API int fr_recommend_meanrank(const fr_rec_args* a, const int64_t* pos_keys, int64_t n_pos, int64_t* out, void* ws,
+                                 size_t ws_bytes, uint32_t* err_flag, void* stream);
+
+/*
  * fr_mlp_infer: a whole MLP in one launch, for inference.  Each layer is Linear, then (optionally) BatchNorm1d on its RUNNING
  * statistics, then the activation (the codes of fr_linear_fwd: 0 none, 1 relu, 2 leakyrelu 0.01, 3 sigmoid, 4 tanh);
  *     Y[M, n_out_last] = (net_0(X) + net_1(X) + ...  in list order, fp32 adds from the first) / out_div      (IEEE division,

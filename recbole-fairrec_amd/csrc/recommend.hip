@@ -526,6 +526,428 @@ static int rec_cap(int D, int k) {
     return cap < lo ? lo : cap;
 }
 
+// ---- full-sort evaluation without the matrix: single cells of it, and the rank sums of GAUC ------------------------------
+constexpr int MR_C = 128;                    // thresholds of a user in LDS per pass over its slice
+constexpr uint32_t MR_SKIP = 0xffffffffu;    // a key that is no positive (listed twice, or outside the matrix): above every cell
+constexpr uint32_t MR_NAN = 0xfffffffeu;     // a NaN positive: above every cell as well, and counted
+
+struct CellK {
+    const float* X;
+    const float* W;
+    const float* ub;
+    const float* ib;
+    const long long* indptr;
+    const long long* hist;
+    const long long* cu;      // the cells: (cu[c], ci[c]) -> score[c] ...
+    const long long* ci;
+    const long long* keys;    // ... or the sorted keys user * N + item -> tb[c] = the score's image in the order (MR_SKIP, MR_NAN)
+    float* score;
+    uint32_t* tb;
+    uint32_t* err;
+    long long U, N, hist_len, n;
+    int D, epi, mask_pad;
+    float bias0, scale;
+};
+
+// A wave scores 32 cells: the MFMA chain of recommend_kernel over the cells' 32 user rows and 32 item rows, read from memory
+// as they lie (column 2s + (l >> 5) of step s, zero beyond D: the same ceil(D / 2) steps), of which cell c is the diagonal
+// element (c, c) -- register (c & 3) + 4 (c >> 3) of the lane c + 32 ((c >> 2) & 1).  The bias adds, the exact epilogue and the
+// mask follow as recommend_kernel and recommend_mask_kernel apply them.
+__global__ __launch_bounds__(256) void recommend_cells_kernel(CellK a) {
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const long long c = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 + li;
+    const bool in = c < a.n;
+    long long u = 0, it = 0;
+    bool skip = false;
+    if (in) {
+        if (a.keys) {
+            const long long key = a.keys[c];
+            skip = key < 0 || key >= a.U * a.N || (c > 0 && a.keys[c - 1] == key);
+            if (!skip) {
+                u = key / a.N;
+                it = key - u * a.N;
+            }
+        } else {
+            u = a.cu[c];
+            it = a.ci[c];
+            if (u < 0 || u >= a.U || it < 0 || it >= a.N) {
+                skip = true;
+                u = it = 0;      // (its loads stay on row 0)
+                if (h == 0) atomicOr(a.err, FR_DEV_ERR_INDEX_RANGE);
+            }
+        }
+    }
+    const float* xr = a.X + (size_t)u * a.D;
+    const float* wr = a.W + (size_t)it * a.D;
+    const int D = a.D, steps = (D + 1) >> 1;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int s0 = 0; s0 < steps; s0 += 8) {
+        float xa[8], wb[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int col = 2 * (s0 + j) + h;
+            xa[j] = col < D ? xr[col] : 0.f;
+            wb[j] = col < D ? wr[col] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (s0 + j < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[j], wb[j], acc, 0, 0, 0);
+    }
+    const int rsel = (li & 3) + 4 * (li >> 3);
+    float x = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (r == rsel) x = acc[r];
+    if (!in || h != ((li >> 2) & 1)) return;
+    if (skip) {
+        if (a.keys) a.tb[c] = MR_SKIP;
+        else a.score[c] = __uint_as_float(0x7fc00000u);
+        return;
+    }
+    if (a.ub) x = x + a.ub[u];
+    if (a.ib) x = x + a.ib[it];
+    x = x + a.bias0;
+    x = epilogue_exact(x, a.epi, a.scale);
+    bool masked = a.mask_pad && it == 0;
+    if (!masked && a.indptr) {
+        long long p = a.indptr[u], q = a.indptr[u + 1];
+        p = p < 0 ? 0 : p;
+        q = q > a.hist_len ? a.hist_len : q;
+        while (p < q) {
+            const long long m = (p + q) >> 1;
+            const long long v = a.hist[m];
+            if (v == it) {
+                masked = true;
+                break;
+            }
+            if (v < it) p = m + 1;
+            else q = m;
+        }
+    }
+    if (masked) x = -INFINITY;
+    if (a.keys) a.tb[c] = x != x ? MR_NAN : order_bits(x);
+    else a.score[c] = x;
+}
+
+struct MrK {
+    const float* X;
+    const float* W;
+    const float* ub;
+    const float* ib;
+    const long long* indptr;
+    const long long* hist;
+    const long long* keys;
+    const uint32_t* tb;
+    u64* out;
+    long long U, N, hist_len, slice_len, n_pos;
+    int D, epi, mask_pad;
+    float bias0, scale;
+};
+
+// out[u] = { positives, 0, positives } of user u (a thread each): the `+ 1` of every positive's rank, and pos_len
+__global__ __launch_bounds__(256) void recommend_meanrank_init_kernel(const long long* __restrict__ keys, const uint32_t* __restrict__ tb,
+                                                                      long long n_pos, long long U, long long N, u64* __restrict__ out) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (u >= U) return;
+    long long b[2];
+    for (int e = 0; e < 2; ++e) {
+        long long p = 0, q = n_pos;
+        while (p < q) {
+            const long long m = (p + q) >> 1;
+            if (keys[m] < (u + e) * N) p = m + 1;
+            else q = m;
+        }
+        b[e] = p;
+    }
+    u64 n = 0;
+    for (long long p = b[0]; p < b[1]; ++p) n += tb[p] != MR_SKIP ? 1 : 0;
+    out[u * 3 + 0] = n;
+    out[u * 3 + 1] = 0;
+    out[u * 3 + 2] = n;
+}
+
+// Workgroup (tile of 32 users, slice of the items), tiled, staged and multiplied as recommend_kernel, so that a cell counted here
+// has the bits of the cell ranked there.  Every cell gets the exact epilogue and the mask: the pad item, and a bit per (user,
+// item of the step) set from the users' ascending histories, which 8 threads per user walk along with the steps (the next 8
+// entries of a user wait in registers; a step without history loads nothing).  A live cell (not masked, above -inf) adds 1 to
+// user_len.  The scores of the user's positives (recommend_cells_kernel's images in the order) are its thresholds, up to MR_C
+// of them sorted in LDS: a live cell at or above the lowest one is staged, and adds lb + ub to the user's sum, lb (ub) = the
+// thresholds below (not above) it -- 2 for every positive it beats and 1 for every positive it ties with, which is what
+// 2 * pos_rank_sum counts beyond the positives themselves.  A tile whose longest list has more than MR_C thresholds goes over
+// its slice once per MR_C of them.  Integer LDS and global atomics only: the same result on every call.
+__global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+    const int li = lane & 31, h = lane >> 5;
+    const int D = a.D, Dx = (D + 1) | 1, epi = a.epi;
+    u64* sum = reinterpret_cast<u64*>(smem);                      // [32]
+    long long* hp = reinterpret_cast<long long*>(sum + REC_UT);   // [32], [32]: the users' history inside the slice
+    long long* hq = hp + REC_UT;
+    long long* pp = hq + REC_UT;                                  // [32], [32]: the users' keys
+    long long* pq = pp + REC_UT;
+    uint32_t* thr = reinterpret_cast<uint32_t*>(pq + REC_UT);     // [32][MR_C] ascending
+    uint32_t* low = thr + REC_UT * MR_C;                          // [32] the lowest threshold of the pass
+    int* nt = reinterpret_cast<int*>(low + REC_UT);               // [32] thresholds of the pass
+    int* ulen = nt + REC_UT;                                      // [32]
+    uint32_t* mbits = reinterpret_cast<uint32_t*>(ulen + REC_UT); // [32][4] history bits of the step's 128 items
+    float* ubs = reinterpret_cast<float*>(mbits + REC_UT * 4);    // [32]
+    float* Xs = ubs + REC_UT;                                     // [32][Dx]
+    float* Ws = Xs + REC_UT * Dx;                                 // [128][REC_WST]
+    uint32_t* stg_x = reinterpret_cast<uint32_t*>(Ws + REC_IB * REC_WST) + wave * REC_STG;      // [4][REC_STG] images ...
+    unsigned short* stg_c = reinterpret_cast<unsigned short*>(Ws + REC_IB * REC_WST + 4 * REC_STG) + wave * REC_STG;   // ... users
+    const long long u0 = (long long)blockIdx.x * REC_UT;
+    const long long lo = (long long)blockIdx.y * a.slice_len;
+    const long long hi = lo + a.slice_len < a.N ? lo + a.slice_len : a.N;
+    const bool hist = a.indptr != nullptr;
+
+    for (int e = tid; e < REC_UT * Dx; e += 256) {
+        const int u = e / Dx, c = e - u * Dx;
+        Xs[e] = (c < D && u0 + u < a.U) ? a.X[(size_t)(u0 + u) * D + c] : 0.f;
+    }
+    if (tid < REC_UT) {
+        sum[tid] = 0ull;
+        ulen[tid] = 0;
+        ubs[tid] = (a.ub && u0 + tid < a.U) ? a.ub[u0 + tid] : 0.f;
+    }
+    if (tid < 2 * REC_UT) {      // lower bounds of the slice's two ends in each user's history
+        const int u = tid >> 1;
+        const long long bound = (tid & 1) ? hi : lo;
+        long long p = 0, q = 0;
+        if (hist && u0 + u < a.U) {
+            p = a.indptr[u0 + u];
+            q = a.indptr[u0 + u + 1];
+            p = p < 0 ? 0 : p;
+            q = q > a.hist_len ? a.hist_len : q;
+            while (p < q) {
+                const long long m = (p + q) >> 1;
+                if (a.hist[m] < bound) p = m + 1;
+                else q = m;
+            }
+        }
+        ((tid & 1) ? hq : hp)[u] = p;
+    } else if (tid < 4 * REC_UT) {      // the users' ranges of the sorted keys
+        const int u = (tid - 2 * REC_UT) >> 1;
+        long long p = 0, q = 0;
+        if (u0 + u < a.U) {
+            const long long bound = (u0 + u + (tid & 1)) * a.N;
+            q = a.n_pos;
+            while (p < q) {
+                const long long m = (p + q) >> 1;
+                if (a.keys[m] < bound) p = m + 1;
+                else q = m;
+            }
+        }
+        ((tid & 1) ? pq : pp)[u] = p;
+    }
+    __syncthreads();
+    long long longest = 0;
+    for (int u = 0; u < REC_UT; ++u) longest = pq[u] - pp[u] > longest ? pq[u] - pp[u] : longest;
+    const long long npass = longest > MR_C ? (longest + MR_C - 1) / MR_C : 1;
+    const int gu = tid >> 3, sub = tid & 7;      // history walk: 8 threads per user
+    const long long hqg = hq[gu];
+
+    float pre[16];
+    auto fetch = [&](long long i0, int c0) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int e = tid + 256 * j, item = e >> 5, col = e & 31;
+            const long long it = i0 + item;
+            pre[j] = (it < hi && c0 + col < D) ? a.W[(size_t)it * D + c0 + col] : 0.f;
+        }
+    };
+    for (long long pass = 0; pass < npass; ++pass) {
+        for (int uu = wave; uu < REC_UT; uu += 4) {      // a wave sorts a user's thresholds of this pass by counting
+            const long long base = pp[uu] + pass * MR_C, left = pq[uu] - base;
+            const int n = left < 0 ? 0 : (left > MR_C ? MR_C : (int)left);
+            uint32_t* t = thr + uu * MR_C;
+            uint32_t mine[MR_C / 64];
+            int rank[MR_C / 64];
+#pragma unroll
+            for (int q = 0; q < MR_C / 64; ++q) {
+                const int i = lane + 64 * q;
+                mine[q] = i < n ? a.tb[base + i] : MR_SKIP;
+                t[i] = mine[q];
+                rank[q] = 0;
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (int j = 0; j < n; ++j) {      // (LDS operations of a wave execute in order)
+                const uint32_t v = t[j];
+#pragma unroll
+                for (int q = 0; q < MR_C / 64; ++q) rank[q] += (v < mine[q] || (v == mine[q] && j < lane + 64 * q)) ? 1 : 0;
+            }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int q = 0; q < MR_C / 64; ++q) {
+                if (lane + 64 * q < n) {
+                    t[rank[q]] = mine[q];
+                    if (rank[q] == 0) low[uu] = mine[q];
+                }
+            }
+            if (lane == 0) {
+                nt[uu] = n;
+                if (n == 0) low[uu] = MR_SKIP;
+            }
+        }
+        long long cur = hp[gu];
+        long long hv = (hist && cur + sub < hqg) ? a.hist[cur + sub] : 0x7fffffffffffffffLL;
+        if (lo < hi) fetch(lo, 0);
+        __syncthreads();
+        for (long long i0 = lo; i0 < hi; i0 += REC_IB) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            const long long item = i0 + wave * 32 + li;
+            const bool ok = item < hi;
+            const float ibv = (a.ib && ok) ? a.ib[item] : 0.f;
+            for (int c0 = 0; c0 < D; c0 += REC_DK) {
+                __syncthreads();      // the image is free, and so are the history bits of the step before
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const int e = tid + 256 * j;
+                    Ws[(e >> 5) * REC_WST + (e & 31)] = pre[j];
+                }
+                if (hist && c0 == 0 && tid < REC_UT * 4) mbits[tid] = 0u;
+                __syncthreads();
+                if (c0 + REC_DK < D) fetch(i0, c0 + REC_DK);
+                else if (i0 + REC_IB < hi) fetch(i0 + REC_IB, 0);
+                if (hist && c0 == 0) {      // the users' history entries inside [i0, i0 + 128): ascending, so a prefix of the 8 waiting
+                    const long long end = i0 + REC_IB;
+                    for (;;) {
+                        const bool hit = hv < end;
+                        const u64 m = __ballot(hit);
+                        if (!m) break;
+                        if (hit && hv >= i0) atomicOr(&mbits[gu * 4 + (int)((hv - i0) >> 5)], 1u << (int)((hv - i0) & 31));
+                        const int nh = __popcll((m >> (lane & 56)) & 0xffull);
+                        if (nh) {
+                            cur += nh;
+                            hv = cur + sub < hqg ? a.hist[cur + sub] : 0x7fffffffffffffffLL;
+                        }
+                    }
+                }
+                const int left = (D - c0 + 1) >> 1, steps = left < REC_DK / 2 ? left : REC_DK / 2;
+                const float* xp = Xs + li * Dx + c0 + h;
+                const float* wp = Ws + (wave * 32 + li) * REC_WST + h;
+                for (int s = 0; s < steps; ++s)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xp[2 * s], wp[2 * s], acc, 0, 0, 0);
+            }
+            if (hist) __syncthreads();      // the history bits are set
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                int nst = 0;      // staged cells of this wave (uniform)
+#pragma unroll
+                for (int rr = 0; rr < 8; ++rr) {
+                    const int r = half * 8 + rr;
+                    const int ur = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    float x = acc[r];
+                    if (a.ub) x = x + ubs[ur];
+                    if (a.ib) x = x + ibv;
+                    x = x + a.bias0;
+                    x = epilogue_exact(x, epi, a.scale);
+                    bool alive = ok && u0 + ur < a.U && x > -INFINITY;      // (a NaN is no live cell)
+                    if (a.mask_pad && item == 0) alive = false;
+                    if (hist && ((mbits[ur * 4 + wave] >> li) & 1u)) alive = false;
+                    if (pass == 0) {      // user_len: the live cells of the two users of this register
+                        const u64 am = __ballot(alive);
+                        const int na = __popc((uint32_t)(h ? am >> 32 : am));
+                        if (li == 0 && na) atomicAdd(&ulen[ur], na);
+                    }
+                    const uint32_t ob = order_bits(x);
+                    const bool cand = alive && ob >= low[ur];
+                    const u64 m = __ballot(cand);
+                    if (m) {
+                        if (cand) {
+                            const int pos = nst + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+                            stg_x[pos] = ob;
+                            stg_c[pos] = (unsigned short)ur;
+                        }
+                        nst += __popcll(m);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                for (int e = lane; e < nst; e += 64) {      // (LDS operations of a wave execute in order: the staged cells are there)
+                    const int ur = stg_c[e];
+                    const uint32_t ob = stg_x[e];
+                    const uint32_t* t = thr + ur * MR_C;
+                    const int n = nt[ur];
+                    int p = 0, q = n;
+                    while (p < q) {
+                        const int m = (p + q) >> 1;
+                        if (t[m] < ob) p = m + 1;
+                        else q = m;
+                    }
+                    const int lb = p;
+                    q = n;
+                    while (p < q) {
+                        const int m = (p + q) >> 1;
+                        if (t[m] <= ob) p = m + 1;
+                        else q = m;
+                    }
+                    atomicAdd(&sum[ur], (u64)(lb + p));
+                }
+            }
+        }
+        __syncthreads();      // every staged cell is counted before the next pass's thresholds come in
+    }
+    if (tid < REC_UT && u0 + tid < a.U) {
+        atomicAdd(&a.out[(u0 + tid) * 3 + 0], sum[tid]);
+        atomicAdd(&a.out[(u0 + tid) * 3 + 1], (u64)ulen[tid]);
+    }
+}
+
+static size_t mr_lds_bytes(int D) {
+    const int Dx = (D + 1) | 1;
+    return (size_t)REC_UT * (5 * 8 + MR_C * 4 + 4 + 4 + 4 + 16 + 4) + (size_t)REC_UT * Dx * 4 + (size_t)REC_IB * REC_WST * 4 +
+           4 * REC_STG * (4 + 2);
+}
+
+// The arguments fr_recommend_cells / fr_recommend_meanrank read of an fr_rec_args (k, slices and scores_out are not theirs)
+static int eval_check(const fr_rec_args* a, const char* who) {
+    FR_CHECK_ARG(a, "%s: null argument struct", who);
+    FR_CHECK_ARG(a->X && a->W, "%s: null X or W", who);
+    FR_CHECK_ARG(a->n_users >= 0 && a->n_users <= 0x7fffffffLL && a->n_items >= 1 && a->n_items <= 0x7fffffffLL,
+                 "%s: bad n_users / n_items", who);
+    FR_CHECK_ARG(a->dim >= 1 && a->dim <= 256, "%s: dim %d not in 1..256", who, a->dim);
+    FR_CHECK_ARG(a->epilogue >= 0 && a->epilogue <= 2, "%s: unknown epilogue %d", who, a->epilogue);
+    FR_CHECK_ARG(a->epilogue != 1 || a->scale > 0.f, "%s: epilogue 1 needs scale > 0", who);
+    if (a->hist_indptr) {
+        FR_CHECK_ARG(a->hist_len >= 0 && (a->hist_items || a->hist_len == 0), "%s: history CSR without items", who);
+        FR_CHECK_ARG(a->hist_sorted == 1, "%s: the history CSR must be ascending within each user (hist_sorted = 1)", who);
+    }
+    return FR_OK;
+}
+
+static int launch_cells(const fr_rec_args* a, const long long* cu, const long long* ci, const long long* keys, long long n,
+                        float* score, uint32_t* tb, uint32_t* err, hipStream_t stream) {
+    CellK p;
+    p.X = a->X;
+    p.W = a->W;
+    p.ub = a->user_bias;
+    p.ib = a->item_bias;
+    p.indptr = reinterpret_cast<const long long*>(a->hist_indptr);
+    p.hist = reinterpret_cast<const long long*>(a->hist_items);
+    p.cu = cu;
+    p.ci = ci;
+    p.keys = keys;
+    p.score = score;
+    p.tb = tb;
+    p.err = err;
+    p.U = a->n_users;
+    p.N = a->n_items;
+    p.hist_len = a->hist_indptr ? a->hist_len : 0;
+    p.n = n;
+    p.D = a->dim;
+    p.epi = a->epilogue;
+    p.mask_pad = a->mask_pad ? 1 : 0;
+    p.bias0 = a->bias0;
+    p.scale = a->scale;
+    ProfScope prof(K_REC_CELLS, stream);
+    FR_LAUNCH(prof, recommend_cells_kernel, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, stream, p);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
 }  // namespace fr
 
 using namespace fr;
@@ -594,6 +1016,78 @@ extern "C" int fr_recommend_topk(const fr_rec_args* a, float* val_out, int64_t* 
     }
     FR_LAUNCH(prof2, topk_merge_kernel, dim3((unsigned)a->n_users), dim3(256), (size_t)S * a->k * sizeof(u64), stream,
               (const u64*)p.ws, S, (int)a->k, (const float*)nullptr, 0LL, val_out, reinterpret_cast<long long*>(idx_out));
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+extern "C" int fr_recommend_cells(const fr_rec_args* a, const int64_t* cell_user, const int64_t* cell_item, int64_t n_cells,
+                                  float* score_out, uint32_t* err_flag, void* stream_) {
+    int rc;
+    if ((rc = eval_check(a, "fr_recommend_cells"))) return rc;
+    FR_CHECK_ARG(n_cells >= 0 && n_cells <= (0x7fffffffLL << 7), "fr_recommend_cells: n_cells out of range");
+    FR_CHECK_ARG(err_flag && (n_cells == 0 || (cell_user && cell_item && score_out)), "fr_recommend_cells: null pointer");
+    FR_CHECK_ARG(n_cells == 0 || a->n_users >= 1, "fr_recommend_cells: cells of an empty set of users");
+    if (n_cells == 0) return FR_OK;
+    return launch_cells(a, reinterpret_cast<const long long*>(cell_user), reinterpret_cast<const long long*>(cell_item), nullptr,
+                        n_cells, score_out, nullptr, err_flag, (hipStream_t)stream_);
+}
+
+extern "C" size_t fr_recommend_meanrank_workspace_bytes(const fr_rec_args* a, int64_t n_pos) {
+    if (eval_check(a, "fr_recommend_meanrank_workspace_bytes") || n_pos < 0) return 0;
+    return (size_t)n_pos * sizeof(uint32_t);
+}
+
+extern "C" int fr_recommend_meanrank(const fr_rec_args* a, const int64_t* pos_keys, int64_t n_pos, int64_t* out, void* ws,
+                                     size_t ws_bytes, uint32_t* err_flag, void* stream_) {
+    int rc;
+    if ((rc = eval_check(a, "fr_recommend_meanrank"))) return rc;
+    FR_CHECK_ARG(n_pos >= 0 && n_pos <= (0x7fffffffLL << 7), "fr_recommend_meanrank: n_pos out of range");
+    FR_CHECK_ARG(out && err_flag && (n_pos == 0 || pos_keys), "fr_recommend_meanrank: null pointer");
+    const size_t need = (size_t)n_pos * sizeof(uint32_t);
+    FR_CHECK_ARG(need == 0 || (ws && ws_bytes >= need && ((uintptr_t)ws & 3) == 0),
+                 "fr_recommend_meanrank: workspace too small or misaligned (%zu < %zu bytes)", ws_bytes, need);
+    const long long tiles = (a->n_users + REC_UT - 1) / REC_UT;
+    long long len;
+    const int S = plan_slices(a->n_items, 1, tiles < 1 ? 1 : tiles, 2 * 256, 1024, REC_IB, 0, &len);
+    FR_CHECK_ARG(S >= 1, "fr_recommend_meanrank: FAIRREC_REC_SLICES out of range (at most %d)", REC_SLICES_MAX);
+    if (a->n_users == 0) return FR_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    uint32_t* tb = static_cast<uint32_t*>(ws);
+    const long long* keys = reinterpret_cast<const long long*>(pos_keys);
+    if (n_pos > 0 && (rc = launch_cells(a, nullptr, nullptr, keys, n_pos, nullptr, tb, err_flag, stream))) return rc;
+    MrK p;
+    p.X = a->X;
+    p.W = a->W;
+    p.ub = a->user_bias;
+    p.ib = a->item_bias;
+    p.indptr = reinterpret_cast<const long long*>(a->hist_indptr);
+    p.hist = reinterpret_cast<const long long*>(a->hist_items);
+    p.keys = keys;
+    p.tb = tb;
+    p.out = reinterpret_cast<u64*>(out);
+    p.U = a->n_users;
+    p.N = a->n_items;
+    p.hist_len = a->hist_indptr ? a->hist_len : 0;
+    p.slice_len = len;
+    p.n_pos = n_pos;
+    p.D = a->dim;
+    p.epi = a->epilogue;
+    p.mask_pad = a->mask_pad ? 1 : 0;
+    p.bias0 = a->bias0;
+    p.scale = a->scale;
+    const size_t ldsb = mr_lds_bytes(p.D);
+    static size_t have = 0;
+    if (ldsb > have) {
+        FR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(recommend_meanrank_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
+        have = ldsb;
+    }
+    ProfScope prof(K_REC_MEANRANK, stream);
+    prof_work(K_REC_MEANRANK, 2.0 * (double)a->n_users * (double)a->n_items * a->dim);
+    FR_LAUNCH(prof, recommend_meanrank_init_kernel, dim3((unsigned)((a->n_users + 255) / 256)), dim3(256), 0, stream, keys,
+              (const uint32_t*)tb, (long long)n_pos, p.U, p.N, p.out);
+    FR_CHECK_LAUNCH();
+    FR_LAUNCH(prof, recommend_meanrank_kernel, dim3((unsigned)tiles, (unsigned)S), dim3(256), ldsb, stream, p);
     FR_CHECK_LAUNCH();
     return FR_OK;
 }

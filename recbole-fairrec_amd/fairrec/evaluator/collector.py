@@ -10,6 +10,8 @@ With 'gauc' among the metrics the three ranking branches also gather `rec.meanra
 [2 * pos_rank_sum, user_len, pos_len] per user (fr_eval_meanrank_segments; exact integers, the first column doubled because a
 tied rank is a half); without it they collect and launch what they did before.  `eval_args.mode: labeled` keeps `rec.score`
 and `data.label` per batch (eval_batch_collect_labeled).
+
+`full_sort_eval: fused` feeds `eval_batch_collect_fused` the model's factors instead of the matrix (same keys, same values).
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ class Collector:
         self.meanrank = 'gauc' in [m.lower() for m in (config['metrics'] or [])]
         self._parts: Dict[str, List[torch.Tensor]] = {}
         self._data: Dict[str, object] = {}
+        self._err = None      # device error word of the fused path's kernels (eval_batch_collect_fused)
 
     def data_collect(self, train_data):
         """collector.py:80-97: what the exposure metrics need from the training data -- the catalogue size and how often
@@ -102,6 +105,61 @@ class Collector:
         for s in self.sst:
             if s in interaction:
                 self._add('data.' + s, interaction[s].to(scores.device)[positive_u])
+
+    def eval_batch_collect_fused(self, factors, interaction, hist_indptr: torch.Tensor, hist_items: torch.Tensor,
+                                 positive_u: torch.Tensor, positive_i: torch.Tensor):
+        """`eval_batch_collect` without its [users, n_items] matrix (`full_sort_eval: fused`): `factors` is what the model's
+        `full_sort_factors` hook answered for the batch's users, (hist_indptr, hist_items) their history CSR, ascending within a
+        user (case_study.history_csr).  The same keys, shapes and dtypes, and the same values as `eval_batch_collect` gathers
+        from the matrix fr_recommend_topk would write for these arguments: the list is selected in the kernel that scores
+        (k = K + 1, to see a tie at its end), a user whose list hangs on an exact tie gets its dense row after all and is
+        ranked on the host as there, the positives' scores are single cells (fr_recommend_cells), and `rec.meanrank` counts
+        the cells against them tile by tile (fr_recommend_meanrank)."""
+        from ..functional import recommend_cells, recommend_meanrank, recommend_topk
+        from ..utils.case_study import DENSE_ROWS_BYTES, history_csr
+        lib = _C.lib()
+        X, W = factors['X'], factors['W']
+        ub = factors.get('user_bias')
+        kw = dict(item_bias=factors.get('item_bias'), bias0=factors.get('bias0', 0.0), epilogue=factors.get('epilogue', 0),
+                  scale=factors.get('scale', 1.0), mask_pad=True)
+        U, n_items, dev = X.shape[0], W.shape[0], X.device
+        K = min(max(self.topk), n_items)
+        positive_u, positive_i = positive_u.to(dev, torch.int64), positive_i.to(dev, torch.int64)
+        if self._err is None:
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        vals, topk_idx = recommend_topk(X, W, min(K + 1, n_items), user_bias=ub, hist_indptr=hist_indptr, hist_items=hist_items,
+                                        **kw)
+        topk_idx = topk_idx[:, :K].contiguous()
+        # the rows `eval_batch_collect` finds: the K + 1 best values of a row are the same whoever selects them
+        tied = (vals[:, 1:] == vals[:, :-1]).any(dim=1).nonzero().view(-1)
+        group = max(DENSE_ROWS_BYTES // (4 * n_items), 1)
+        for lo in range(0, tied.numel(), group):
+            rows = tied[lo:lo + group]
+            ip, hi = history_csr(hist_indptr, hist_items, rows, n_items)
+            dense = recommend_topk(X[rows], W, 1, user_bias=None if ub is None else ub.view(-1)[rows], hist_indptr=ip,
+                                   hist_items=hi, want_scores=True, **kw)[2]
+            topk_idx[rows] = self._host_topk(dense, K).to(dev)
+        keys = torch.sort(positive_u * n_items + positive_i).values
+        rec = torch.empty((U, K + 1), dtype=torch.int32, device=dev)
+        _C.check(lib.fr_eval_hits(topk_idx.data_ptr(), U, K, n_items, keys.data_ptr(), keys.numel(), rec.data_ptr(),
+                                  _C.current_stream()), "fr_eval_hits")
+        if self.meanrank:
+            self._add('rec.meanrank', recommend_meanrank(X, W, keys, self._err, user_bias=ub, hist_indptr=hist_indptr,
+                                                         hist_items=hist_items, **kw))
+        self._add('rec.topk', rec)
+        self._add('rec.items', topk_idx)
+        self._add('rec.positive_score', recommend_cells(X, W, positive_u, positive_i, self._err, user_bias=ub,
+                                                        hist_indptr=hist_indptr, hist_items=hist_items, **kw))
+        self._add('data.positive_i', positive_i)
+        for s in self.sst:
+            if s in interaction:
+                self._add('data.' + s, interaction[s].to(dev)[positive_u])
+
+    def check_device_errors(self):
+        """Raises if a kernel of the fused path met an id outside its table (one host sync; the matrix path indexes with
+        torch and raises there)."""
+        if self._err is not None and int(self._err.item()):
+            raise _C.FairrecError('full_sort_eval fused: a positive (user row, item) lies outside the batch or the item table')
 
     def eval_batch_collect_candidates(self, origin_scores: torch.Tensor, row_idx: torch.Tensor, interaction,
                                       positive_u: torch.Tensor, positive_i: torch.Tensor, n_items: int):

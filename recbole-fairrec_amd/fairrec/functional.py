@@ -556,35 +556,43 @@ def topk_rows(scores, k, slices=0):
     return val, idx
 
 
-def recommend_topk(X, W, k, user_bias=None, item_bias=None, bias0=0.0, epilogue=0, scale=1.0, mask_pad=False,
-                   hist_indptr=None, hist_items=None, want_scores=False, slices=0):
-    """fr_recommend_topk: (values, indices[, scores]) of the k best items of every row of X against the item table W, score
-    = epilogue(((X[u] . W[i] + user_bias[u]) + item_bias[i]) + bias0), the pad item and the history CSR (ascending within a
-    user) scored -inf.  Nothing of size [users, items] is stored unless `want_scores` asks for the dense masked matrix."""
+def _rec_args(who, X, W, user_bias, item_bias, bias0, epilogue, scale, mask_pad, hist_indptr, hist_items):
+    """The fr_rec_args of a call (k, slices and scores_out left 0 for the caller) and the tensors its pointers belong to."""
     if not X.is_cuda:
-        raise _C.FairrecError('recommend_topk: ROCm device tensors only')
+        raise _C.FairrecError(f'{who}: ROCm device tensors only')
     X = X.detach().to(torch.float32).contiguous()
     W = W.detach().to(torch.float32).contiguous()
     U, D = X.shape
     N = W.shape[0]
     if W.dim() != 2 or W.shape[1] != D:
-        raise ValueError('recommend_topk: X [U, D] against W [n_items, D]')
-    k = _check_k(k, N)
+        raise ValueError(f'{who}: X [U, D] against W [n_items, D]')
     dev = X.device
     ub = user_bias.detach().to(torch.float32).contiguous().view(-1) if user_bias is not None else None
     ib = item_bias.detach().to(torch.float32).contiguous().view(-1) if item_bias is not None else None
     if (ub is not None and ub.numel() != U) or (ib is not None and ib.numel() != N):
-        raise ValueError('recommend_topk: user_bias [U], item_bias [n_items]')
+        raise ValueError(f'{who}: user_bias [U], item_bias [n_items]')
     ip = hi = None
     if hist_indptr is not None:
         ip = hist_indptr.to(dev, torch.int64).contiguous()
         hi = hist_items.to(dev, torch.int64).contiguous()
         if ip.numel() != U + 1:
-            raise ValueError('recommend_topk: hist_indptr [U + 1]')
-    scores = torch.empty((U, N), dtype=torch.float32, device=dev) if want_scores else None
-    a = _C.FrRecArgs(X.data_ptr(), W.data_ptr(), _C.ptr(ub), _C.ptr(ib), _C.ptr(ip), _C.ptr(hi), _C.ptr(scores), U, N,
-                     hi.numel() if hi is not None else 0, D, k, int(epilogue), int(bool(mask_pad)), 1, int(slices),
+            raise ValueError(f'{who}: hist_indptr [U + 1]')
+    a = _C.FrRecArgs(X.data_ptr(), W.data_ptr(), _C.ptr(ub), _C.ptr(ib), _C.ptr(ip), _C.ptr(hi), 0, U, N,
+                     hi.numel() if hi is not None else 0, D, 0, int(epilogue), int(bool(mask_pad)), 1, 0,
                      float(bias0), float(scale))
+    return a, (X, W, ub, ib, ip, hi)
+
+
+def recommend_topk(X, W, k, user_bias=None, item_bias=None, bias0=0.0, epilogue=0, scale=1.0, mask_pad=False,
+                   hist_indptr=None, hist_items=None, want_scores=False, slices=0):
+    """fr_recommend_topk: (values, indices[, scores]) of the k best items of every row of X against the item table W, score
+    = epilogue(((X[u] . W[i] + user_bias[u]) + item_bias[i]) + bias0), the pad item and the history CSR (ascending within a
+    user) scored -inf.  Nothing of size [users, items] is stored unless `want_scores` asks for the dense masked matrix."""
+    a, keep = _rec_args('recommend_topk', X, W, user_bias, item_bias, bias0, epilogue, scale, mask_pad, hist_indptr, hist_items)
+    U, N, dev = a.n_users, a.n_items, keep[0].device
+    k = _check_k(k, N)
+    scores = torch.empty((U, N), dtype=torch.float32, device=dev) if want_scores else None
+    a.k, a.slices, a.scores_out = k, int(slices), _C.ptr(scores) or None
     lib = _C.lib()
     ws = torch.empty(lib.fr_recommend_topk_workspace_bytes(ctypes.byref(a)) // 8, dtype=torch.int64, device=dev)
     val = torch.empty((U, k), dtype=torch.float32, device=dev)
@@ -592,6 +600,38 @@ def recommend_topk(X, W, k, user_bias=None, item_bias=None, bias0=0.0, epilogue=
     _C.check(lib.fr_recommend_topk(ctypes.byref(a), val.data_ptr(), idx.data_ptr(), _C.ptr(ws), ws.numel() * 8,
                                    _C.current_stream()), "fr_recommend_topk")
     return (val, idx, scores) if want_scores else (val, idx)
+
+
+def recommend_cells(X, W, cell_user, cell_item, err_flag, user_bias=None, item_bias=None, bias0=0.0, epilogue=0, scale=1.0,
+                    mask_pad=False, hist_indptr=None, hist_items=None):
+    """fr_recommend_cells: float32 [n] = the cells (cell_user[c], cell_item[c]) of the masked matrix `recommend_topk(...,
+    want_scores=True)` would return for the same arguments, bit for bit, without the matrix.  An id outside its table sets
+    DEV_ERR_INDEX_RANGE in `err_flag` (a device int32 / uint32 scalar the caller reads when it can afford the sync)."""
+    a, keep = _rec_args('recommend_cells', X, W, user_bias, item_bias, bias0, epilogue, scale, mask_pad, hist_indptr, hist_items)
+    dev = keep[0].device
+    cu = cell_user.to(dev, torch.int64).contiguous().view(-1)
+    ci = cell_item.to(dev, torch.int64).contiguous().view(-1)
+    if cu.numel() != ci.numel():
+        raise ValueError('recommend_cells: cell_user and cell_item of one length')
+    out = torch.empty(cu.numel(), dtype=torch.float32, device=dev)
+    _C.check(_C.lib().fr_recommend_cells(ctypes.byref(a), _C.ptr(cu), _C.ptr(ci), cu.numel(), _C.ptr(out), _C.ptr(err_flag),
+                                         _C.current_stream()), "fr_recommend_cells")
+    return out
+
+
+def recommend_meanrank(X, W, pos_keys, err_flag, user_bias=None, item_bias=None, bias0=0.0, epilogue=0, scale=1.0,
+                       mask_pad=False, hist_indptr=None, hist_items=None):
+    """fr_recommend_meanrank: int64 [U, 3] = [2 * pos_rank_sum, user_len, pos_len] per user, what fr_eval_meanrank_segments
+    returns on the dense masked matrix of the same arguments; pos_keys = the SORTED keys user * n_items + item."""
+    a, keep = _rec_args('recommend_meanrank', X, W, user_bias, item_bias, bias0, epilogue, scale, mask_pad, hist_indptr, hist_items)
+    dev = keep[0].device
+    keys = pos_keys.to(dev, torch.int64).contiguous().view(-1)
+    lib = _C.lib()
+    out = torch.empty((a.n_users, 3), dtype=torch.int64, device=dev)
+    ws = torch.empty(lib.fr_recommend_meanrank_workspace_bytes(ctypes.byref(a), keys.numel()) // 4, dtype=torch.int32, device=dev)
+    _C.check(lib.fr_recommend_meanrank(ctypes.byref(a), _C.ptr(keys), keys.numel(), _C.ptr(out), _C.ptr(ws), ws.numel() * 4,
+                                       _C.ptr(err_flag), _C.current_stream()), "fr_recommend_meanrank")
+    return out
 
 
 # ---- inference through whole MLPs in one launch (csrc/mlp_infer.hip) ----------------------------------------------------

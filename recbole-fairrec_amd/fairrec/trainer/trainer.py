@@ -27,6 +27,24 @@ from ..sampler import host_numpy_stream
 from ..utils import calculate_valid_score, dict2str, early_stopping, ensure_dir, get_local_time
 
 
+def full_sort_eval_of(config) -> str:
+    """The config key `full_sort_eval` of the `eval_args.mode: full` evaluation: `matrix` (default, also for a config without
+    the key: the [users, n_items] score matrix and torch.topk) or `fused` (a model that answers `full_sort_factors` is ranked
+    and counted in the scoring kernel, eval_batch_collect_fused; any other model takes the matrix path).  `fused` selects
+    max(topk) + 1 items per user to see a tie at the end of the list, so max(topk) is at most FR_TOPK_MAX - 1."""
+    value = config['full_sort_eval']
+    value = 'matrix' if value is None else value
+    if value not in ('matrix', 'fused'):
+        raise ValueError(f'full_sort_eval must be matrix or fused, not [{value}]')
+    if value == 'fused':
+        from .._C import FR_TOPK_MAX
+        topk = config['topk'] or [10]
+        if max([topk] if isinstance(topk, int) else list(topk)) > FR_TOPK_MAX - 1:
+            raise ValueError(f'full_sort_eval: fused selects max(topk) + 1 items per user: topk {topk} is above FR_TOPK_MAX - 1 = '
+                             f'{FR_TOPK_MAX - 1}')
+    return value
+
+
 class AbstractTrainer:
     def __init__(self, config, model):
         self.config = config
@@ -58,6 +76,7 @@ class Trainer(AbstractTrainer):
         self.saved_model_file = os.path.join(self.checkpoint_dir, '{}-{}.pth'.format(config['model'], get_local_time()))
         self.weight_decay = config['weight_decay'] or 0.0
         self.saved_sst_embed_file = os.path.join(self.checkpoint_dir, '{}_embed.pth'.format(config['model']))
+        self.full_sort_eval = full_sort_eval_of(config)
 
         self.start_epoch = 0
         self.cur_step = 0
@@ -394,6 +413,13 @@ class Trainer(AbstractTrainer):
         return dense_full_sort_scores(self.model, interaction, n_items, users_per_batch(self.config, n_items),
                                       self.config['ITEM_ID_FIELD'], self.device, sst_list)
 
+    def _full_sort_factors(self, interaction, n_items, sst_list=None):
+        """What the model's `full_sort_factors` hook answers for a batch of users (as case_study asks it), or None: a model
+        without the hook, or one that declines (a scorer of its own, a multi-GPU engine)."""
+        from ..utils.case_study import users_per_batch
+        hook = getattr(self.model, 'full_sort_factors', None)
+        return hook(interaction, sst_list, users_per_batch=users_per_batch(self.config, n_items)) if hook is not None else None
+
     def _ranking_evaluate(self, eval_data, sst_lists=(None,)):
         """One result over everything collected: every batch scored once per entry of `sst_lists` (None = no filter
         argument; the filtered models' validation pools all attribute subsets, trainer.py:1005-1022)."""
@@ -412,13 +438,24 @@ class Trainer(AbstractTrainer):
                                         for lo in range(0, len(interaction), per)])
                     collector.eval_batch_collect_candidates(scores, row_idx, interaction, positive_u, positive_i, n_items)
             return OrderedDict(evaluator.evaluate(collector.get_data_struct()))
+        fused = getattr(self, 'full_sort_eval', 'matrix') == 'fused'
         for user_df, (hist_u, hist_i), positive_u, positive_i in eval_data:
             user_df = user_df.to(self.device)
+            csr = None
             for sst_list in sst_lists:
+                factors = self._full_sort_factors(user_df, n_items, sst_list) if fused else None
+                if factors is not None:                                # `full_sort_eval: fused`: no [users, n_items] matrix
+                    if csr is None:
+                        from ..utils.case_study import history_csr
+                        csr = history_csr(eval_data.hist_indptr, eval_data.hist_items, user_df[eval_data.uid_field], n_items)
+                    collector.eval_batch_collect_fused(factors, user_df, csr[0], csr[1], positive_u, positive_i)
+                    continue
                 scores = self._full_sort_scores(user_df, n_items, sst_list)
                 scores[:, 0] = -float('inf')                           # [PAD], trainer.py:435
                 scores[hist_u, hist_i] = -float('inf')                 # items of earlier phases, :436-437
                 collector.eval_batch_collect(scores, user_df, positive_u, positive_i)
+        if fused:
+            collector.check_device_errors()
         return OrderedDict(evaluator.evaluate(collector.get_data_struct()))
 
     def _labeled_evaluate(self, eval_data, sst_lists=(None,)):
