@@ -34,10 +34,16 @@ __global__ __launch_bounds__(256) void nfcf_bce_kernel(const float* __restrict__
         }
     }
     if (b < B) {
-        const float o = 1.f / (1.f + __expf(-y[b]));
+        // y < -27: o (1 - o) is below the 1e-12 of BCE's backward, which then no longer cancels against the sigmoid's
+        // derivative: dy is proportional to o itself, and __expf is off by |y| u there (8e-7 at y = -28).  The exact
+        // exponential for those rows; none exists behind the scorer's ReLU, and every other row is the bits it was.
+        const float yb = y[b];
+        const float o = 1.f / (1.f + (yb < -27.f ? expf(-yb) : __expf(-yb)));
         const float t = label[b];
         // torch.nn.functional.binary_cross_entropy clamps both logs at -100
-        const float lo = fmaxf(__logf(o), -100.f), l1 = fmaxf(__logf(1.f - o), -100.f);
+        // (the same rows: log(o) = y - log1p(e^y), not the logarithm of an o that is subnormal below y = -87.3 and 0 below
+        // -88.7, where exp(-y) overflows and the term would read 100 for a |y| under 100)
+        const float lo = fmaxf(yb < -27.f ? yb - log1pf(expf(yb)) : __logf(o), -100.f), l1 = fmaxf(__logf(1.f - o), -100.f);
         l = -(t * lo + (1.f - t) * l1);
         out[b] = o;
         const float s = o * (1.f - o);
@@ -423,6 +429,7 @@ extern "C" int fr_nfcf_loss(const float* y, const float* label, const float* sst
     FR_CHECK_ARG(y && label && out && dy && loss && ws && B >= 1, "fr_nfcf_loss: bad argument");
     FR_CHECK_ARG(ws_bytes >= fr_nfcf_loss_workspace_bytes(B), "fr_nfcf_loss: workspace too small");
     const int nb = (int)((B + 255) / 256), ndf = (int)((B * DF_GROUP + DF_THREADS - 1) / DF_THREADS);
+    // (tests/test_loss_kernels_hip.py reads K from `kout` at this layout's offset: keep the two in step)
     char* p = (char*)ws;
     float* bce_part = (float*)p; p += align_up((size_t)nb * 4, 256);
     float* df_part = (float*)p; p += align_up((size_t)ndf * 4, 256);

@@ -128,7 +128,14 @@ static constexpr int OUTER_ROWS = 16;      // (32 until round 4: 256 workgroups 
 // -log(1e-10 + sigmoid(x)) and its derivative with hardware exp / log / rcp (1-2 ulp): with e = exp(-x), r = 1/(1+e):
 // sigmoid = r, 1 - sigmoid = e*r, so  term = -log(1e-10 + r),  dterm = -(r*r*e) / (1e-10 + r)
 __device__ __forceinline__ float bpr_term_e(float e, float& dterm);
-__device__ __forceinline__ float bpr_term_fast(float x, float& dterm) { return bpr_term_e(__expf(-x), dterm); }
+// (x < -88.7: exp(-x) overflows, and r * r * e = 0 * 0 * inf is not a number.  Held at the largest finite float, r and the
+// derivative are 0 like the plain bpr_term's, the term -log(1e-10) as before; every finite exponential is left as it was.
+// Only the overflow is held: a NaN score -- which the callers send down this path, no NaN is below 40 -- stays NaN in the
+// term and the derivative, so a diverged step still shows in its loss (fminf would have returned the finite operand))
+__device__ __forceinline__ float bpr_term_fast(float x, float& dterm) {
+    const float e = __expf(-x);
+    return bpr_term_e(e > 3.402823466e+38f ? 3.402823466e+38f : e, dterm);
+}
 // ... from e = exp(-x) itself: the outer form has x_ij = a_j + c_i, so exp(-x_ij) = exp(-a_j) exp(-c_i) is ONE multiplication per
 // pair instead of an exponential (B exponentials per row block and per thread column instead of B^2; |a|, |c| < 40 or the
 // plain form is used: no overflow of a factor)
@@ -273,10 +280,11 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
             if (err) atomicOr(err, FR_DEV_ERR_INDEX_RANGE);
             y = 0;
         }
-        const float lse = mx + __logf(se);
-        l = lse - z[y];
+        // the maximum is taken off BEFORE anything is added to it (torch's log_softmax): mx + log(se) would round at
+        // ulp(|mx|) / 2, which at |mx| = 1e4 is 5e-4 on the loss and on every probability's exponent
+        l = __logf(se) - (z[y] - mx);
         for (int c = 0; c < C; ++c)
-            dlogits[(size_t)m * C + c] = (__expf(z[c] - lse) - (c == (int)y ? 1.f : 0.f)) / (float)M;
+            dlogits[(size_t)m * C + c] = (__expf(z[c] - mx) / se - (c == (int)y ? 1.f : 0.f)) / (float)M;
     }
     l = wave_sum(l);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
