@@ -1157,6 +1157,36 @@ FR_API int fr_recommend_meanrank(const fr_rec_args* a, const int64_t* pos_keys, 
                                  size_t ws_bytes, uint32_t* err_flag, void* stream);
 
 /*
+ * fr_rows_l2_normalize: Y[r, :] = X[r, :] / max(|X[r, :]|_2, eps) for the M rows of an fp32 matrix -- the unit vectors whose
+ * dot product is the cosine similarity of the rows (eps as in nn.CosineSimilarity).  With both factors of fr_recommend_topk
+ * normalised once, epilogue 2 ranks sigmoid(cos(x_u, w_i)): PFCN_DMF's `full_sort_scorer: towers`.
+ *
+ * X [M, D] with row stride ldx, Y [M, D] with row stride ldy (floats; ldx, ldy >= D; the columns D.. of a row of Y are not
+ * written), norm_out optional [M].  1 <= D <= 256 (the fused ranking entries' own limit), M >= 0; M == 0 is FR_OK with
+ * nothing launched.  Y == X (with ldy == ldx) is allowed: a wave reads the whole of a row before it writes it; any other
+ * overlap of X and Y is not.  No workspace, no atomics, no LDS: one wave per row, column c in lane c % 64, slot e = c / 64.
+ *
+ * A row, in fp32 with every operation rounded to nearest:
+ *   1. each lane l:  s_l = 0;  for e = 0, 1, ... while l + 64 e < D:  s_l = fmaf(x[l + 64 e], x[l + 64 e], s_l)
+ *   2. s = the sum of the 64 s_l in the fixed butterfly order of the library's wave sum: six rounds
+ *      s_l += s_(l xor o), o = 32, 16, 8, 4, 2, 1, after which every lane holds s
+ *   3. n = sqrt(s), d = fmaxf(n, eps), y[c] = x[c] / d          (square root and quotient correctly rounded: __fsqrt_rn and
+ *      __fdiv_rn in their IEEE meaning)
+ *   4. norm_out[r] = n, the unclamped norm
+ *   5. a NaN or an infinity comes out as IEEE arithmetic gives it: an infinite norm (an infinite entry, or a sum of squares
+ *      that overflows) turns finite entries into 0 and infinite ones into NaN; a NaN entry makes n NaN, fmaxf then returns
+ *      eps, so the row's NaN stays NaN and its other entries come out as x / eps.  An all-zero row stays all zero (eps > 0).
+ * The bits of a row of Y and its norm depend on that row, D and eps alone -- not on M, the row's position, the wave that
+ * takes it, its neighbours' contents or the strides.  Against exact arithmetic: E + 6 roundings in s (E = ceil(D / 64)), halved
+ * by the root, one each for root and quotient: |y - y_exact| <= ((E + 6) / 2 + 2) 2^-24 |y_exact| to first order.
+ *
+ * FR_EINVAL before anything is launched or written, fr_last_error naming the entry: M < 0, D outside 1..256, ldx < D or
+ * ldy < D, a negative or NaN eps, a null X or Y with M > 0.
+ */
+FR_API int fr_rows_l2_normalize(const float* X, int64_t M, int32_t D, int64_t ldx, float eps, float* Y, int64_t ldy,
+                                float* norm_out, void* stream);
+
+/*
  * fr_mlp_infer: a whole MLP in one launch, for inference.  Each layer is Linear, then (optionally) BatchNorm1d on its RUNNING
  * statistics, then the activation (the codes of fr_linear_fwd: 0 none, 1 relu, 2 leakyrelu 0.01, 3 sigmoid, 4 tanh);
  *     Y[M, n_out_last] = (net_0(X) + net_1(X) + ...  in list order, fp32 adds from the first) / out_div      (IEEE division,

@@ -315,6 +315,7 @@ _PROTOS = {
     "fr_recommend_cells": (c_int, [POINTER(FrRecArgs), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "fr_recommend_meanrank_workspace_bytes": (c_size_t, [POINTER(FrRecArgs), c_int64]),
     "fr_recommend_meanrank": (c_int, [POINTER(FrRecArgs), c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fr_rows_l2_normalize": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "fr_mlp_infer": (c_int, [POINTER(FrMlpNet), c_int32, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "fr_pair_mlp_supported": (c_int, [c_int32, c_int32, POINTER(c_int32), c_int32]),
     "fr_pair_mlp_scores": (c_int, [POINTER(FrPairMlpArgs), c_void_p]),

@@ -634,6 +634,35 @@ def recommend_meanrank(X, W, pos_keys, err_flag, user_bias=None, item_bias=None,
     return out
 
 
+# ---- unit rows: the cosine of two rows as the dot product of their normalised forms (csrc/rows_normalize.hip) ------------
+def rows_l2_normalize(X, eps=1e-8, out=None, want_norm=False):
+    """fr_rows_l2_normalize: Y[r] = X[r] / max(|X[r]|, eps) for every row of a [rows, D] fp32 matrix, D in 1..256 (rows may be
+    strided, columns not), with the arithmetic of include/fairrec_hip.h: a row's bits depend on that row, D and eps alone.
+    `out`: where to write -- X itself for an in-place call -- else a new tensor.  `want_norm`: also the rows' unclamped norms,
+    (Y, norms [rows]).  Inference only: no autograd graph."""
+    if not X.is_cuda:
+        raise _C.FairrecError('rows_l2_normalize: ROCm device tensors only; there is no CPU fallback')
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise _C.FairrecError('rows_l2_normalize: X is a [rows, D] fp32 matrix')
+    X = X.detach()
+    M, D = X.shape
+    if not 1 <= D <= 256:
+        raise ValueError(f'rows_l2_normalize: D = {D} not in 1..256')
+    if D > 1 and X.stride(1) != 1:
+        X = X.contiguous()
+    Y = torch.empty((M, D), dtype=torch.float32, device=X.device) if out is None else out.detach()
+    if Y.shape != X.shape or Y.dtype != torch.float32 or Y.device != X.device or (D > 1 and Y.stride(1) != 1):
+        raise _C.FairrecError('rows_l2_normalize: out is an fp32 matrix of the shape and device of X with unit column stride')
+    norms = torch.empty(M, dtype=torch.float32, device=X.device) if want_norm else None
+    if M:
+        ldx = X.stride(0) if M > 1 else max(X.stride(0), D)
+        ldy = Y.stride(0) if M > 1 else max(Y.stride(0), D)
+        _C.check(_C.lib().fr_rows_l2_normalize(X.data_ptr(), M, D, ldx, float(eps), Y.data_ptr(), ldy, _C.ptr(norms),
+                                               _C.current_stream()), "fr_rows_l2_normalize")
+    Y = Y if out is None else out
+    return (Y, norms) if want_norm else Y
+
+
 # ---- inference through whole MLPs in one launch (csrc/mlp_infer.hip) ----------------------------------------------------
 def mlp_net(module) -> "_C.FrMlpNet":
     """The fr_mlp_net of an `MLPLayers` module: its Linear layers, its BatchNorm layers' RUNNING statistics, its activation.
