@@ -792,7 +792,11 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_stats_kernel(const float* _
 // fin[2n], fin[2n+1] = mean and 1/sqrt(var + eps) of column n; running statistics and invstd_out updated here.
 // Two passes over the chunk partials (count_c, mean_c, M2_c): mean = sum count_c mean_c / M, then
 // M2 = sum [M2_c + count_c (mean_c - mean)^2] -- the exact decomposition of the two-pass variance, as plain sums (four
-// waves take a quarter of the chunks each in ascending order, the quarters are added in order: a fixed tree).  The
+// waves take a quarter of the chunks each in ascending order, the quarters are added in order: a fixed tree).  A wave's
+// chain is a compensated sum (bn_sum_comp: what each addition rounds away is kept and added at the chain's end): in a plain
+// chain a chunk with an outlier (M2_c ~ 2^40) swallowed the terms behind it, each half a spacing of the running sum -- 1/std
+// of a [32768, N] column with one entry 2^20 came out 45 ulp off.  A chain of one or two chunks (M <= 256) keeps its bits: a
+// single addition has nothing to compensate.  The
 // sequential Chan update it replaces was a chain of 2 divisions per chunk: 20 us for 256 chunks.
 __global__ __launch_bounds__(BN_THREADS) void bn_fwd_fold_kernel(const float* __restrict__ part, int chunks, int M, int N, int rc,
                                                                  float eps, float momentum, float* __restrict__ rmean,
@@ -810,7 +814,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_fold_kernel(const float* __
     // launch, which is nothing but a latency chain (7.6 us with the two passes loading eight at a time; same sums, same order).
     constexpr int QMAX = 64;
     const int nn = ok ? n : N - 1;
-    float s = 0.f, m2 = 0.f;
+    float s = 0.f, m2 = 0.f, mc = 0.f;     // mc: what the additions into m2 rounded away (bn_sum_comp)
     if (q <= QMAX) {
         float2 pv[QMAX];
 #pragma unroll
@@ -828,7 +832,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_fold_kernel(const float* __
             if (c0 + k < c1) {
                 const float nb = (float)(min(M, (c0 + k + 1) * rc) - (c0 + k) * rc);
                 const float d = pv[k].x - mean_;
-                m2 += fmaf(nb * d, d, pv[k].y);
+                bn_sum_comp(fmaf(nb * d, d, pv[k].y), m2, mc);
             }
         s = mean_;
     } else {
@@ -846,12 +850,12 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_fold_kernel(const float* __
             const float nb = (float)(min(M, (c + 1) * rc) - c * rc);
             const float2 p = reinterpret_cast<const float2*>(part)[(size_t)c * N + nn];
             const float d = p.x - mean_;
-            m2 += fmaf(nb * d, d, p.y);
+            bn_sum_comp(fmaf(nb * d, d, p.y), m2, mc);
         }
         s = mean_;
     }
     const float mean = s;
-    sh[wave][lane] = m2;
+    sh[wave][lane] = m2 + mc;
     __syncthreads();
     if (wave != 0 || !ok) return;
     m2 = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
@@ -1017,7 +1021,7 @@ __device__ __forceinline__ float2 bn_fold_stats_inline(const float* __restrict__
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = (chunks + BN_WAVES - 1) / BN_WAVES, c0 = wave * q, c1 = min(chunks, c0 + q);
     const int nn = n < N ? n : N - 1;
-    float s = 0.f, m2 = 0.f, mean;
+    float s = 0.f, m2 = 0.f, mc = 0.f, mean;
     if (q <= QMAX) {
         float2 pv[QMAX];
 #pragma unroll
@@ -1035,7 +1039,7 @@ __device__ __forceinline__ float2 bn_fold_stats_inline(const float* __restrict__
             if (c0 + k < c1) {
                 const float nb = (float)(min(M, (c0 + k + 1) * rc) - (c0 + k) * rc);
                 const float d = pv[k].x - mean;
-                m2 += fmaf(nb * d, d, pv[k].y);
+                bn_sum_comp(fmaf(nb * d, d, pv[k].y), m2, mc);
             }
     } else {
 #pragma unroll 8
@@ -1049,10 +1053,10 @@ __device__ __forceinline__ float2 bn_fold_stats_inline(const float* __restrict__
             const float nb = (float)(min(M, (c + 1) * rc) - c * rc);
             const float2 p = reinterpret_cast<const float2*>(part)[(size_t)c * N + nn];
             const float d = p.x - mean;
-            m2 += fmaf(nb * d, d, p.y);
+            bn_sum_comp(fmaf(nb * d, d, p.y), m2, mc);
         }
     }
-    sh[wave][lane] = m2;
+    sh[wave][lane] = m2 + mc;
     __syncthreads();
     m2 = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
     __syncthreads();

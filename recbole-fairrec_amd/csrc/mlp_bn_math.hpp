@@ -17,6 +17,15 @@ __device__ __forceinline__ float bn_bwd_dz(float dy, float s, float xh, float a1
     return __fmul_rn(isg, fmaf(-a2, xh, fmaf(dy, s, -a1)));
 }
 
+// s += t, and what the addition rounded away (exactly: Knuth's two-sum, no branch) is collected in c; s + c at the end of a
+// chain is the compensated sum.  With two terms it is s itself: |error| <= half a spacing of s.
+__device__ __forceinline__ void bn_sum_comp(float t, float& s, float& c) {
+    const float n = s + t;
+    const float tp = n - s;
+    c += (s - (n - tp)) + (t - tp);
+    s = n;
+}
+
 // running statistic <- (1 - momentum) old + momentum value
 __device__ __forceinline__ float bn_running(float old, float momentum, float value) {
     return fmaf(momentum, value, __fmul_rn(1.f - momentum, old));
