@@ -962,17 +962,31 @@ FR_API int fr_randperm(uint32_t* state, int64_t n, int64_t* out, void* ws, size_
 /* ---- evaluation metrics (next-row f-2), recbole/evaluator/metrics.py ------------------------------------------------
  *   fr_topk_metrics           : rec_topk int32 [n_users, k+1] = hit flags of the ranked list | number of positives
  *                               (collector.py:146-154) -> out[6][k] doubles = Hit, MRR, NDCG, Recall, Precision, MAP
- *                               @ 1..k, means over users (metrics.py:40-232)
+ *                               @ 1..k, means over users (metrics.py:40-232).  A hit flag is any non-zero value.  A row
+ *                               with zero positives: NDCG 0 (divided by the ideal DCG of all k ranks, where the
+ *                               reference's index wraps), MAP 0, Recall 0 / 0 = NaN as the reference -- and then every
+ *                               Recall@j of the call is NaN
  *   fr_group_sums             : stats[s][g][0..2] = sum value, count, sum wtrue over the members
  *                               perm[seg_start[s] .. seg_start[s+1]) of segment s whose group index is g (perm = NULL:
- *                               identity).  The (item, group) tables of the fairness metrics (:948-970, :1322-1335)
+ *                               identity; wtrue = NULL: the third sum is 0).  A group no member of the segment has:
+ *                               0, 0, 0; an empty segment: all zeros.  A member whose group index is outside
+ *                               [0, n_groups) is counted in no cell.  1 <= n_groups <= 8.  The (item, group) tables of
+ *                               the fairness metrics (:948-970, :1322-1335)
  *   fr_fair_metrics_from_stats: out[0..4] = Value, Absolute, Under, Over unfairness (n_groups == 2; `+ 1e-5` counts as
  *                               the reference) and DifferentialFairness (float32 table, alpha = 1/n_segments) as means
- *                               over the segments (:972-979, :1068-1075, :1164-1171, :1260-1267, :1337-1342)
- * Double-precision sums in a fixed order. */
+ *                               over the segments (:972-979, :1068-1075, :1164-1171, :1260-1267, :1337-1342).  Any
+ *                               other n_groups: out[0..3] = 0.  DifferentialFairness per segment = the largest
+ *                               |logf(a) - logf(b)| over the pairs of table entries; a pair whose difference is NaN (the
+ *                               logarithm of a non-positive entry, i.e. a negative score sum) does not enter the maximum
+ *                               and the result stays finite (numpy's maximum in the reference's formula gives NaN there)
+ * Double-precision sums in a fixed order: the same input gives the same bits on every call.  FR_EINVAL (null pointer, a
+ * size below 1, n_groups outside 1..8, workspace below *_workspace_bytes) is returned before anything is launched or
+ * written. */
 /* fr_eval_hits: the `rec.topk` matrix of a batch of users (collector.py:146-154): rec_topk int32 [n_rows, k+1], entry
  * [u][j] = 1 if topk_idx[u][j] (the j-th ranked item id of row u) is a positive of row u, [u][k] = its number of
- * positives.  pos_keys = the sorted keys row * n_items + item of the batch's positives (no dense 0/1 matrix). */
+ * positives.  pos_keys = the sorted keys row * n_items + item of the batch's positives (no dense 0/1 matrix; may be NULL
+ * when n_pos == 0; distinct: a key listed twice counts twice in [u][k]).  List entries are item ids in [0, n_items); an entry outside that range is never a hit (its key would
+ * lie in another row's range).  FR_EINVAL (null pointer, n_rows, k or n_items below 1, n_pos < 0) before any launch. */
 FR_API int fr_eval_hits(const int64_t* topk_idx, int64_t n_rows, int32_t k, int64_t n_items, const int64_t* pos_keys,
                         int64_t n_pos, int32_t* rec_topk, void* stream);
 /* fr_eval_topk_segments: the ranked lists of an evaluation batch under the uniN protocol (trainer.py:441-456 + collector.py:149).

@@ -90,7 +90,11 @@ def value_type_unfairness(kind, pos_score, pos_iids, neg_score, neg_iids, sst_va
 
 
 def differential_fairness(score, iids, sst_value):
-    """metrics.py:1311-1342 (float32 tables, concentration parameter 1, alpha = 1 / #items)."""
+    """metrics.py:1311-1342 (float32 tables, concentration parameter 1, alpha = 1 / #items).
+
+    A non-positive table entry (a negative score sum) has a NaN logarithm; np.maximum carries it and the result here is
+    NaN.  The device kernel (csrc/metrics.hip) leaves such a pair out of the item's maximum and returns a finite number;
+    which of the two the reference's own tensors give is not on record (tests/test_metrics_ref.py asserts both sides)."""
     vals, sst_idx = np.unique(sst_value, return_inverse=True)
     _, iid_idx = np.unique(iids, return_inverse=True)
     K, G = iid_idx.max() + 1, len(vals)

@@ -8,6 +8,17 @@
 //   fair_from_stats_kernel   Value / Absolute / Under / Over unfairness (:972-979 and siblings) and DifferentialFairness
 //                            (:1337-1342, float32 tables like the reference) as means over the items
 // All sums are double precision in a fixed order (bit-reproducible).
+//
+// Edges the reference leaves to chance, as they are pinned here (tests/test_metrics_kernels_hip.py, DESIGN.md "Evaluation
+// quirks"):
+//   * a `rec.topk` row with zero positives: its NDCG@k is 0 (the reference's idcg index min(k, 0) - 1 wraps to the last
+//     rank, so it divides by the ideal DCG of all K ranks), its MAP@k is 0, its Recall@k is 0 / 0 = NaN as in the
+//     reference -- and so is every Recall@k of that evaluation;
+//   * fr_eval_hits: a list entry outside [0, n_items) is never a hit (its key would lie in another row's range);
+//   * fr_group_sums: a member whose group index is outside [0, n_groups) is counted in no cell;
+//   * DifferentialFairness: a pair of table entries one of whose float32 logarithms is NaN (a non-positive entry, from a
+//     negative score sum) does not enter the item's maximum, and the result stays finite; numpy's maximum in the
+//     reference's formula would return NaN there (oracle.metrics.differential_fairness does).
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -20,6 +31,8 @@ __device__ __forceinline__ double wave_sum_d(double x) {
 }
 
 // one wave per 64 users (lane = user); part[block][m][k], m = hit, mrr, ndcg, recall, precision, map
+// A row with zero positives: NDCG 0 (divided by the ideal DCG of all K ranks, the reference's wrapped index), MAP 0,
+// Recall NaN (0 / 0, as the reference).
 __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restrict__ rec_topk, long long U, int K,
                                                           double* __restrict__ part) {
     const int lane = threadIdx.x;
@@ -31,6 +44,9 @@ __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restr
     int csum = 0;
     double first_rr = 0.0, dcg = 0.0, idcg = 0.0, sum_pre = 0.0;
     double* out = part + (size_t)blockIdx.x * 6 * K;
+    double idcg_all = 0.0;       // ilen <= 0 only: the ideal DCG of all K ranks
+    if (ok && ilen <= 0)
+        for (int k = 0; k < K; ++k) idcg_all += 1.0 / log2((double)(k + 2));
     for (int k = 0; k < K; ++k) {
         const bool hit = ok && row[k] != 0;
         const double disc = 1.0 / log2((double)(k + 2));
@@ -40,7 +56,7 @@ __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restr
         if (k < ilen) idcg += disc;
         const double v0 = ok && csum > 0 ? 1.0 : 0.0;
         const double v1 = ok ? first_rr : 0.0;
-        const double v2 = ok ? dcg / idcg : 0.0;
+        const double v2 = ok ? dcg / (ilen > 0 ? idcg : idcg_all) : 0.0;
         const double v3 = ok ? (double)csum / (double)pos_len : 0.0;
         const double v4 = ok ? (double)csum / (double)(k + 1) : 0.0;
         // MAP (metrics.py:100-139): sum over the hits so far of Precision@j, over min(k + 1, min(positives, K))
@@ -61,7 +77,8 @@ __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restr
 
 // rec_topk[u][k] = 1 if the k-th ranked item of row u is one of its positives, rec_topk[u][K] = number of positives of
 // row u (collector.py:146-154 without the dense [users, items] 0/1 matrix): the positives arrive as the SORTED keys
-// row * n_items + item; membership and the per-row count are binary searches.
+// row * n_items + item; membership and the per-row count are binary searches.  A list entry outside [0, n_items) is never
+// a hit: its key would fall into another row's range.
 __device__ __forceinline__ long long lower_bound_ll(const int64_t* __restrict__ a, long long n, long long key) {
     long long lo = 0, hi = n;
     while (lo < hi) {
@@ -82,9 +99,10 @@ __global__ __launch_bounds__(256) void eval_hits_kernel(const int64_t* __restric
     if (k == K) {
         rec_topk[t] = (int32_t)(lower_bound_ll(pos_keys, n_pos, (u + 1) * n_items) - lower_bound_ll(pos_keys, n_pos, u * n_items));
     } else {
-        const long long key = u * n_items + topk_idx[u * K + k];
+        const long long item = topk_idx[u * K + k];
+        const long long key = u * n_items + item;
         const long long p = lower_bound_ll(pos_keys, n_pos, key);
-        rec_topk[t] = (p < n_pos && pos_keys[p] == key) ? 1 : 0;
+        rec_topk[t] = (item >= 0 && item < n_items && p < n_pos && pos_keys[p] == key) ? 1 : 0;
     }
 }
 
@@ -101,6 +119,7 @@ __global__ __launch_bounds__(256) void column_sum_kernel(const double* __restric
 static constexpr int GS_GROUP = 16, GS_THREADS = 256, GS_MAXG = 8;
 
 // stats[k][g][0..2] = sum value, count, sum wtrue over the members perm[seg_start[k] .. seg_start[k+1]) with group g
+// (a group no member has: 0, 0, 0; a member whose group index is outside [0, G) is counted in no cell)
 __global__ __launch_bounds__(GS_THREADS) void group_sums_kernel(const int64_t* __restrict__ perm,
                                                                 const int64_t* __restrict__ seg_start, long long K,
                                                                 const int32_t* __restrict__ group,
@@ -160,6 +179,7 @@ __global__ __launch_bounds__(256) void fair_from_stats_kernel(const double* __re
             t[3] = fabs((p0 - r0 > 0 ? p0 - r0 : 0.0) - (p1 - r1 > 0 ? p1 - r1 : 0.0));
         }
         // DifferentialFairness: float32 table (score_sum + 1/K) / (count + 1), epsilon = max pairwise |log a - log b|
+        // (a NaN difference -- the logarithm of a non-positive entry -- fails `e > eps` and leaves the maximum as it is)
         float eps = 0.f;
         const double alpha = 1.0 / (double)K;
         for (int i = 0; i < G; ++i) {
