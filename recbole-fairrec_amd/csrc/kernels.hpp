@@ -99,6 +99,19 @@ struct SortJobList {
 };
 int launch_sort_many(const SortJobList& jobs, int64_t n_rows_max, uint32_t* err, hipStream_t stream);
 
+// The masking writes on a dense [U, ld] score matrix (recommend.hip): column 0 with mask_pad, and the cells of every user's
+// history CSR (indptr may be null), become -inf.  Accounted under K_TOPK_ROWS.
+int launch_score_mask(float* scores, long long U, long long N, long long ld, const long long* indptr, const long long* hist,
+                      long long hist_len, int mask_pad, hipStream_t stream);
+
+// a history CSR as fr_rec_args and fr_pair_mlp_args carry it: optional; with it, items (unless empty) and the ascending order
+inline int check_hist_csr(const int64_t* indptr, const int64_t* items, int64_t len, int32_t sorted, const char* who) {
+    if (!indptr) return FR_OK;
+    FR_CHECK_ARG(len >= 0 && (items || len == 0), "%s: history CSR without items (hist_indptr without hist_items)", who);
+    FR_CHECK_ARG(sorted == 1, "%s: the history CSR must be ascending within each user (hist_sorted = 1)", who);
+    return FR_OK;
+}
+
 // Device view of a lazy-Adam table.
 struct TableV {
     float* p;

@@ -188,25 +188,6 @@ __global__ __launch_bounds__(256) void pair_mlp_kernel(PairK a) {
     }
 }
 
-// the pad column and the history cells become -inf (a wave per user)
-__global__ __launch_bounds__(256) void pair_mlp_mask_kernel(float* __restrict__ scores, const long long* __restrict__ indptr,
-                                                            const long long* __restrict__ hist, long long hist_len,
-                                                            long long U, long long N, long long ld, int mask_pad) {
-    const int lane = threadIdx.x & 63;
-    const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (u >= U) return;
-    float* row = scores + (size_t)u * ld;
-    if (mask_pad && lane == 0) row[0] = -INFINITY;
-    if (!indptr) return;
-    long long p = indptr[u], q = indptr[u + 1];
-    p = p < 0 ? 0 : p;
-    q = q > hist_len ? hist_len : q;
-    for (long long j = p + lane; j < q; j += 64) {
-        const long long it = hist[j];
-        if (it >= 0 && it < N) row[it] = -INFINITY;
-    }
-}
-
 // widths, layer count and activation of a scorer this entry serves
 static int pm_shape_check(int32_t n1, int32_t n_linears, const int32_t* n_out, int32_t act, const char* who) {
     FR_CHECK_ARG(n_linears >= 2 && n_linears <= FR_PAIR_MLP_MAX_LINEARS, "%s: n_linears %d not in 2..%d", who, n_linears,
@@ -245,10 +226,7 @@ extern "C" int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream_) {
                  (long long)a->n_users);
     FR_CHECK_ARG(a->n_items >= 0 && a->n_items <= 0x7fffffffLL, "%s: n_items %lld out of range", who, (long long)a->n_items);
     FR_CHECK_ARG(a->ld >= a->n_items, "%s: ld %lld < n_items %lld", who, (long long)a->ld, (long long)a->n_items);
-    if (a->hist_indptr) {
-        FR_CHECK_ARG(a->hist_len >= 0 && (a->hist_items || a->hist_len == 0), "%s: hist_indptr without hist_items", who);
-        FR_CHECK_ARG(a->hist_sorted == 1, "%s: the history CSR must be ascending within each user (hist_sorted = 1)", who);
-    }
+    if ((rc = check_hist_csr(a->hist_indptr, a->hist_items, a->hist_len, a->hist_sorted, who))) return rc;
     if (a->n_users == 0 || a->n_items == 0) return FR_OK;
 
     p.P = a->P;
@@ -275,13 +253,8 @@ extern "C" int fr_pair_mlp_scores(const fr_pair_mlp_args* a, void* stream_) {
     prof_work(K_PAIR_MLP, pl.flop * (double)a->n_users * (double)a->n_items);
     FR_LAUNCH(prof, pair_mlp_kernel, dim3((unsigned)tiles, (unsigned)S), dim3(256), ldsb, stream, p);
     FR_CHECK_LAUNCH();
-    if (a->mask_pad || a->hist_indptr) {
-        ProfScope prof2(K_TOPK_ROWS, stream);      // (as fr_recommend_topk accounts its mask pass: K_PAIR_MLP times the scorer alone)
-        FR_LAUNCH(prof2, pair_mlp_mask_kernel, dim3((unsigned)((a->n_users + 3) / 4)), dim3(256), 0, stream, a->scores_out,
-                  reinterpret_cast<const long long*>(a->hist_indptr), reinterpret_cast<const long long*>(a->hist_items),
-                  a->hist_indptr ? (long long)a->hist_len : 0LL, (long long)a->n_users, (long long)a->n_items, (long long)a->ld,
-                  a->mask_pad ? 1 : 0);
-        FR_CHECK_LAUNCH();
-    }
+    if (a->mask_pad || a->hist_indptr)      // (accounted under K_TOPK_ROWS: K_PAIR_MLP times the scorer alone)
+        return launch_score_mask(a->scores_out, a->n_users, a->n_items, a->ld, reinterpret_cast<const long long*>(a->hist_indptr),
+                                 reinterpret_cast<const long long*>(a->hist_items), a->hist_len, a->mask_pad, stream);
     return FR_OK;
 }

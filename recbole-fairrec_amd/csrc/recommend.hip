@@ -136,18 +136,150 @@ __device__ __forceinline__ void wave_compact(u64* b, int kp, int c, int k, u64* 
     if (lane == 0) *cnt = *kept = c < k ? c : k;
 }
 
-struct RecK {
+// ---- the score tile: what recommend_kernel, recommend_cells_kernel and recommend_meanrank_kernel share -----------------------
+// A cell (user, item) has one score, whichever kernel computes it and however the work was cut: the fp32 MFMA chain over the
+// column pairs, ascending from 0 (rec_link), then cell_score.  The two tiled kernels run the chain in RecTile::step, on the
+// users rec_load_users put in LDS; the cells kernel feeds rec_link from memory, the same ceil(D / 2) links.  Every piece below
+// is defined once, so that an edit to the tile is an edit to all three.
+
+// the arguments of an fr_rec_args that every kernel reads (rec_fill); RecK, CellK and MrK add their own
+struct RecArgs {
     const float* X;
     const float* W;
     const float* ub;
     const float* ib;
     const long long* indptr;
     const long long* hist;
+    long long U, N, hist_len;
+    int D, epi, mask_pad;
+    float bias0, scale;
+};
+
+// one link of a cell's chain: A = X (lane l: user l & 31, column 2s + (l >> 5)), B = W^T (item l & 31, the same column) ...
+__device__ __forceinline__ f32x16 rec_link(float x, float w, f32x16 acc) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(x, w, acc, 0, 0, 0);
+}
+
+// ... after which accumulator register r of a lane, h = l >> 5, holds (user rec_user_of(r, h), item l & 31)
+__device__ __forceinline__ int rec_user_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// What the chain's sum becomes before the epilogue: the bias adds in this order.  ubv / ibv are read only under a.ub / a.ib.
+__device__ __forceinline__ float cell_sum(const RecArgs& a, float acc, float ubv, float ibv) {
+    float x = acc;
+    if (a.ub) x = x + ubv;
+    if (a.ib) x = x + ibv;
+    return x + a.bias0;
+}
+
+// The score of a cell.  (recommend_kernel without scores_out stages cell_sum and applies epilogue_exact to the staged sums
+// that may enter a list: the same two halves, in the same order.)
+__device__ __forceinline__ float cell_score(const RecArgs& a, float acc, float ubv, float ibv) {
+    return epilogue_exact(cell_sum(a, acc, ubv, ibv), a.epi, a.scale);
+}
+
+// user u's range of the history CSR, clamped to the items array
+__device__ __forceinline__ void hist_range(const long long* __restrict__ indptr, long long hist_len, long long u, long long& p,
+                                           long long& q) {
+    p = indptr[u];
+    q = indptr[u + 1];
+    p = p < 0 ? 0 : p;
+    q = q > hist_len ? hist_len : q;
+}
+
+// is `item` among the ascending hist[p..q)?
+__device__ __forceinline__ bool hist_has(const long long* __restrict__ hist, long long p, long long q, long long item) {
+    while (p < q) {
+        const long long m = (p + q) >> 1;
+        const long long v = hist[m];
+        if (v == item) return true;
+        if (v < item) p = m + 1;
+        else q = m;
+    }
+    return false;
+}
+
+// the first position of user u's history that holds an item >= bound (0 without a history, or beyond the last user)
+__device__ __forceinline__ long long hist_lower_bound(const RecArgs& a, long long u, long long bound) {
+    long long p = 0, q = 0;
+    if (a.indptr && u < a.U) {
+        hist_range(a.indptr, a.hist_len, u, p, q);
+        while (p < q) {
+            const long long m = (p + q) >> 1;
+            if (a.hist[m] < bound) p = m + 1;
+            else q = m;
+        }
+    }
+    return p;
+}
+
+// [hp[u], hq[u]): the history of user u0 + u inside the slice [lo, hi) of the items (threads 0..63)
+__device__ __forceinline__ void rec_slice_history(const RecArgs& a, long long u0, long long lo, long long hi, long long* hp,
+                                                  long long* hq, int tid) {
+    if (tid < 2 * REC_UT) ((tid & 1) ? hq : hp)[tid >> 1] = hist_lower_bound(a, u0 + (tid >> 1), (tid & 1) ? hi : lo);
+}
+
+// the tile's users: Xs [32][(D + 1) | 1], zero beyond column D and beyond user U, and their biases ubs [32]
+__device__ __forceinline__ void rec_load_users(const RecArgs& a, long long u0, float* Xs, float* ubs, int tid) {
+    const int D = a.D, Dx = (D + 1) | 1;
+    for (int e = tid; e < REC_UT * Dx; e += 256) {
+        const int u = e / Dx, c = e - u * Dx;
+        Xs[e] = (c < D && u0 + u < a.U) ? a.X[(size_t)(u0 + u) * D + c] : 0.f;
+    }
+    if (tid < REC_UT) ubs[tid] = (a.ub && u0 + tid < a.U) ? a.ub[u0 + tid] : 0.f;
+}
+
+// The slice's rows of W go through LDS 128 items x 32 columns at a time (Ws [128][REC_WST]), fetched into registers one
+// chunk ahead: the caller fetches (lo, 0) before its first step, and a step requests what the next one stages.
+struct RecTile {
+    float pre[16];      // element tid + 256 j of the chunk [128][32]
+
+    __device__ __forceinline__ void fetch(const RecArgs& a, long long i0, long long hi, int c0, int tid) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int e = tid + 256 * j, item = e >> 5, col = e & 31;
+            const long long it = i0 + item;
+            pre[j] = (it < hi && c0 + col < a.D) ? a.W[(size_t)it * a.D + c0 + col] : 0.f;
+        }
+    }
+
+    // The 32 users x items i0 + 32 wave .. + 31 of the slice [.., hi): per chunk, the image is staged between two barriers
+    // (the first one also ends whatever the caller did with LDS since the step before), the next chunk is requested, and the
+    // chain goes on.  In the first chunk staged() runs before the second barrier and fetched() behind the request.
+    template <class Staged, class Fetched>
+    __device__ __forceinline__ f32x16 step(const RecArgs& a, const float* Xs, float* Ws, long long i0, long long hi, int tid,
+                                           Staged&& staged, Fetched&& fetched) {
+        const int lane = tid & 63, wave = uniform(tid >> 6), li = lane & 31, h = lane >> 5;
+        const int D = a.D, Dx = (D + 1) | 1;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int c0 = 0; c0 < D; c0 += REC_DK) {
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int e = tid + 256 * j;
+                Ws[(e >> 5) * REC_WST + (e & 31)] = pre[j];
+            }
+            if (c0 == 0) staged();
+            __syncthreads();
+            if (c0 + REC_DK < D) fetch(a, i0, hi, c0 + REC_DK, tid);
+            else if (i0 + REC_IB < hi) fetch(a, i0 + REC_IB, hi, 0, tid);
+            if (c0 == 0) fetched();
+            const int left = (D - c0 + 1) >> 1, steps = left < REC_DK / 2 ? left : REC_DK / 2;
+            const float* xp = Xs + li * Dx + c0 + h;
+            const float* wp = Ws + (wave * 32 + li) * REC_WST + h;
+            for (int s = 0; s < steps; ++s) acc = rec_link(xp[2 * s], wp[2 * s], acc);
+        }
+        return acc;
+    }
+};
+
+struct RecK : RecArgs {
     float* scores;
     u64* ws;
-    long long U, N, hist_len, slice_len;
-    int D, k, epi, mask_pad, S, cap;
-    float bias0, scale, inv_scale;
+    long long slice_len;
+    int k, S, cap;
+    float inv_scale;
 };
 
 // A staged candidate: the exact key against the threshold, the mask test, then the push.
@@ -155,20 +287,8 @@ __device__ __forceinline__ void rec_push(const RecK& a, u64* buf, int* cnt, int 
                                          long long p, long long q) {
     u64 key = make_key(score, (uint32_t)item);
     if (!(key > t)) return;
-    bool masked = a.mask_pad && item == 0;
-    if (!masked) {
-        while (p < q) {      // [p, q): the user's history inside this slice (empty for most users of most slices)
-            const long long m = (p + q) >> 1;
-            const long long v = a.hist[m];
-            if (v == item) {
-                masked = true;
-                break;
-            }
-            if (v < item) p = m + 1;
-            else q = m;
-        }
-    }
-    if (masked) {
+    // [p, q): the user's history inside this slice (empty for most users of most slices)
+    if ((a.mask_pad && item == 0) || hist_has(a.hist, p, q, item)) {
         key = make_key(-INFINITY, (uint32_t)item);
         if (!(key > t)) return;
     }
@@ -176,23 +296,21 @@ __device__ __forceinline__ void rec_push(const RecK& a, u64* buf, int* cnt, int 
     if (pos < a.cap) buf[(size_t)ur * a.cap + pos] = key;
 }
 
-// Workgroup (tile of 32 users, slice of the items).  The users' rows stay in LDS for the whole launch; the slice's rows of W
-// go through LDS 128 items x 32 columns at a time, fetched into registers one chunk ahead.  Wave w multiplies the 32 users
-// with items 32w..32w+31 of the step: A = X (lane l: user l & 31, column 2s + (l >> 5)), B = W^T, so that accumulator
-// register r of a lane holds (user (r & 3) + 8 (r >> 2) + 4 (l >> 5), item l & 31) and the chain over the columns is one
-// ascending fmaf chain from 0 (v_mfma_f32_32x32x2_f32).  A cell that may beat its user's threshold (epilogue_approx against the
-// user's limit; with scores_out every cell's exact score is computed anyway) is staged in the wave's LDS list, eight
-// registers' worth at a time, and the staged cells then get their exact score and key side by side on the lanes (one
-// divergent pass per 512 cells instead of one per register); one above the threshold is pushed into the user's LDS list after
-// the mask test (pad item; binary search in the part of the user's history that lies in the slice, found once per launch).  A
-// list that could overflow in the next step is compacted to its best k, and threshold and limit rise.  A list holds up to
-// cap - 128 >= k keys between steps, about 2k where LDS allows: rank counting costs (k + slack)^2 per slack survivors.
-// Each slice's sorted list goes to the workspace.
+// Workgroup (tile of 32 users, slice of the items).  The users' rows stay in LDS for the whole launch; the slice's rows of W go
+// through the score tile above: wave w multiplies the 32 users with items 32w..32w+31 of the step, and the chain over the
+// columns is one ascending fmaf chain from 0 (v_mfma_f32_32x32x2_f32).  A cell that may beat its user's threshold
+// (epilogue_approx against the user's limit; with scores_out every cell's exact score is computed anyway) is staged in the
+// wave's LDS list, eight registers' worth at a time, and the staged cells then get their exact score and key side by side on
+// the lanes (one divergent pass per 512 cells instead of one per register); one above the threshold is pushed into the user's
+// LDS list after the mask test (pad item; binary search in the part of the user's history that lies in the slice, found once
+// per launch).  A list that could overflow in the next step is compacted to its best k, and threshold and limit rise.  A list
+// holds up to cap - 128 >= k keys between steps, about 2k where LDS allows: rank counting costs (k + slack)^2 per slack
+// survivors.  Each slice's sorted list goes to the workspace.
 __global__ __launch_bounds__(256) void recommend_kernel(RecK a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
     const int li = lane & 31, h = lane >> 5;
-    const int D = a.D, Dx = (D + 1) | 1, cap = a.cap, k = a.k, epi = a.epi;
+    const int Dx = (a.D + 1) | 1, cap = a.cap, k = a.k, epi = a.epi;
     const bool dense = a.scores != nullptr;
     u64* buf = reinterpret_cast<u64*>(smem);              // [32][cap]
     u64* thr = buf + (size_t)REC_UT * cap;                // [32]
@@ -210,86 +328,37 @@ __global__ __launch_bounds__(256) void recommend_kernel(RecK a) {
     const long long lo = (long long)blockIdx.y * a.slice_len;
     const long long hi = lo + a.slice_len < a.N ? lo + a.slice_len : a.N;
 
-    for (int e = tid; e < REC_UT * Dx; e += 256) {
-        const int u = e / Dx, c = e - u * Dx;
-        Xs[e] = (c < D && u0 + u < a.U) ? a.X[(size_t)(u0 + u) * D + c] : 0.f;
-    }
+    rec_load_users(a, u0, Xs, ubs, tid);
     if (tid < REC_UT) {
         thr[tid] = 0ull;
         lim[tid] = -INFINITY;
         cnt[tid] = 0;
         kept[tid] = 0;
-        ubs[tid] = (a.ub && u0 + tid < a.U) ? a.ub[u0 + tid] : 0.f;
     }
-    if (tid < 2 * REC_UT) {      // lower bounds of the slice's two ends in each user's history
-        const int u = tid >> 1;
-        const long long bound = (tid & 1) ? hi : lo;
-        long long p = 0, q = 0;
-        if (a.indptr && u0 + u < a.U) {
-            p = a.indptr[u0 + u];
-            q = a.indptr[u0 + u + 1];
-            p = p < 0 ? 0 : p;
-            q = q > a.hist_len ? a.hist_len : q;
-            while (p < q) {
-                const long long m = (p + q) >> 1;
-                if (a.hist[m] < bound) p = m + 1;
-                else q = m;
-            }
-        }
-        ((tid & 1) ? hq : hp)[u] = p;
-    }
+    rec_slice_history(a, u0, lo, hi, hp, hq, tid);
 
-    float pre[16];
-    auto fetch = [&](long long i0, int c0) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int e = tid + 256 * j, item = e >> 5, col = e & 31;
-            const long long it = i0 + item;
-            pre[j] = (it < hi && c0 + col < D) ? a.W[(size_t)it * D + c0 + col] : 0.f;
-        }
-    };
-    if (lo < hi) fetch(lo, 0);
+    RecTile tile;
+    if (lo < hi) tile.fetch(a, lo, hi, 0, tid);
     for (long long i0 = lo; i0 < hi; i0 += REC_IB) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         const long long item = i0 + wave * 32 + li;
         const bool ok = item < hi;
         const float ibv = (a.ib && ok) ? a.ib[item] : 0.f;
-        for (int c0 = 0; c0 < D; c0 += REC_DK) {
-            __syncthreads();      // the image is free: the products of the chunk before, and the compaction, are done
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int e = tid + 256 * j;
-                Ws[(e >> 5) * REC_WST + (e & 31)] = pre[j];
-            }
-            __syncthreads();
-            if (c0 + REC_DK < D) fetch(i0, c0 + REC_DK);
-            else if (i0 + REC_IB < hi) fetch(i0 + REC_IB, 0);
-            const int left = (D - c0 + 1) >> 1, steps = left < REC_DK / 2 ? left : REC_DK / 2;
-            const float* xp = Xs + li * Dx + c0 + h;
-            const float* wp = Ws + (wave * 32 + li) * REC_WST + h;
-            for (int s = 0; s < steps; ++s)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xp[2 * s], wp[2 * s], acc, 0, 0, 0);
-        }
+        // (the step's first barrier: the compaction of the step before is done as well)
+        const f32x16 acc = tile.step(a, Xs, Ws, i0, hi, tid, [] {}, [] {});
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             int nst = 0;      // staged cells of this wave (uniform)
 #pragma unroll
             for (int rr = 0; rr < 8; ++rr) {
                 const int r = half * 8 + rr;
-                const int ur = (r & 3) + 8 * (r >> 2) + 4 * h;
-                float x = acc[r];
-                if (a.ub) x = x + ubs[ur];
-                if (a.ib) x = x + ibv;
-                x = x + a.bias0;
+                const int ur = rec_user_of(r, h);
                 const bool live = ok && u0 + ur < a.U;
-                float rough;
+                float x, rough;
                 if (dense) {
-                    x = epilogue_exact(x, epi, a.scale);
+                    x = rough = cell_score(a, acc[r], ubs[ur], ibv);
                     if (live) a.scores[(size_t)(u0 + ur) * a.N + item] = x;
-                    rough = x;
                 } else {
+                    x = cell_sum(a, acc[r], ubs[ur], ibv);
                     rough = epilogue_approx(x, epi, a.scale, a.inv_scale);
                 }
                 const bool cand = live && !(rough < lim[ur]);
@@ -327,19 +396,19 @@ __global__ __launch_bounds__(256) void recommend_kernel(RecK a) {
     }
 }
 
-// scores_out of fr_recommend_topk: the pad column and the history cells become -inf (a wave per user)
+// A dense [U, ld] score matrix (scores_out of fr_recommend_topk, fr_pair_mlp_scores): the pad column and the history cells
+// become -inf (a wave per user)
 __global__ __launch_bounds__(256) void recommend_mask_kernel(float* __restrict__ scores, const long long* __restrict__ indptr,
                                                              const long long* __restrict__ hist, long long hist_len,
-                                                             long long U, long long N, int mask_pad) {
+                                                             long long U, long long N, long long ld, int mask_pad) {
     const int lane = threadIdx.x & 63;
     const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= U) return;
-    float* row = scores + (size_t)u * N;
+    float* row = scores + (size_t)u * ld;
     if (mask_pad && lane == 0) row[0] = -INFINITY;
     if (!indptr) return;
-    long long p = indptr[u], q = indptr[u + 1];
-    p = p < 0 ? 0 : p;
-    q = q > hist_len ? hist_len : q;
+    long long p, q;
+    hist_range(indptr, hist_len, u, p, q);
     for (long long j = p + lane; j < q; j += 64) {
         const long long it = hist[j];
         if (it >= 0 && it < N) row[it] = -INFINITY;
@@ -485,21 +554,44 @@ static int plan_slices(long long n, int k, long long groups, long long want, lon
     return (int)((n + len - 1) / len);
 }
 
-static int rec_check(const fr_rec_args* a, const char* who) {
+// The arguments every entry reads of an fr_rec_args (k, slices and scores_out are fr_recommend_topk's alone).  Every launch
+// puts n_users, or its tiles, into a grid dimension.
+static int eval_check(const fr_rec_args* a, const char* who) {
     FR_CHECK_ARG(a, "%s: null argument struct", who);
     FR_CHECK_ARG(a->X && a->W, "%s: null X or W", who);
-    FR_CHECK_ARG(a->n_users >= 0 && a->n_items >= 1 && a->n_items <= 0x7fffffffLL, "%s: bad n_users / n_items", who);
+    FR_CHECK_ARG(a->n_users >= 0 && a->n_users <= 0x7fffffffLL && a->n_items >= 1 && a->n_items <= 0x7fffffffLL,
+                 "%s: bad n_users / n_items", who);
     FR_CHECK_ARG(a->dim >= 1 && a->dim <= 256, "%s: dim %d not in 1..256", who, a->dim);
-    FR_CHECK_ARG(a->k >= 1 && a->k <= FR_TOPK_MAX && a->k <= a->n_items, "%s: k %d not in 1..min(%d, n_items)", who, a->k,
-                 FR_TOPK_MAX);
     FR_CHECK_ARG(a->epilogue >= 0 && a->epilogue <= 2, "%s: unknown epilogue %d", who, a->epilogue);
     FR_CHECK_ARG(a->epilogue != 1 || a->scale > 0.f, "%s: epilogue 1 needs scale > 0", who);
-    if (a->hist_indptr) {
-        FR_CHECK_ARG(a->hist_len >= 0 && (a->hist_items || a->hist_len == 0), "%s: history CSR without items", who);
-        FR_CHECK_ARG(a->hist_sorted == 1, "%s: the history CSR must be ascending within each user (hist_sorted = 1)", who);
-    }
+    return check_hist_csr(a->hist_indptr, a->hist_items, a->hist_len, a->hist_sorted, who);
+}
+
+static int rec_check(const fr_rec_args* a, const char* who) {
+    int rc;
+    if ((rc = eval_check(a, who))) return rc;
+    FR_CHECK_ARG(a->k >= 1 && a->k <= FR_TOPK_MAX && a->k <= a->n_items, "%s: k %d not in 1..min(%d, n_items)", who, a->k,
+                 FR_TOPK_MAX);
     FR_CHECK_ARG(a->slices >= 0, "%s: slices < 0", who);
     return FR_OK;
+}
+
+// the kernels' share of the arguments
+static void rec_fill(RecArgs& p, const fr_rec_args* a) {
+    p.X = a->X;
+    p.W = a->W;
+    p.ub = a->user_bias;
+    p.ib = a->item_bias;
+    p.indptr = reinterpret_cast<const long long*>(a->hist_indptr);
+    p.hist = reinterpret_cast<const long long*>(a->hist_items);
+    p.U = a->n_users;
+    p.N = a->n_items;
+    p.hist_len = a->hist_indptr ? a->hist_len : 0;
+    p.D = a->dim;
+    p.epi = a->epilogue;
+    p.mask_pad = a->mask_pad ? 1 : 0;
+    p.bias0 = a->bias0;
+    p.scale = a->scale;
 }
 
 static int rec_plan(const fr_rec_args* a, long long* slice_len) {
@@ -531,28 +623,20 @@ constexpr int MR_C = 128;                    // thresholds of a user in LDS per 
 constexpr uint32_t MR_SKIP = 0xffffffffu;    // a key that is no positive (listed twice, or outside the matrix): above every cell
 constexpr uint32_t MR_NAN = 0xfffffffeu;     // a NaN positive: above every cell as well, and counted
 
-struct CellK {
-    const float* X;
-    const float* W;
-    const float* ub;
-    const float* ib;
-    const long long* indptr;
-    const long long* hist;
+struct CellK : RecArgs {
     const long long* cu;      // the cells: (cu[c], ci[c]) -> score[c] ...
     const long long* ci;
     const long long* keys;    // ... or the sorted keys user * N + item -> tb[c] = the score's image in the order (MR_SKIP, MR_NAN)
     float* score;
     uint32_t* tb;
     uint32_t* err;
-    long long U, N, hist_len, n;
-    int D, epi, mask_pad;
-    float bias0, scale;
+    long long n;
 };
 
-// A wave scores 32 cells: the MFMA chain of recommend_kernel over the cells' 32 user rows and 32 item rows, read from memory
-// as they lie (column 2s + (l >> 5) of step s, zero beyond D: the same ceil(D / 2) steps), of which cell c is the diagonal
-// element (c, c) -- register (c & 3) + 4 (c >> 3) of the lane c + 32 ((c >> 2) & 1).  The bias adds, the exact epilogue and the
-// mask follow as recommend_kernel and recommend_mask_kernel apply them.
+// A wave scores 32 cells: the chain of the score tile over the cells' 32 user rows and 32 item rows, read from memory as they
+// lie (column 2s + (l >> 5) of link s, zero beyond D: the same ceil(D / 2) links), of which cell c is the diagonal element
+// (c, c) -- the register r of lane c or c + 32 with rec_user_of(r, h) = c.  cell_score and the mask (as recommend_mask_kernel
+// applies it) follow.
 __global__ __launch_bounds__(256) void recommend_cells_kernel(CellK a) {
     const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
     const long long c = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 + li;
@@ -593,57 +677,40 @@ __global__ __launch_bounds__(256) void recommend_cells_kernel(CellK a) {
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if (s0 + j < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[j], wb[j], acc, 0, 0, 0);
+            if (s0 + j < steps) acc = rec_link(xa[j], wb[j], acc);
     }
-    const int rsel = (li & 3) + 4 * (li >> 3);
     float x = 0.f;
+    bool diag = false;      // one lane of each pair (l, l + 32) holds the diagonal
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-        if (r == rsel) x = acc[r];
-    if (!in || h != ((li >> 2) & 1)) return;
+    for (int r = 0; r < 16; ++r) {
+        if (rec_user_of(r, h) == li) {
+            x = acc[r];
+            diag = true;
+        }
+    }
+    if (!in || !diag) return;
     if (skip) {
         if (a.keys) a.tb[c] = MR_SKIP;
         else a.score[c] = __uint_as_float(0x7fc00000u);
         return;
     }
-    if (a.ub) x = x + a.ub[u];
-    if (a.ib) x = x + a.ib[it];
-    x = x + a.bias0;
-    x = epilogue_exact(x, a.epi, a.scale);
+    x = cell_score(a, x, a.ub ? a.ub[u] : 0.f, a.ib ? a.ib[it] : 0.f);
     bool masked = a.mask_pad && it == 0;
     if (!masked && a.indptr) {
-        long long p = a.indptr[u], q = a.indptr[u + 1];
-        p = p < 0 ? 0 : p;
-        q = q > a.hist_len ? a.hist_len : q;
-        while (p < q) {
-            const long long m = (p + q) >> 1;
-            const long long v = a.hist[m];
-            if (v == it) {
-                masked = true;
-                break;
-            }
-            if (v < it) p = m + 1;
-            else q = m;
-        }
+        long long p, q;
+        hist_range(a.indptr, a.hist_len, u, p, q);
+        masked = hist_has(a.hist, p, q, it);
     }
     if (masked) x = -INFINITY;
     if (a.keys) a.tb[c] = x != x ? MR_NAN : order_bits(x);
     else a.score[c] = x;
 }
 
-struct MrK {
-    const float* X;
-    const float* W;
-    const float* ub;
-    const float* ib;
-    const long long* indptr;
-    const long long* hist;
+struct MrK : RecArgs {
     const long long* keys;
     const uint32_t* tb;
     u64* out;
-    long long U, N, hist_len, slice_len, n_pos;
-    int D, epi, mask_pad;
-    float bias0, scale;
+    long long slice_len, n_pos;
 };
 
 // out[u] = { positives, 0, positives } of user u (a thread each): the `+ 1` of every positive's rank, and pos_len
@@ -668,8 +735,8 @@ __global__ __launch_bounds__(256) void recommend_meanrank_init_kernel(const long
     out[u * 3 + 2] = n;
 }
 
-// Workgroup (tile of 32 users, slice of the items), tiled, staged and multiplied as recommend_kernel, so that a cell counted here
-// has the bits of the cell ranked there.  Every cell gets the exact epilogue and the mask: the pad item, and a bit per (user,
+// Workgroup (tile of 32 users, slice of the items) on the score tile of recommend_kernel: a cell counted here is the cell
+// ranked there.  Every cell gets its exact score (cell_score) and the mask: the pad item, and a bit per (user,
 // item of the step) set from the users' ascending histories, which 8 threads per user walk along with the steps (the next 8
 // entries of a user wait in registers; a step without history loads nothing).  A live cell (not masked, above -inf) adds 1 to
 // user_len.  The scores of the user's positives (recommend_cells_kernel's images in the order) are its thresholds, up to MR_C
@@ -681,7 +748,7 @@ __global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
     const int li = lane & 31, h = lane >> 5;
-    const int D = a.D, Dx = (D + 1) | 1, epi = a.epi;
+    const int Dx = (a.D + 1) | 1;
     u64* sum = reinterpret_cast<u64*>(smem);                      // [32]
     long long* hp = reinterpret_cast<long long*>(sum + REC_UT);   // [32], [32]: the users' history inside the slice
     long long* hq = hp + REC_UT;
@@ -702,32 +769,13 @@ __global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
     const long long hi = lo + a.slice_len < a.N ? lo + a.slice_len : a.N;
     const bool hist = a.indptr != nullptr;
 
-    for (int e = tid; e < REC_UT * Dx; e += 256) {
-        const int u = e / Dx, c = e - u * Dx;
-        Xs[e] = (c < D && u0 + u < a.U) ? a.X[(size_t)(u0 + u) * D + c] : 0.f;
-    }
+    rec_load_users(a, u0, Xs, ubs, tid);
     if (tid < REC_UT) {
         sum[tid] = 0ull;
         ulen[tid] = 0;
-        ubs[tid] = (a.ub && u0 + tid < a.U) ? a.ub[u0 + tid] : 0.f;
     }
-    if (tid < 2 * REC_UT) {      // lower bounds of the slice's two ends in each user's history
-        const int u = tid >> 1;
-        const long long bound = (tid & 1) ? hi : lo;
-        long long p = 0, q = 0;
-        if (hist && u0 + u < a.U) {
-            p = a.indptr[u0 + u];
-            q = a.indptr[u0 + u + 1];
-            p = p < 0 ? 0 : p;
-            q = q > a.hist_len ? a.hist_len : q;
-            while (p < q) {
-                const long long m = (p + q) >> 1;
-                if (a.hist[m] < bound) p = m + 1;
-                else q = m;
-            }
-        }
-        ((tid & 1) ? hq : hp)[u] = p;
-    } else if (tid < 4 * REC_UT) {      // the users' ranges of the sorted keys
+    rec_slice_history(a, u0, lo, hi, hp, hq, tid);
+    if (tid >= 2 * REC_UT && tid < 4 * REC_UT) {      // the users' ranges of the sorted keys
         const int u = (tid - 2 * REC_UT) >> 1;
         long long p = 0, q = 0;
         if (u0 + u < a.U) {
@@ -748,15 +796,7 @@ __global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
     const int gu = tid >> 3, sub = tid & 7;      // history walk: 8 threads per user
     const long long hqg = hq[gu];
 
-    float pre[16];
-    auto fetch = [&](long long i0, int c0) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int e = tid + 256 * j, item = e >> 5, col = e & 31;
-            const long long it = i0 + item;
-            pre[j] = (it < hi && c0 + col < D) ? a.W[(size_t)it * D + c0 + col] : 0.f;
-        }
-    };
+    RecTile tile;
     for (long long pass = 0; pass < npass; ++pass) {
         for (int uu = wave; uu < REC_UT; uu += 4) {      // a wave sorts a user's thresholds of this pass by counting
             const long long base = pp[uu] + pass * MR_C, left = pq[uu] - base;
@@ -792,27 +832,19 @@ __global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
         }
         long long cur = hp[gu];
         long long hv = (hist && cur + sub < hqg) ? a.hist[cur + sub] : 0x7fffffffffffffffLL;
-        if (lo < hi) fetch(lo, 0);
+        if (lo < hi) tile.fetch(a, lo, hi, 0, tid);
         __syncthreads();
         for (long long i0 = lo; i0 < hi; i0 += REC_IB) {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             const long long item = i0 + wave * 32 + li;
             const bool ok = item < hi;
             const float ibv = (a.ib && ok) ? a.ib[item] : 0.f;
-            for (int c0 = 0; c0 < D; c0 += REC_DK) {
-                __syncthreads();      // the image is free, and so are the history bits of the step before
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int e = tid + 256 * j;
-                    Ws[(e >> 5) * REC_WST + (e & 31)] = pre[j];
-                }
-                if (hist && c0 == 0 && tid < REC_UT * 4) mbits[tid] = 0u;
-                __syncthreads();
-                if (c0 + REC_DK < D) fetch(i0, c0 + REC_DK);
-                else if (i0 + REC_IB < hi) fetch(i0 + REC_IB, 0);
-                if (hist && c0 == 0) {      // the users' history entries inside [i0, i0 + 128): ascending, so a prefix of the 8 waiting
+            const f32x16 acc = tile.step(
+                a, Xs, Ws, i0, hi, tid,
+                [&] {      // (behind the step's first barrier the history bits of the step before are free)
+                    if (hist && tid < REC_UT * 4) mbits[tid] = 0u;
+                },
+                [&] {      // the users' history entries inside [i0, i0 + 128): ascending, so a prefix of the 8 waiting
+                    if (!hist) return;
                     const long long end = i0 + REC_IB;
                     for (;;) {
                         const bool hit = hv < end;
@@ -825,13 +857,7 @@ __global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
                             hv = cur + sub < hqg ? a.hist[cur + sub] : 0x7fffffffffffffffLL;
                         }
                     }
-                }
-                const int left = (D - c0 + 1) >> 1, steps = left < REC_DK / 2 ? left : REC_DK / 2;
-                const float* xp = Xs + li * Dx + c0 + h;
-                const float* wp = Ws + (wave * 32 + li) * REC_WST + h;
-                for (int s = 0; s < steps; ++s)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xp[2 * s], wp[2 * s], acc, 0, 0, 0);
-            }
+                });
             if (hist) __syncthreads();      // the history bits are set
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
@@ -839,12 +865,8 @@ __global__ __launch_bounds__(256, 2) void recommend_meanrank_kernel(MrK a) {
 #pragma unroll
                 for (int rr = 0; rr < 8; ++rr) {
                     const int r = half * 8 + rr;
-                    const int ur = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    float x = acc[r];
-                    if (a.ub) x = x + ubs[ur];
-                    if (a.ib) x = x + ibv;
-                    x = x + a.bias0;
-                    x = epilogue_exact(x, epi, a.scale);
+                    const int ur = rec_user_of(r, h);
+                    const float x = cell_score(a, acc[r], ubs[ur], ibv);
                     bool alive = ok && u0 + ur < a.U && x > -INFINITY;      // (a NaN is no live cell)
                     if (a.mask_pad && item == 0) alive = false;
                     if (hist && ((mbits[ur * 4 + wave] >> li) & 1u)) alive = false;
@@ -902,48 +924,28 @@ static size_t mr_lds_bytes(int D) {
            4 * REC_STG * (4 + 2);
 }
 
-// The arguments fr_recommend_cells / fr_recommend_meanrank read of an fr_rec_args (k, slices and scores_out are not theirs)
-static int eval_check(const fr_rec_args* a, const char* who) {
-    FR_CHECK_ARG(a, "%s: null argument struct", who);
-    FR_CHECK_ARG(a->X && a->W, "%s: null X or W", who);
-    FR_CHECK_ARG(a->n_users >= 0 && a->n_users <= 0x7fffffffLL && a->n_items >= 1 && a->n_items <= 0x7fffffffLL,
-                 "%s: bad n_users / n_items", who);
-    FR_CHECK_ARG(a->dim >= 1 && a->dim <= 256, "%s: dim %d not in 1..256", who, a->dim);
-    FR_CHECK_ARG(a->epilogue >= 0 && a->epilogue <= 2, "%s: unknown epilogue %d", who, a->epilogue);
-    FR_CHECK_ARG(a->epilogue != 1 || a->scale > 0.f, "%s: epilogue 1 needs scale > 0", who);
-    if (a->hist_indptr) {
-        FR_CHECK_ARG(a->hist_len >= 0 && (a->hist_items || a->hist_len == 0), "%s: history CSR without items", who);
-        FR_CHECK_ARG(a->hist_sorted == 1, "%s: the history CSR must be ascending within each user (hist_sorted = 1)", who);
-    }
-    return FR_OK;
-}
-
 static int launch_cells(const fr_rec_args* a, const long long* cu, const long long* ci, const long long* keys, long long n,
                         float* score, uint32_t* tb, uint32_t* err, hipStream_t stream) {
     CellK p;
-    p.X = a->X;
-    p.W = a->W;
-    p.ub = a->user_bias;
-    p.ib = a->item_bias;
-    p.indptr = reinterpret_cast<const long long*>(a->hist_indptr);
-    p.hist = reinterpret_cast<const long long*>(a->hist_items);
+    rec_fill(p, a);
     p.cu = cu;
     p.ci = ci;
     p.keys = keys;
     p.score = score;
     p.tb = tb;
     p.err = err;
-    p.U = a->n_users;
-    p.N = a->n_items;
-    p.hist_len = a->hist_indptr ? a->hist_len : 0;
     p.n = n;
-    p.D = a->dim;
-    p.epi = a->epilogue;
-    p.mask_pad = a->mask_pad ? 1 : 0;
-    p.bias0 = a->bias0;
-    p.scale = a->scale;
     ProfScope prof(K_REC_CELLS, stream);
     FR_LAUNCH(prof, recommend_cells_kernel, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, stream, p);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+int launch_score_mask(float* scores, long long U, long long N, long long ld, const long long* indptr, const long long* hist,
+                      long long hist_len, int mask_pad, hipStream_t stream) {
+    ProfScope prof(K_TOPK_ROWS, stream);
+    FR_LAUNCH(prof, recommend_mask_kernel, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, stream, scores, indptr, hist,
+              indptr ? hist_len : 0LL, U, N, ld, mask_pad ? 1 : 0);
     FR_CHECK_LAUNCH();
     return FR_OK;
 }
@@ -974,26 +976,13 @@ extern "C" int fr_recommend_topk(const fr_rec_args* a, float* val_out, int64_t* 
     if (a->n_users == 0) return FR_OK;
     hipStream_t stream = (hipStream_t)stream_;
     RecK p;
-    p.X = a->X;
-    p.W = a->W;
-    p.ub = a->user_bias;
-    p.ib = a->item_bias;
-    p.indptr = reinterpret_cast<const long long*>(a->hist_indptr);
-    p.hist = reinterpret_cast<const long long*>(a->hist_items);
+    rec_fill(p, a);
     p.scores = a->scores_out;
     p.ws = static_cast<u64*>(ws);
-    p.U = a->n_users;
-    p.N = a->n_items;
-    p.hist_len = a->hist_indptr ? a->hist_len : 0;
     p.slice_len = len;
-    p.D = a->dim;
     p.k = a->k;
-    p.epi = a->epilogue;
-    p.mask_pad = a->mask_pad ? 1 : 0;
     p.S = S;
     p.cap = rec_cap(a->dim, a->k);
-    p.bias0 = a->bias0;
-    p.scale = a->scale;
     p.inv_scale = a->epilogue == 1 ? 1.0f / a->scale : 1.0f;
     const size_t ldsb = rec_lds_bytes(p.D, p.cap);
     static size_t have = 0;
@@ -1008,12 +997,10 @@ extern "C" int fr_recommend_topk(const fr_rec_args* a, float* val_out, int64_t* 
     prof_work(K_RECOMMEND, 2.0 * (double)a->n_users * (double)a->n_items * a->dim);
     FR_LAUNCH(prof, recommend_kernel, dim3((unsigned)tiles, (unsigned)S), dim3(256), ldsb, stream, p);
     FR_CHECK_LAUNCH();
+    if (a->scores_out && (a->mask_pad || a->hist_indptr) &&
+        (rc = launch_score_mask(a->scores_out, p.U, p.N, p.N, p.indptr, p.hist, p.hist_len, p.mask_pad, stream)))
+        return rc;
     ProfScope prof2(K_TOPK_ROWS, stream);
-    if (a->scores_out && (a->mask_pad || a->hist_indptr)) {
-        FR_LAUNCH(prof2, recommend_mask_kernel, dim3((unsigned)((a->n_users + 3) / 4)), dim3(256), 0, stream, a->scores_out,
-                  p.indptr, p.hist, p.hist_len, p.U, p.N, p.mask_pad);
-        FR_CHECK_LAUNCH();
-    }
     FR_LAUNCH(prof2, topk_merge_kernel, dim3((unsigned)a->n_users), dim3(256), (size_t)S * a->k * sizeof(u64), stream,
               (const u64*)p.ws, S, (int)a->k, (const float*)nullptr, 0LL, val_out, reinterpret_cast<long long*>(idx_out));
     FR_CHECK_LAUNCH();
@@ -1056,25 +1043,12 @@ extern "C" int fr_recommend_meanrank(const fr_rec_args* a, const int64_t* pos_ke
     const long long* keys = reinterpret_cast<const long long*>(pos_keys);
     if (n_pos > 0 && (rc = launch_cells(a, nullptr, nullptr, keys, n_pos, nullptr, tb, err_flag, stream))) return rc;
     MrK p;
-    p.X = a->X;
-    p.W = a->W;
-    p.ub = a->user_bias;
-    p.ib = a->item_bias;
-    p.indptr = reinterpret_cast<const long long*>(a->hist_indptr);
-    p.hist = reinterpret_cast<const long long*>(a->hist_items);
+    rec_fill(p, a);
     p.keys = keys;
     p.tb = tb;
     p.out = reinterpret_cast<u64*>(out);
-    p.U = a->n_users;
-    p.N = a->n_items;
-    p.hist_len = a->hist_indptr ? a->hist_len : 0;
     p.slice_len = len;
     p.n_pos = n_pos;
-    p.D = a->dim;
-    p.epi = a->epilogue;
-    p.mask_pad = a->mask_pad ? 1 : 0;
-    p.bias0 = a->bias0;
-    p.scale = a->scale;
     const size_t ldsb = mr_lds_bytes(p.D);
     static size_t have = 0;
     if (ldsb > have) {
