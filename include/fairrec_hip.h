@@ -979,9 +979,26 @@ FR_API int fr_randperm(uint32_t* state, int64_t n, int64_t* out, void* ws, size_
  *                               |logf(a) - logf(b)| over the pairs of table entries; a pair whose difference is NaN (the
  *                               logarithm of a non-positive entry, i.e. a negative score sum) does not enter the maximum
  *                               and the result stays finite (numpy's maximum in the reference's formula gives NaN there)
+ *   fr_df_cells               : DifferentialFairness for ANY number of groups, out[0] (double) = what fr_group_sums +
+ *                               fr_fair_metrics_from_stats give in out[4], without an [items, groups] table: memory is
+ *                               O(members + items).  Positions j in [item_start[k], item_start[k+1]) are the members of
+ *                               item k, member b = perm[j] (perm = NULL: identity); group[b] (int32) and value[b] (float)
+ *                               are indexed by member.  Inside an item's range the members must be SORTED by group, or at
+ *                               least the members of one group contiguous (a run): the caller's sort of the key
+ *                               item * n_groups + group gives that; a group split into two runs counts as two cells.
+ *                               A run whose group index is outside [0, n_groups) forms no cell.  Per run: s = sum of
+ *                               value in double, c = its members; table entry a = (float)((s + 1.0 / n_items) / (c + 1.0)).
+ *                               A group without a run in the item: the entry (float)(1.0 / n_items).  Per item: l =
+ *                               logf(a) over its entries, the absent entry once if fewer than n_groups groups have a run,
+ *                               NaN logarithms left out; d = lmax - lmin in float32, eps = d > 0 ? d : 0 -- the largest
+ *                               |logf(a) - logf(b)| over the pairs, as float32 subtraction is monotone, with the rule
+ *                               above for NaN pairs.  out[0] = mean over the n_items items of (double)eps.  n_groups == 1:
+ *                               exactly +0.0.  An empty item range has the absent entry only: eps = 0.
+ *                               1 <= n_items, 1 <= n_groups <= INT32_MAX; ws of fr_df_cells_workspace_bytes(n_items) bytes
+ *                               (0 for n_items < 1)
  * Double-precision sums in a fixed order: the same input gives the same bits on every call.  FR_EINVAL (null pointer, a
- * size below 1, n_groups outside 1..8, workspace below *_workspace_bytes) is returned before anything is launched or
- * written. */
+ * size below 1, n_groups outside 1..8 -- fr_df_cells: below 1 --, workspace below *_workspace_bytes) is returned before
+ * anything is launched or written. */
 /* fr_eval_hits: the `rec.topk` matrix of a batch of users (collector.py:146-154): rec_topk int32 [n_rows, k+1], entry
  * [u][j] = 1 if topk_idx[u][j] (the j-th ranked item id of row u) is a positive of row u, [u][k] = its number of
  * positives.  pos_keys = the sorted keys row * n_items + item of the batch's positives (no dense 0/1 matrix; may be NULL
@@ -1041,6 +1058,9 @@ FR_API int fr_group_sums(const int64_t* perm, const int64_t* seg_start, int64_t 
 FR_API size_t fr_fair_metrics_workspace_bytes(int64_t n_segments);
 FR_API int fr_fair_metrics_from_stats(const double* stats, int64_t n_segments, int32_t n_groups, double* out, void* ws,
                                       size_t ws_bytes, void* stream);
+FR_API size_t fr_df_cells_workspace_bytes(int64_t n_items);
+FR_API int fr_df_cells(const int64_t* perm, const int64_t* item_start, int64_t n_items, const int32_t* group,
+                       const float* value, int32_t n_groups, double* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- built-in profiler -------------------------------------------------------------------------------
  * When enabled every kernel launch of this library is bracketed by a hipEvent pair recorded on the

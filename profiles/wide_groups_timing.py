@@ -1,0 +1,125 @@
+"""Times the DifferentialFairness part of fairrec.evaluator.fairness_metrics at catalogue scale, split into index work and
+kernels: the cell walk (fr_df_cells, G > 8) and, for context, the dense table path (fr_group_sums + fr_fair_metrics_from_stats,
+G <= 8) on the same positives.
+
+    python profiles/wide_groups_timing.py [--positives 10000000] [--items 100001] [--groups 21 294 8]
+
+Positives: item ids Zipf-distributed (probability of the r-th most popular item ~ 1 / r) over ids 1 .. items - 1, group
+indices uniform, scores uniform in [0, 1), all from one seeded generator.  Device events around each part, 5 warm calls, then
+the median of 20.  Prints one JSON line per G.  The steps are the wrapper's own (fairrec/evaluator/metrics.py `_df_wide` /
+`_group_sums` + `_from_stats`), restated here so that an event can stand between them; the script checks that the restated
+steps return the wrapper's result bit for bit before it times anything.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "recbole-fairrec_amd"))
+
+from fairrec import _C                                        # noqa: E402
+from fairrec.evaluator import metrics as M                    # noqa: E402
+
+
+def positives(n, n_items, G, seed=0):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    w = 1.0 / torch.arange(1, n_items, dtype=torch.float64, device="cuda")
+    cdf = torch.cumsum(w / w.sum(), 0)
+    items = torch.searchsorted(cdf, torch.rand(n, generator=g, device="cuda", dtype=torch.float64)).clamp_(max=n_items - 2) + 1
+    group = torch.randint(0, G, (n,), generator=g, device="cuda", dtype=torch.int32)
+    score = torch.rand(n, generator=g, device="cuda")
+    return items, group, score
+
+
+def wide_parts(items, gidx, value, G):
+    lib, dev = _C.lib(), value.device
+
+    def index():
+        skey, perm = torch.sort(items.to(torch.int64) * G + gidx.to(torch.int64), stable=True)
+        item_of = torch.div(skey, G, rounding_mode='floor')
+        _, counts = torch.unique_consecutive(item_of, return_counts=True)
+        K = counts.numel()
+        item_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=item_start[1:])
+        return K, item_start, (skey - item_of * G).to(torch.int32), value[perm].contiguous()
+
+    def kernel(K, item_start, group, val):
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.fr_df_cells_workspace_bytes(K), dtype=torch.uint8, device=dev)
+        _C.check(lib.fr_df_cells(0, item_start.data_ptr(), K, group.data_ptr(), val.data_ptr(), G, out.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _C.current_stream()), "fr_df_cells")
+        return out
+
+    return index, kernel, lambda: M._df_wide(items, gidx, value, G)
+
+
+def dense_parts(items, gidx, value, G):
+    lib, dev = _C.lib(), value.device
+
+    def index():
+        keys, perm = torch.sort(items, stable=True)
+        _, counts = torch.unique_consecutive(keys, return_counts=True)
+        K = counts.numel()
+        seg_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=seg_start[1:])
+        return K, seg_start, perm
+
+    def kernel(K, seg_start, perm):
+        stats = torch.empty((K, G, 3), dtype=torch.float64, device=dev)
+        _C.check(lib.fr_group_sums(perm.data_ptr(), seg_start.data_ptr(), K, gidx.data_ptr(), value.data_ptr(), 0, G,
+                                   stats.data_ptr(), _C.current_stream()), "fr_group_sums")
+        out = torch.empty(5, dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.fr_fair_metrics_workspace_bytes(K), dtype=torch.uint8, device=dev)
+        _C.check(lib.fr_fair_metrics_from_stats(stats.data_ptr(), K, G, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _C.current_stream()), "fr_fair_metrics_from_stats")
+        return out[4:]
+
+    def wrapper():
+        st, K = M._group_sums(items, gidx, value, None, G)
+        return float(M._from_stats(st, K, G)[4])
+
+    return index, kernel, wrapper
+
+
+def timed(index, kernel, warm=5, reps=20):
+    ms = {"index": [], "kernel": []}
+    for r in range(warm + reps):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        args = index()
+        e[1].record()
+        out = kernel(*args)
+        e[2].record()
+        torch.cuda.synchronize()
+        if r >= warm:
+            ms["index"].append(e[0].elapsed_time(e[1]))
+            ms["kernel"].append(e[1].elapsed_time(e[2]))
+    total = [a + b for a, b in zip(ms["index"], ms["kernel"])]
+    return {"index_ms": statistics.median(ms["index"]), "kernel_ms": statistics.median(ms["kernel"]),
+            "total_ms": statistics.median(total), "total_ms_min_max": [min(total), max(total)]}, args[0], float(out.cpu()[0])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--positives", type=int, default=10_000_000)
+    ap.add_argument("--items", type=int, default=100_001)
+    ap.add_argument("--groups", type=int, nargs="+", default=[21, 294, 8])
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    for G in a.groups:
+        items, gidx, score = positives(a.positives, a.items, G)
+        path = "cells (fr_df_cells)" if G > M.NARROW_GROUPS else "dense (fr_group_sums + fr_fair_metrics_from_stats)"
+        index, kernel, wrapper = (wide_parts if G > M.NARROW_GROUPS else dense_parts)(items, gidx, score, G)
+        t, K, value = timed(index, kernel)
+        assert value == wrapper(), "the restated steps are not the wrapper's"
+        most = int(torch.bincount(items).max())
+        print(json.dumps({"G": G, "path": path, "positives": a.positives, "distinct_items": K, "most_popular_item": most,
+                          "differential_fairness": value, **t}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -7,6 +7,8 @@
 //                            fairness term (16 lanes per segment, fixed order)
 //   fair_from_stats_kernel   Value / Absolute / Under / Over unfairness (:972-979 and siblings) and DifferentialFairness
 //                            (:1337-1342, float32 tables like the reference) as means over the items
+//   df_cells_kernel          DifferentialFairness for any number of groups from the members sorted by (item, group): the
+//                            same table entries and the same epsilon, without the [items, groups] table
 // All sums are double precision in a fixed order (bit-reproducible).
 //
 // Edges the reference leaves to chance, as they are pinned here (tests/test_metrics_kernels_hip.py, DESIGN.md "Evaluation
@@ -202,6 +204,128 @@ __global__ __launch_bounds__(256) void fair_from_stats_kernel(const double* __re
     if (threadIdx.x < 5) {
         const int q = threadIdx.x;
         part[(size_t)blockIdx.x * 5 + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+// ---- DifferentialFairness for any number of groups: a walk over the sorted (item, group) cells, no items x groups table ----------
+// 16 lanes per item (as group_sums_kernel), 16 consecutive members of the item's range per trip.  PRECONDITION: inside an
+// item's range the members of one group are contiguous (a run).  A run's sum is a segmented inclusive scan in double over
+// the trip's 16 lanes (four __shfl_up steps, each taken only from a lane of the same run) plus the carry of the run left
+// open by the trip before; the lane of the run's LAST member finishes the cell: entry, logf, the lane's running maximum and
+// minimum of the logarithms, its count of runs.  Order of a cell's additions, for L members: at most four scan additions
+// inside a trip, then one per further trip the run reaches into -- at most floor((L + 14) / 16) of them, since a run may
+// start anywhere in a trip: every member passes through at most 4 + floor((L + 14) / 16) additions.
+// part[block] = sum of the block's 16 epsilons in sub-group order.
+// Loads run DF_AHEAD trips ahead of the scan (a popular item is one long chain of trips for its 16 lanes: the chain should
+// wait for memory once per DF_AHEAD trips, not once per trip); the order of the additions does not depend on it.
+static constexpr int DF_GROUP = 16, DF_THREADS = 256, DF_AHEAD = 4;
+
+struct DfWalk {
+    float lmax, lmin;                 // over the logarithms of this lane's finished cells
+    long long runs;                   // cells this lane finished
+    double carry_s;                   // the run open at the end of the trip before: its sum, its members, its group
+    long long carry_c;
+    int carry_g;
+};
+
+// one trip: member j = base + sub of the range [j0, j1) with group g and value v (anything where j >= j1); g_after: the
+// sub-group's lane 0 holds the group of the first member of the NEXT trip
+__device__ __forceinline__ void df_trip(DfWalk& w, long long j, long long j0, long long j1, int sub, int lane0, int g, float v,
+                                        int g_after, int G, double alpha) {
+    const bool have = j < j1;
+    const int g_up = __shfl_up(g, 1, DF_GROUP), g_down = __shfl_down(g, 1, DF_GROUP), g_next = __shfl(g_after, 0, DF_GROUP);
+    const bool head = have && (j == j0 || (sub == 0 ? w.carry_g : g_up) != g);
+    const bool tail = have && (j + 1 >= j1 || (sub == DF_GROUP - 1 ? g_next : g_down) != g);
+    const unsigned heads = (unsigned)(__ballot(head) >> lane0) & 0xffffu;
+    const unsigned upto = heads & ((2u << sub) - 1u);            // the heads at or before this lane
+    const int dist = upto ? sub - (31 - __clz(upto)) : sub;       // members of this lane's run before it in this trip
+    double s = have ? (double)v : 0.0;
+#pragma unroll
+    for (int o = 1; o < DF_GROUP; o <<= 1) {
+        const double t = __shfl_up(s, o, DF_GROUP);
+        if (dist >= o) s += t;
+    }
+    long long c = dist + 1;
+    if (!upto) {                      // no head up to here: the run came in from the trip before
+        s = w.carry_s + s;
+        c += w.carry_c;
+    }
+    if (tail && g >= 0 && g < G) {
+        const float l = logf((float)((s + alpha) / ((double)c + 1.0)));
+        if (l == l) {                 // a NaN logarithm (a non-positive entry) is left out
+            w.lmax = fmaxf(w.lmax, l);
+            w.lmin = fminf(w.lmin, l);
+        }
+        ++w.runs;
+    }
+    w.carry_s = __shfl(s, DF_GROUP - 1, DF_GROUP);
+    w.carry_c = __shfl(c, DF_GROUP - 1, DF_GROUP);
+    w.carry_g = __shfl(g, DF_GROUP - 1, DF_GROUP);
+}
+
+__global__ __launch_bounds__(DF_THREADS) void df_cells_kernel(const int64_t* __restrict__ perm,
+                                                              const int64_t* __restrict__ item_start, long long K,
+                                                              const int32_t* __restrict__ group,
+                                                              const float* __restrict__ value, int G,
+                                                              double* __restrict__ part) {
+    const int sub = threadIdx.x & (DF_GROUP - 1), sg = threadIdx.x / DF_GROUP;
+    const int lane0 = threadIdx.x & 63 & ~(DF_GROUP - 1);        // the sub-group's first lane in its wave
+    const long long k = (long long)blockIdx.x * (DF_THREADS / DF_GROUP) + sg;
+    const bool live = k < K;          // (no early exit: every thread reaches the block's fold below)
+    const long long j0 = live ? item_start[k] : 0, j1 = live ? item_start[k + 1] : 0;
+    const double alpha = 1.0 / (double)K;
+    DfWalk w = {-INFINITY, INFINITY, 0, 0.0, 0, 0};
+    int g[DF_AHEAD], gn[DF_AHEAD];
+    float v[DF_AHEAD], vn[DF_AHEAD];
+    // a position past the range reads the range's last member instead (no branch around a load; df_trip ignores it)
+    if (j0 < j1) {
+#pragma unroll
+        for (int q = 0; q < DF_AHEAD; ++q) {
+            const long long j = j0 + q * DF_GROUP + sub, jc = j < j1 ? j : j1 - 1, b = perm ? perm[jc] : jc;
+            g[q] = group[b];
+            v[q] = value[b];
+        }
+    }
+    for (long long base = j0; base < j1; base += DF_AHEAD * DF_GROUP) {   // (the bounds are the sub-group's: its 16 lanes stay together)
+#pragma unroll
+        for (int q = 0; q < DF_AHEAD; ++q) {          // the next DF_AHEAD trips, in flight during the scans of these
+            const long long j = base + (DF_AHEAD + q) * DF_GROUP + sub, jc = j < j1 ? j : j1 - 1, b = perm ? perm[jc] : jc;
+            gn[q] = group[b];
+            vn[q] = value[b];
+        }
+#pragma unroll
+        for (int q = 0; q < DF_AHEAD; ++q) {
+            const long long trip = base + q * DF_GROUP;
+            if (trip < j1) df_trip(w, trip + sub, j0, j1, sub, lane0, g[q], v[q], q + 1 < DF_AHEAD ? g[q + 1] : gn[0], G, alpha);
+        }
+#pragma unroll
+        for (int q = 0; q < DF_AHEAD; ++q) {
+            g[q] = gn[q];
+            v[q] = vn[q];
+        }
+    }
+    float lmax = w.lmax, lmin = w.lmin;
+    long long runs = w.runs;
+#pragma unroll
+    for (int o = DF_GROUP / 2; o > 0; o >>= 1) {
+        lmax = fmaxf(lmax, __shfl_xor(lmax, o, 64));
+        lmin = fminf(lmin, __shfl_xor(lmin, o, 64));
+        runs += __shfl_xor(runs, o, 64);
+    }
+    if (runs < G) {                   // a group without a run: the entry (0 + 1 / K) / (0 + 1), once
+        const float l = logf((float)alpha);
+        lmax = fmaxf(lmax, l);
+        lmin = fminf(lmin, l);
+    }
+    const float d = lmax - lmin;      // = the largest |log a - log b| over the pairs: float32 subtraction is monotone
+    __shared__ double red[DF_THREADS / DF_GROUP];
+    if (sub == 0) red[sg] = live && d > 0.f ? (double)d : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0;
+#pragma unroll
+        for (int q = 0; q < DF_THREADS / DF_GROUP; ++q) a += red[q];
+        part[blockIdx.x] = a;
     }
 }
 
@@ -656,6 +780,31 @@ extern "C" int fr_fair_metrics_from_stats(const double* stats, int64_t n_segment
     FR_CHECK_LAUNCH();
     hipLaunchKernelGGL(column_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, blocks, 5,
                        1.0 / (double)n_segments, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+// workspace of fr_df_cells: one double per block of 16 items
+extern "C" size_t fr_df_cells_workspace_bytes(int64_t n_items) {
+    const long long per_block = DF_THREADS / DF_GROUP;
+    return n_items < 1 ? 0 : (size_t)((n_items + per_block - 1) / per_block) * sizeof(double);
+}
+
+extern "C" int fr_df_cells(const int64_t* perm, const int64_t* item_start, int64_t n_items, const int32_t* group,
+                           const float* value, int32_t n_groups, double* out, void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    FR_CHECK_ARG(item_start && group && value && out && ws, "fr_df_cells: null pointer");
+    FR_CHECK_ARG(n_items >= 1 && n_groups >= 1, "fr_df_cells: n_items >= 1 and n_groups >= 1 (got %lld, %d)",
+                 (long long)n_items, (int)n_groups);
+    FR_CHECK_ARG(ws_bytes >= fr_df_cells_workspace_bytes(n_items), "fr_df_cells: workspace too small");
+    const long long per_block = DF_THREADS / DF_GROUP;
+    const long long blocks = (n_items + per_block - 1) / per_block;
+    FR_CHECK_ARG(blocks <= 0x7fffffffLL, "fr_df_cells: %lld items are more than one launch takes", (long long)n_items);
+    ProfScope prof(K_DF_CELLS, stream);
+    FR_LAUNCH(prof, df_cells_kernel, dim3((unsigned)blocks), dim3(DF_THREADS), 0, stream, perm, item_start, (long long)n_items,
+              group, value, (int)n_groups, (double*)ws);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(column_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, blocks, 1, 1.0 / (double)n_items, out);
     FR_CHECK_LAUNCH();
     return FR_OK;
 }

@@ -191,6 +191,8 @@ _PROTOS = {
     "fr_group_sums": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "fr_fair_metrics_workspace_bytes": (c_size_t, [c_int64]),
     "fr_fair_metrics_from_stats": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_df_cells_workspace_bytes": (c_size_t, [c_int64]),
+    "fr_df_cells": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_value_metrics_workspace_bytes": (c_size_t, [c_int64]),
     "fr_value_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_auc_sorted_workspace_bytes": (c_size_t, [c_int64]),

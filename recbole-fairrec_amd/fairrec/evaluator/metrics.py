@@ -8,7 +8,8 @@ Inputs are the arrays the reference's Collector gathers (collector.py:131-205), 
   neg_score, neg_i                        (uni100-style modes) the first len(pos) negatives of the batch order
   sst[<name>]                             the user's attribute value per positive pair
 The torch ops here are index plumbing (sort / unique of the id columns); every reduction is a HIP kernel
-(csrc/metrics.hip: fr_topk_metrics, fr_group_sums, fr_fair_metrics_from_stats).
+(csrc/metrics.hip: fr_topk_metrics, fr_group_sums, fr_fair_metrics_from_stats; fr_df_cells for an attribute, or an
+intersection of attributes (`sst_intersections`), with more than eight values).
 
 `eval_args.mode: labeled` is evaluation by value: 'auc', 'logloss', 'mae', 'rmse' of `rec.score` (what `predict` returned)
 against `data.label` (LABEL_FIELD), every row of the evaluation set (fr_value_metrics, fr_auc_sorted).  'gauc' is a ranking
@@ -74,17 +75,48 @@ def _from_stats(stats, K, G):
     return out.cpu()
 
 
-def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=None, neg_i=None, mode="full",
-                     value_type=True) -> Dict[str, float]:
-    """NonParity + DifferentialFairness per attribute; Value / Absolute / Under / Over unfairness on the FIRST attribute
-    (as the reference's classes read `sst_attr_list[0]`, metrics.py:905)."""
-    res = {}
-    pos_score = pos_score.to(torch.float32).contiguous()
-    first = True
-    for name, col in sst.items():
-        G, gidx = _group_index(col)
-        if G < 2:
-            raise ValueError(f'there is only one value for {name} sensitive attribute')
+NARROW_GROUPS = 8      # fr_group_sums / fr_fair_metrics_from_stats keep a segment's per-group sums in registers: n_groups <= 8
+
+
+def _group_means_wide(gidx, value, G):
+    """the G group means for G > NARROW_GROUPS, from fr_group_sums with the roles swapped: the GROUPS are its segments (a
+    stable argsort of the group index, the G + 1 group boundaries), every member sits in its one group 0."""
+    lib = _C.lib()
+    dev = value.device
+    perm = torch.sort(gidx, stable=True).indices
+    seg_start = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(gidx.to(torch.int64), minlength=G), 0, out=seg_start[1:])
+    zero = torch.zeros(value.numel(), dtype=torch.int32, device=dev)
+    stats = torch.empty((G, 1, 3), dtype=torch.float64, device=dev)
+    _C.check(lib.fr_group_sums(perm.data_ptr(), seg_start.data_ptr(), G, zero.data_ptr(), value.data_ptr(), 0, 1,
+                               stats.data_ptr(), _C.current_stream()), "fr_group_sums")
+    return (stats[:, 0, 0] / stats[:, 0, 1]).cpu()
+
+
+def _df_wide(items, gidx, value, G):
+    """DifferentialFairness for G > NARROW_GROUPS: ONE stable sort of the key item * G + group, the item boundaries from the
+    sorted keys, then fr_df_cells walks the (item, group) cells -- no [items, G] table.  The members are handed over in sorted
+    order (perm = NULL), so the walk reads its two columns front to back."""
+    lib = _C.lib()
+    dev = value.device
+    skey, perm = torch.sort(items.to(torch.int64) * G + gidx.to(torch.int64), stable=True)
+    item_of = torch.div(skey, G, rounding_mode='floor')
+    _, counts = torch.unique_consecutive(item_of, return_counts=True)
+    K = counts.numel()
+    item_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=item_start[1:])
+    group = (skey - item_of * G).to(torch.int32)
+    val = value[perm].contiguous()
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.fr_df_cells_workspace_bytes(K), dtype=torch.uint8, device=dev)
+    _C.check(lib.fr_df_cells(0, item_start.data_ptr(), K, group.data_ptr(), val.data_ptr(), G, out.data_ptr(), ws.data_ptr(),
+                             ws.numel(), _C.current_stream()), "fr_df_cells")
+    return float(out.cpu()[0])
+
+
+def _nonparity_and_df(res, name, G, gidx, pos_score, pos_i):
+    """the two metrics every attribute (and every intersection of attributes) gets; the path is chosen by G"""
+    if G <= NARROW_GROUPS:
         # NonParity (metrics.py:864-882): |difference| of the two group means, population std for more groups
         st, _ = _group_sums(None, gidx, pos_score, None, G)
         means = (st[0, :, 0] / st[0, :, 1]).cpu()
@@ -92,6 +124,28 @@ def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=N
             (means[0] - means[1]).abs() if G == 2 else means.std(unbiased=False))
         st, K = _group_sums(pos_i, gidx, pos_score, None, G)
         res[f'Differential Fairness of sensitive attribute {name}'] = float(_from_stats(st, K, G)[4])
+    else:
+        means = _group_means_wide(gidx, pos_score, G)
+        res[f'NonParity Unfairness of sensitive attribute {name}'] = float(means.std(unbiased=False))
+        res[f'Differential Fairness of sensitive attribute {name}'] = _df_wide(pos_i, gidx, pos_score, G)
+
+
+def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=None, neg_i=None, mode="full",
+                     value_type=True, intersections=None) -> Dict[str, float]:
+    """NonParity + DifferentialFairness per attribute, any number of values; Value / Absolute / Under / Over unfairness on the
+    FIRST attribute (as the reference's classes read `sst_attr_list[0]`, metrics.py:905), which has to be binary.
+    `intersections`: lists of attribute names out of `sst`; each adds NonParity + DifferentialFairness 'of sensitive attribute
+    a&b', whose groups are the distinct value tuples present among the rows."""
+    res = {}
+    pos_score = pos_score.to(torch.float32).contiguous()
+    first = True
+    index = {}
+    for name, col in sst.items():
+        G, gidx = _group_index(col)
+        index[name] = gidx
+        if G < 2:
+            raise ValueError(f'there is only one value for {name} sensitive attribute')
+        _nonparity_and_df(res, name, G, gidx, pos_score, pos_i)
         if first and value_type:
             if G != 2:
                 raise ValueError('sensitive attribute must be binary')
@@ -110,6 +164,10 @@ def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=N
             for q, label in enumerate(("Value", "Absolute", "Underestimation", "Overestimation")):
                 res[f'{label} Unfairness of sensitive attribute {name}'] = float(v[q])
         first = False
+    for names in intersections or ():
+        # equal tuples of group indices <=> equal tuples of values
+        tuples, inv = torch.unique(torch.stack([index[n].to(torch.int64) for n in names], dim=1), dim=0, return_inverse=True)
+        _nonparity_and_df(res, '&'.join(names), int(tuples.shape[0]), inv.to(torch.int32).contiguous(), pos_score, pos_i)
     return res
 
 
@@ -273,6 +331,24 @@ class Evaluator:
             raise ValueError(f"value metrics {value} need eval_args.mode 'labeled', not '{self.mode}'")
         if ranking and self.mode == 'labeled':
             raise ValueError(f"ranking metrics {ranking} need eval_args.mode full / uniN / popN, not 'labeled'")
+        self.intersections = self._intersections(config['sst_intersections'], list(config['sst_attr_list'] or []))
+
+    @staticmethod
+    def _intersections(entries, attrs):
+        """`sst_intersections`: a list of lists, each two or more distinct names out of `sst_attr_list`"""
+        if entries is None:
+            return []
+        if not isinstance(entries, (list, tuple)):
+            raise ValueError(f'sst_intersections must be a list of lists of attribute names, not {entries!r}')
+        for e in entries:
+            if not isinstance(e, (list, tuple)) or len(e) < 2 or not all(isinstance(n, str) for n in e):
+                raise ValueError(f'sst_intersections: {e!r} is not a list of two or more attribute names')
+            if len(set(e)) != len(e):
+                raise ValueError(f'sst_intersections: {e!r} names an attribute twice')
+            missing = [n for n in e if n not in attrs]
+            if missing:
+                raise ValueError(f'sst_intersections: {missing} not in sst_attr_list {attrs}')
+        return [list(e) for e in entries]
 
     def evaluate(self, collected: Dict[str, torch.Tensor]) -> Dict[str, float]:
         res = {}
@@ -300,10 +376,13 @@ class Evaluator:
                                        self.config['tail_ratio']))
         if self.FAIR & set(self.metrics):
             sst = {s: collected['data.' + s] for s in self.config['sst_attr_list']}
+            extra = {}
+            if self.intersections and {"nonparityunfairness", "differentialfairness"} & set(self.metrics):
+                extra['intersections'] = self.intersections
             fair = fairness_metrics(collected['rec.positive_score'], collected['data.positive_i'], sst,
                                     collected.get('rec.negative_score'), collected.get('data.negative_i'), self.mode,
                                     value_type=bool({"valueunfairness", "absoluteunfairness", "underunfairness",
-                                                     "overunfairness"} & set(self.metrics)))
+                                                     "overunfairness"} & set(self.metrics)), **extra)
             want = {"nonparityunfairness": "NonParity", "valueunfairness": "Value Unfairness",
                     "absoluteunfairness": "Absolute", "underunfairness": "Underestimation",
                     "overunfairness": "Overestimation", "differentialfairness": "Differential"}
