@@ -996,9 +996,32 @@ FR_API int fr_randperm(uint32_t* state, int64_t n, int64_t* out, void* ws, size_
  *                               exactly +0.0.  An empty item range has the absent entry only: eps = 0.
  *                               1 <= n_items, 1 <= n_groups <= INT32_MAX; ws of fr_df_cells_workspace_bytes(n_items) bytes
  *                               (0 for n_items < 1)
- * Double-precision sums in a fixed order: the same input gives the same bits on every call.  FR_EINVAL (null pointer, a
- * size below 1, n_groups outside 1..8 -- fr_df_cells: below 1 --, workspace below *_workspace_bytes) is returned before
- * anything is launched or written. */
+ *   fr_topk_metrics_grouped   : fr_topk_metrics per GROUP of users, groups as segments: the members of group g are the rows
+ *                               perm[group_start[g] .. group_start[g+1]) of rec_topk (perm int64 [n_users], NULL = identity;
+ *                               group_start int64 [n_groups + 1] on the device, ascending, [0] = 0, [n_groups] = n_users).
+ *                               out[g][6][k] = the mean over group g's members of the per-user terms fr_topk_metrics averages,
+ *                               rows in its order.  A group with a zero-positive row: Recall NaN in that group only (NDCG and
+ *                               MAP of the row 0, as above); an empty group: NaN everywhere.  Any n_groups >= 1.
+ *                               SUMMATION ORDER (a contract): group g's range is cut into chunks of 64 consecutive positions,
+ *                               lane = position within the chunk; a chunk is reduced by the xor butterfly (offsets 32, 16, ..,
+ *                               1); the chunk sums are added in ascending chunk order from 0.0; the result is multiplied by
+ *                               1.0 / (double)n_g.  With one group and the identity permutation (NULL or explicit) that is
+ *                               fr_topk_metrics' order and the two entries return the same bits.
+ *                               group_start and perm are clamped into [0, n_users]: a malformed table gives unspecified values
+ *                               and no access outside rec_topk.  ws: fr_topk_metrics_grouped_workspace_bytes(n_users, k,
+ *                               n_groups) bytes; the group sizes are never read on the host.
+ *   fr_gauc_grouped           : GAUC's sums per group from the `rec.meanrank` triples { 2 * pos_rank_sum, user_len, pos_len }
+ *                               (int64 [n_users][3]), groups as above.  A user without a positive (pos_len == 0) or without a
+ *                               negative (user_len == pos_len) is dropped; for the others auc_u = pair / ((user_len - pos_len)
+ *                               * pos_len), pair = (user_len + 1) * pos_len - pos_len * (pos_len + 1) / 2 - pos_rank_sum,
+ *                               integers up to the one division.  out[g] = { sum of auc_u * pos_len, sum of pos_len } (the
+ *                               caller divides; both 0 when every user of the group is dropped), kept[g] = { users kept,
+ *                               dropped for no positive, dropped for no negative }.  The chunks and the order of
+ *                               fr_topk_metrics_grouped, without the last multiplication.
+ * Double-precision sums in a fixed order, no floating-point atomics: the same input gives the same bits on every call.
+ * FR_EINVAL (null pointer -- other than a perm that may be NULL --, a size below 1, n_groups outside 1..8 -- fr_df_cells and
+ * the *_grouped entries: below 1 --, workspace below *_workspace_bytes) is returned before anything is launched or written;
+ * the *_workspace_bytes functions return 0 for arguments out of range. */
 /* fr_eval_hits: the `rec.topk` matrix of a batch of users (collector.py:146-154): rec_topk int32 [n_rows, k+1], entry
  * [u][j] = 1 if topk_idx[u][j] (the j-th ranked item id of row u) is a positive of row u, [u][k] = its number of
  * positives.  pos_keys = the sorted keys row * n_items + item of the batch's positives (no dense 0/1 matrix; may be NULL
@@ -1053,6 +1076,12 @@ FR_API int fr_eval_meanrank_segments(const int64_t* seg_start, int64_t n_users, 
 FR_API size_t fr_topk_metrics_workspace_bytes(int64_t n_users, int32_t k);
 FR_API int fr_topk_metrics(const int32_t* rec_topk, int64_t n_users, int32_t k, double* out, void* ws, size_t ws_bytes,
                            void* stream);
+FR_API size_t fr_topk_metrics_grouped_workspace_bytes(int64_t n_users, int32_t k, int64_t n_groups);
+FR_API int fr_topk_metrics_grouped(const int32_t* rec_topk, const int64_t* perm, const int64_t* group_start, int64_t n_users,
+                                   int32_t k, int64_t n_groups, double* out, void* ws, size_t ws_bytes, void* stream);
+FR_API size_t fr_gauc_grouped_workspace_bytes(int64_t n_users, int64_t n_groups);
+FR_API int fr_gauc_grouped(const int64_t* meanrank, const int64_t* perm, const int64_t* group_start, int64_t n_users,
+                           int64_t n_groups, double* out, int64_t* kept, void* ws, size_t ws_bytes, void* stream);
 FR_API int fr_group_sums(const int64_t* perm, const int64_t* seg_start, int64_t n_segments, const int32_t* group,
                          const float* value, const float* wtrue, int32_t n_groups, double* stats, void* stream);
 FR_API size_t fr_fair_metrics_workspace_bytes(int64_t n_segments);

@@ -2,6 +2,8 @@
 // round trip and without the reference's Python loops over interactions (:950-960) or over items x groups (:1331-1335).
 //
 //   topk_metrics_kernel      Hit / MRR / NDCG / Recall / Precision / MAP @ 1..K from the `rec.topk` matrix (:40-232)
+//   topk_grouped_kernel      the same six metrics per group of users (groups as segments of a permutation), and
+//   gauc_grouped_kernel      GAUC's two sums per group from `rec.meanrank`: a wave per chunk of 64 members, any number of groups
 //   group_sums_kernel        per (item segment, group): sum of scores, count, count of positives -- the tables every
 //                            fairness metric starts from (:948-970, :1322-1335); same segment machinery as the FOCF
 //                            fairness term (16 lanes per segment, fixed order)
@@ -32,20 +34,18 @@ __device__ __forceinline__ double wave_sum_d(double x) {
     return x;
 }
 
-// one wave per 64 users (lane = user); part[block][m][k], m = hit, mrr, ndcg, recall, precision, map
+// The per-user terms of the six top-k metrics of one wave of 64 rows and their butterfly sums: lane = one row of `rec_topk`
+// (row u; !ok: a lane without a row, every term 0), out[m][k] = wave sum, m = hit, mrr, ndcg, recall, precision, map.
 // A row with zero positives: NDCG 0 (divided by the ideal DCG of all K ranks, the reference's wrapped index), MAP 0,
-// Recall NaN (0 / 0, as the reference).
-__global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restrict__ rec_topk, long long U, int K,
-                                                          double* __restrict__ part) {
-    const int lane = threadIdx.x;
-    const long long u = (long long)blockIdx.x * 64 + lane;
-    const bool ok = u < U;
+// Recall NaN (0 / 0, as the reference).  Shared by topk_metrics_kernel (lane = user of the block) and
+// topk_grouped_kernel (lane = member of a group's chunk): the same terms, the same bits.
+__device__ __forceinline__ void topk_wave_terms(const int32_t* __restrict__ rec_topk, long long u, bool ok, int K, int lane,
+                                                double* __restrict__ out) {
     const int32_t* row = rec_topk + (ok ? u : 0) * (long long)(K + 1);
     const int pos_len = ok ? row[K] : 1;
     const int ilen = pos_len < K ? pos_len : K;
     int csum = 0;
     double first_rr = 0.0, dcg = 0.0, idcg = 0.0, sum_pre = 0.0;
-    double* out = part + (size_t)blockIdx.x * 6 * K;
     double idcg_all = 0.0;       // ilen <= 0 only: the ideal DCG of all K ranks
     if (ok && ilen <= 0)
         for (int k = 0; k < K; ++k) idcg_all += 1.0 / log2((double)(k + 2));
@@ -75,6 +75,169 @@ __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restr
             out[5 * K + k] = s5;
         }
     }
+}
+
+// one wave per 64 users (lane = user); part[block][m][k]
+__global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restrict__ rec_topk, long long U, int K,
+                                                          double* __restrict__ part) {
+    const int lane = threadIdx.x;
+    const long long u = (long long)blockIdx.x * 64 + lane;
+    topk_wave_terms(rec_topk, u, u < U, K, lane, part + (size_t)blockIdx.x * 6 * K);
+}
+
+// ---- the same metrics (and GAUC's sums) per group of users: groups as segments -----------------------------------------------
+// Group g's members are the rows perm[group_start[g] .. group_start[g+1]) (perm NULL: identity).  Its range is cut into chunks
+// of 64 consecutive positions; chunk_start[g] = number of chunks of the groups before g, so chunk c of group g is block
+// chunk_start[g] + c of the main grid, which has ceil(U / 64) + G blocks -- at least as many as there are chunks -- and finds
+// its (group, chunk) by binary search.  Everything read from group_start and perm is clamped into [0, U]: a malformed table gives
+// unspecified values, never an address outside the inputs or the workspace (chunk_start is clamped to the grid as well).
+__device__ __forceinline__ long long clamp_ll(long long x, long long lo, long long hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+__device__ __forceinline__ void group_range(const int64_t* __restrict__ group_start, long long g, long long U, long long& lo,
+                                            long long& hi) {
+    lo = clamp_ll(group_start[g], 0, U);
+    hi = clamp_ll(group_start[g + 1], lo, U);
+}
+
+static constexpr int CS_THREADS = 256;
+
+// chunk_start[0 .. G]: the exclusive scan of ceil(n_g / 64), by ONE block (a thread scans a contiguous run of groups)
+__global__ __launch_bounds__(CS_THREADS) void group_chunk_scan_kernel(const int64_t* __restrict__ group_start, long long G,
+                                                                      long long U, long long max_chunks,
+                                                                      long long* __restrict__ chunk_start) {
+    __shared__ long long tot[CS_THREADS];
+    const int t = threadIdx.x;
+    const long long per = (G + CS_THREADS - 1) / CS_THREADS;
+    const long long g0 = t * per < G ? t * per : G, g1 = g0 + per < G ? g0 + per : G;
+    long long mine = 0;
+    for (long long g = g0; g < g1; ++g) {
+        long long lo, hi;
+        group_range(group_start, g, U, lo, hi);
+        mine += (hi - lo + 63) / 64;
+    }
+    tot[t] = mine;
+    __syncthreads();
+    long long run = 0;
+    for (int s = 0; s < t; ++s) run += tot[s];
+    for (long long g = g0; g < g1; ++g) {
+        long long lo, hi;
+        group_range(group_start, g, U, lo, hi);
+        chunk_start[g] = run < max_chunks ? run : max_chunks;
+        run += (hi - lo + 63) / 64;
+    }
+    if (t == CS_THREADS - 1) chunk_start[G] = run < max_chunks ? run : max_chunks;
+}
+
+// the (group, chunk) of block b, or false: the last g with chunk_start[g] <= b (groups without a chunk share their
+// successor's entry and are passed over)
+__device__ __forceinline__ bool block_chunk(const long long* __restrict__ chunk_start, long long G, long long b, long long& g,
+                                            long long& c) {
+    if (b >= chunk_start[G]) return false;
+    long long lo = 0, hi = G;            // invariant: chunk_start[lo] <= b < chunk_start[hi]
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (chunk_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    g = lo;
+    c = b - chunk_start[lo];
+    return true;
+}
+
+// the row of lane `lane` of block b, or ok = false
+__device__ __forceinline__ long long chunk_member(const int64_t* __restrict__ perm, const int64_t* __restrict__ group_start,
+                                                  long long U, long long g, long long c, int lane, bool& ok) {
+    long long lo, hi;
+    group_range(group_start, g, U, lo, hi);
+    const long long j = lo + c * 64 + lane;
+    ok = j < hi;
+    if (!ok) return 0;
+    return perm ? clamp_ll(perm[j], 0, U - 1) : j;
+}
+
+// one wave per chunk (lane = position within the chunk); part[block][m][k] as topk_metrics_kernel
+__global__ __launch_bounds__(64) void topk_grouped_kernel(const int32_t* __restrict__ rec_topk,
+                                                          const int64_t* __restrict__ perm,
+                                                          const int64_t* __restrict__ group_start, long long U, int K,
+                                                          long long G, const long long* __restrict__ chunk_start,
+                                                          double* __restrict__ part) {
+    long long g, c;
+    if (!block_chunk(chunk_start, G, blockIdx.x, g, c)) return;
+    bool ok;
+    const long long u = chunk_member(perm, group_start, U, g, c, threadIdx.x, ok);
+    topk_wave_terms(rec_topk, u, ok, K, threadIdx.x, part + (size_t)blockIdx.x * 6 * K);
+}
+
+// out[g][j] = (sum over group g's chunks, in chunk order, of part[chunk][j]) * (1 / n_g)    j < n; an empty group: NaN
+__global__ __launch_bounds__(256) void group_fold_kernel(const double* __restrict__ part,
+                                                         const long long* __restrict__ chunk_start,
+                                                         const int64_t* __restrict__ group_start, long long U, long long G,
+                                                         int n, bool mean, double* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= G * n) return;
+    const long long g = t / n;
+    const int j = (int)(t % n);
+    long long lo, hi;
+    group_range(group_start, g, U, lo, hi);
+    double a = 0.0;
+    for (long long b = chunk_start[g]; b < chunk_start[g + 1]; ++b) a += part[b * n + j];
+    if (mean) a = hi > lo ? a * (1.0 / (double)(hi - lo)) : __longlong_as_double(0x7ff8000000000000LL);
+    out[t] = a;
+}
+
+__device__ __forceinline__ int wave_sum_i(int x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// GAUC's sums per chunk from the `rec.meanrank` triples { 2 * pos_rank_sum, user_len, pos_len }: a user with a positive and a
+// negative adds auc_u * pos_len and pos_len, auc_u = pair / ((user_len - pos_len) * pos_len) with pair = (user_len + 1) *
+// pos_len - pos_len * (pos_len + 1) / 2 - pos_rank_sum (evaluator.gauc); numerator and denominator are integers (both doubled),
+// so the one division rounds once.  part_d[block][2]; part_i[block][3] = users kept, without a positive, without a negative.
+__global__ __launch_bounds__(64) void gauc_grouped_kernel(const int64_t* __restrict__ meanrank,
+                                                          const int64_t* __restrict__ perm,
+                                                          const int64_t* __restrict__ group_start, long long U, long long G,
+                                                          const long long* __restrict__ chunk_start,
+                                                          double* __restrict__ part_d, long long* __restrict__ part_i) {
+    long long g, c;
+    if (!block_chunk(chunk_start, G, blockIdx.x, g, c)) return;
+    const int lane = threadIdx.x;
+    bool ok;
+    const long long u = chunk_member(perm, group_start, U, g, c, lane, ok);
+    const long long two_rank = ok ? meanrank[u * 3] : 0, user_len = ok ? meanrank[u * 3 + 1] : 0,
+                    pos_len = ok ? meanrank[u * 3 + 2] : 0;
+    const bool no_pos = ok && pos_len == 0, no_neg = ok && pos_len != 0 && user_len == pos_len;
+    const bool keep = ok && !no_pos && !no_neg;
+    double term = 0.0, weight = 0.0;
+    if (keep) {
+        const long long pair2 = 2 * (user_len + 1) * pos_len - pos_len * (pos_len + 1) - two_rank;
+        const double auc_u = (double)pair2 / (double)(2 * (user_len - pos_len) * pos_len);
+        weight = (double)pos_len;
+        term = auc_u * weight;
+    }
+    const double s0 = wave_sum_d(term), s1 = wave_sum_d(weight);
+    const int n0 = wave_sum_i(keep ? 1 : 0), n1 = wave_sum_i(no_pos ? 1 : 0), n2 = wave_sum_i(no_neg ? 1 : 0);
+    if (lane == 0) {
+        part_d[(size_t)blockIdx.x * 2] = s0;
+        part_d[(size_t)blockIdx.x * 2 + 1] = s1;
+        part_i[(size_t)blockIdx.x * 3] = n0;
+        part_i[(size_t)blockIdx.x * 3 + 1] = n1;
+        part_i[(size_t)blockIdx.x * 3 + 2] = n2;
+    }
+}
+
+// kept[g][q] = sum over group g's chunks of part_i[chunk][q]
+__global__ __launch_bounds__(256) void group_fold_counts_kernel(const long long* __restrict__ part_i,
+                                                                const long long* __restrict__ chunk_start, long long G,
+                                                                int64_t* __restrict__ kept) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= G * 3) return;
+    const long long g = t / 3;
+    const int q = (int)(t % 3);
+    long long a = 0;
+    for (long long b = chunk_start[g]; b < chunk_start[g + 1]; ++b) a += part_i[b * 3 + q];
+    kept[t] = a;
 }
 
 // rec_topk[u][k] = 1 if the k-th ranked item of row u is one of its positives, rec_topk[u][K] = number of positives of
@@ -717,6 +880,83 @@ extern "C" int fr_topk_metrics(const int32_t* rec_topk, int64_t n_users, int32_t
     FR_CHECK_LAUNCH();
     hipLaunchKernelGGL(column_sum_kernel, dim3((unsigned)((6 * k + 255) / 256)), dim3(256), 0, stream, (const double*)ws,
                        blocks, 6 * k, 1.0 / (double)n_users, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+// the main grid of the grouped entries: ceil(n_users / 64) + n_groups blocks, an upper bound on the chunks; 0 = out of range
+static long long grouped_blocks(int64_t n_users, int64_t n_groups) {
+    if (n_users < 1 || n_groups < 1 || n_groups > 0x7fffffffLL) return 0;
+    const long long blocks = (n_users + 63) / 64 + n_groups;
+    return blocks <= 0x7fffffffLL ? blocks : 0;
+}
+
+// workspace: part[blocks][6][k] doubles, then chunk_start[n_groups + 1]
+extern "C" size_t fr_topk_metrics_grouped_workspace_bytes(int64_t n_users, int32_t k, int64_t n_groups) {
+    const long long blocks = grouped_blocks(n_users, n_groups);
+    if (blocks == 0 || k < 1 || blocks > (1ll << 56) / (6ll * k)) return 0;      // (the partials alone would pass 2^59 bytes)
+    return ((size_t)blocks * 6 * k + (size_t)n_groups + 1) * 8;
+}
+
+extern "C" int fr_topk_metrics_grouped(const int32_t* rec_topk, const int64_t* perm, const int64_t* group_start, int64_t n_users,
+                                       int32_t k, int64_t n_groups, double* out, void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    FR_CHECK_ARG(rec_topk && group_start && out && ws, "fr_topk_metrics_grouped: null pointer");
+    FR_CHECK_ARG(n_users >= 1 && k >= 1 && n_groups >= 1, "fr_topk_metrics_grouped: n_users, k, n_groups >= 1 (got %lld, %d, %lld)",
+                 (long long)n_users, (int)k, (long long)n_groups);
+    const long long blocks = grouped_blocks(n_users, n_groups);
+    FR_CHECK_ARG(blocks > 0 && fr_topk_metrics_grouped_workspace_bytes(n_users, k, n_groups) != 0 &&
+                     (long long)n_groups <= 0x7fffffffLL * 256 / (6ll * k),
+                 "fr_topk_metrics_grouped: %lld users in %lld groups are more than one launch takes", (long long)n_users,
+                 (long long)n_groups);
+    FR_CHECK_ARG(ws_bytes >= fr_topk_metrics_grouped_workspace_bytes(n_users, k, n_groups),
+                 "fr_topk_metrics_grouped: workspace too small");
+    double* part = (double*)ws;
+    long long* chunk_start = (long long*)(part + (size_t)blocks * 6 * k);
+    hipLaunchKernelGGL(group_chunk_scan_kernel, dim3(1), dim3(CS_THREADS), 0, stream, group_start, (long long)n_groups,
+                       (long long)n_users, blocks, chunk_start);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(topk_grouped_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, rec_topk, perm, group_start,
+                       (long long)n_users, (int)k, (long long)n_groups, (const long long*)chunk_start, part);
+    FR_CHECK_LAUNCH();
+    const long long cells = (long long)n_groups * 6 * k;
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, (const double*)part,
+                       (const long long*)chunk_start, group_start, (long long)n_users, (long long)n_groups, 6 * (int)k, true, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+// workspace: part_d[blocks][2] doubles, part_i[blocks][3] int64, then chunk_start[n_groups + 1]
+extern "C" size_t fr_gauc_grouped_workspace_bytes(int64_t n_users, int64_t n_groups) {
+    const long long blocks = grouped_blocks(n_users, n_groups);
+    return blocks == 0 ? 0 : ((size_t)blocks * 5 + (size_t)n_groups + 1) * 8;
+}
+
+extern "C" int fr_gauc_grouped(const int64_t* meanrank, const int64_t* perm, const int64_t* group_start, int64_t n_users,
+                               int64_t n_groups, double* out, int64_t* kept, void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    FR_CHECK_ARG(meanrank && group_start && out && kept && ws, "fr_gauc_grouped: null pointer");
+    FR_CHECK_ARG(n_users >= 1 && n_groups >= 1, "fr_gauc_grouped: n_users, n_groups >= 1 (got %lld, %lld)", (long long)n_users,
+                 (long long)n_groups);
+    const long long blocks = grouped_blocks(n_users, n_groups);
+    FR_CHECK_ARG(blocks > 0, "fr_gauc_grouped: %lld users in %lld groups are more than one launch takes", (long long)n_users,
+                 (long long)n_groups);
+    FR_CHECK_ARG(ws_bytes >= fr_gauc_grouped_workspace_bytes(n_users, n_groups), "fr_gauc_grouped: workspace too small");
+    double* part_d = (double*)ws;
+    long long* part_i = (long long*)(part_d + (size_t)blocks * 2);
+    long long* chunk_start = part_i + (size_t)blocks * 3;
+    hipLaunchKernelGGL(group_chunk_scan_kernel, dim3(1), dim3(CS_THREADS), 0, stream, group_start, (long long)n_groups,
+                       (long long)n_users, blocks, chunk_start);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gauc_grouped_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, meanrank, perm, group_start,
+                       (long long)n_users, (long long)n_groups, (const long long*)chunk_start, part_d, part_i);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((n_groups * 2 + 255) / 256)), dim3(256), 0, stream,
+                       (const double*)part_d, (const long long*)chunk_start, group_start, (long long)n_users, (long long)n_groups,
+                       2, false, out);
+    FR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(group_fold_counts_kernel, dim3((unsigned)((n_groups * 3 + 255) / 256)), dim3(256), 0, stream,
+                       (const long long*)part_i, (const long long*)chunk_start, (long long)n_groups, kept);
     FR_CHECK_LAUNCH();
     return FR_OK;
 }

@@ -11,6 +11,9 @@ With 'gauc' among the metrics the three ranking branches also gather `rec.meanra
 tied rank is a half); without it they collect and launch what they did before.  `eval_args.mode: labeled` keeps `rec.score`
 and `data.label` per batch (eval_batch_collect_labeled).
 
+With `utility_by_group` set, every ranking branch also keeps `data.user.<attr>` -- the selected attributes, one value per row of
+`rec.topk` -- and the labeled branch `data.<attr>` per row; without the key the collected keys are what they were.
+
 `full_sort_eval: fused` feeds `eval_batch_collect_fused` the model's factors instead of the matrix (same keys, same values).
 """
 from __future__ import annotations
@@ -22,12 +25,28 @@ import torch
 from .. import _C
 
 
+def utility_attrs(value, attrs) -> List[str]:
+    """`utility_by_group`: None / False = off ([]), True = every attribute of `sst_attr_list`, a list of names = those, each out
+    of `sst_attr_list`."""
+    if value is None or value is False:
+        return []
+    if value is True:
+        return list(attrs)
+    if not isinstance(value, (list, tuple)) or not all(isinstance(n, str) for n in value):
+        raise ValueError(f'utility_by_group must be True or a list of attribute names out of sst_attr_list, not {value!r}')
+    strangers = [n for n in value if n not in attrs]
+    if strangers:
+        raise ValueError(f'utility_by_group: {strangers} not in sst_attr_list {list(attrs)}')
+    return list(dict.fromkeys(value))
+
+
 class Collector:
     def __init__(self, config):
         self.config = config
         topk = config['topk'] or [10]
         self.topk = [topk] if isinstance(topk, int) else list(topk)
         self.sst = list(config['sst_attr_list'] or [])
+        self.utility = utility_attrs(config['utility_by_group'], self.sst)     # attributes kept per USER (`data.user.<attr>`)
         self.full = 'full' in (config['eval_args'] or {}).get('mode', 'full')
         self.meanrank = 'gauc' in [m.lower() for m in (config['metrics'] or [])]
         self._parts: Dict[str, List[torch.Tensor]] = {}
@@ -58,11 +77,28 @@ class Collector:
                  "fr_topk_like_torch_cpu")
         return out
 
+    def _attr(self, interaction, name):
+        if name not in interaction:
+            raise ValueError(f"utility_by_group: the evaluation batches carry no column '{name}'")
+        return interaction[name]
+
+    def _add_user_attrs(self, interaction, dev, row_idx=None, n_users=None):
+        """`utility_by_group`: `data.user.<attr>`, one value per row of the batch's `rec.topk`.  `interaction` has one row per
+        user, or (row_idx given) one per candidate: every row of a user carries the user's value, scattered to its row."""
+        for s in self.utility:
+            col = self._attr(interaction, s).to(dev).reshape(-1)
+            if row_idx is not None:
+                col = torch.zeros(n_users, dtype=col.dtype, device=dev).index_put_((row_idx,), col)
+            self._add('data.user.' + s, col)
+
     def eval_batch_collect_labeled(self, scores: torch.Tensor, interaction):
-        """collector.py:176-181 (`rec.score`, `data.label`): the batch's predictions as they are and its LABEL_FIELD column."""
+        """collector.py:176-181 (`rec.score`, `data.label`): the batch's predictions as they are and its LABEL_FIELD column
+        (`utility_by_group`: and `data.<attr>` per row, which the labeled loader joins)."""
         scores = scores.reshape(-1)
         self._add('rec.score', scores.to(torch.float32))
         self._add('data.label', interaction[self.config['LABEL_FIELD']].to(scores.device, torch.float32).reshape(-1))
+        for s in self.utility:
+            self._add('data.' + s, self._attr(interaction, s).to(scores.device).reshape(-1))
 
     def _meanrank(self, seg, items, scores, pos_keys, n_items):
         """`rec.meanrank` of a batch: one launch, a wave per user (items None: dense rows); pos_keys = the sorted keys
@@ -105,6 +141,7 @@ class Collector:
         for s in self.sst:
             if s in interaction:
                 self._add('data.' + s, interaction[s].to(scores.device)[positive_u])
+        self._add_user_attrs(interaction, scores.device)
 
     def eval_batch_collect_fused(self, factors, interaction, hist_indptr: torch.Tensor, hist_items: torch.Tensor,
                                  positive_u: torch.Tensor, positive_i: torch.Tensor):
@@ -154,6 +191,7 @@ class Collector:
         for s in self.sst:
             if s in interaction:
                 self._add('data.' + s, interaction[s].to(dev)[positive_u])
+        self._add_user_attrs(interaction, dev)
 
     def check_device_errors(self):
         """Raises if a kernel of the fused path met an id outside its table (one host sync; the matrix path indexes with
@@ -179,6 +217,7 @@ class Collector:
         positive_u, positive_i = positive_u.to(dev, torch.int64), positive_i.to(dev, torch.int64)
         U = int(positive_u[-1].item()) + 1                                    # batch_user_num, trainer.py:453
         K = max(self.topk)
+        self._add_user_attrs(interaction, dev, row_idx, U)
         if K <= 62 and (row_idx.numel() < 2 or bool((row_idx[1:] >= row_idx[:-1]).all())):
             # The evaluation loaders emit a batch user by user: a user's candidates are a contiguous segment, and the whole
             # ranking is ONE launch, a wave per user (fr_eval_topk_segments); every lookup the reference makes in its dense

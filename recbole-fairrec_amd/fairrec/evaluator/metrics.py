@@ -11,6 +11,10 @@ The torch ops here are index plumbing (sort / unique of the id columns); every r
 (csrc/metrics.hip: fr_topk_metrics, fr_group_sums, fr_fair_metrics_from_stats; fr_df_cells for an attribute, or an
 intersection of attributes (`sst_intersections`), with more than eight values).
 
+`utility_by_group` (off by default) adds the ranking and value metrics per group of a sensitive attribute or intersection,
+'<m> of <A>=<value>', and their '<m> gap | std | min of sensitive attribute <A>': group_topk_metrics (fr_topk_metrics_grouped),
+group_gauc (fr_gauc_grouped), group_value_metrics (the value kernels on each group's slice of the rows sorted by group).
+
 `eval_args.mode: labeled` is evaluation by value: 'auc', 'logloss', 'mae', 'rmse' of `rec.score` (what `predict` returned)
 against `data.label` (LABEL_FIELD), every row of the evaluation set (fr_value_metrics, fr_auc_sorted).  'gauc' is a ranking
 metric: it reads `rec.meanrank` (fr_eval_meanrank_segments) in the full / uniN / popN modes.
@@ -302,6 +306,74 @@ def gauc(meanrank: torch.Tensor) -> float:
     return float((auc_u * pos_len).sum() / pos_len.sum())
 
 
+TOPK_NAMES = ("hit", "mrr", "ndcg", "recall", "precision", "map")
+
+
+def _group_segments(group_index: torch.Tensor, n_groups: int):
+    """groups as segments (the form of _group_means_wide): perm = a stable sort of the group index, group_start = the cumulative
+    bincount, both on the device"""
+    gidx = group_index.reshape(-1).to(torch.int64)
+    perm = torch.sort(gidx, stable=True).indices.contiguous()
+    start = torch.zeros(n_groups + 1, dtype=torch.int64, device=gidx.device)
+    torch.cumsum(torch.bincount(gidx, minlength=n_groups)[:n_groups], 0, out=start[1:])
+    return perm, start
+
+
+def group_topk_metrics(rec_topk: torch.Tensor, group_index: torch.Tensor, n_groups: int, topk: Iterable[int]):
+    """`topk_metrics` per group of users: {'<name>@<k>': [n_groups values]}.  group_index[u] in [0, n_groups) is the group of row
+    u of `rec_topk`; one launch chain for all groups (fr_topk_metrics_grouped), no host read of the group sizes."""
+    lib = _C.lib()
+    rec = rec_topk.to(torch.int32).contiguous()
+    U, K = rec.shape[0], rec.shape[1] - 1
+    if group_index.numel() != U:
+        raise ValueError(f'group_topk_metrics: {group_index.numel()} group indices for {U} rows')
+    perm, start = _group_segments(group_index, n_groups)
+    out = torch.empty(n_groups * 6 * K, dtype=torch.float64, device=rec.device)
+    ws = torch.empty(lib.fr_topk_metrics_grouped_workspace_bytes(U, K, n_groups), dtype=torch.uint8, device=rec.device)
+    _C.check(lib.fr_topk_metrics_grouped(rec.data_ptr(), perm.data_ptr(), start.data_ptr(), U, K, n_groups, out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _C.current_stream()), "fr_topk_metrics_grouped")
+    vals = out.view(n_groups, 6, K).cpu()
+    return {f"{name}@{k}": [float(vals[g, m, k - 1]) for g in range(n_groups)] for m, name in enumerate(TOPK_NAMES) for k in topk}
+
+
+def group_gauc(meanrank: torch.Tensor, group_index: torch.Tensor, n_groups: int):
+    """`gauc` per group of users from `rec.meanrank`: [n_groups values], NaN for a group whose users are all dropped
+    (fr_gauc_grouped: the two sums per group on the device, the one quotient in float64 on the host)."""
+    lib = _C.lib()
+    mr = meanrank.to(torch.int64).contiguous()
+    U = mr.shape[0]
+    if group_index.numel() != U:
+        raise ValueError(f'group_gauc: {group_index.numel()} group indices for {U} rows')
+    perm, start = _group_segments(group_index, n_groups)
+    out = torch.empty((n_groups, 2), dtype=torch.float64, device=mr.device)
+    kept = torch.empty((n_groups, 3), dtype=torch.int64, device=mr.device)
+    ws = torch.empty(lib.fr_gauc_grouped_workspace_bytes(U, n_groups), dtype=torch.uint8, device=mr.device)
+    _C.check(lib.fr_gauc_grouped(mr.data_ptr(), perm.data_ptr(), start.data_ptr(), U, n_groups, out.data_ptr(), kept.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _C.current_stream()), "fr_gauc_grouped")
+    return [s / w if w > 0 else float('nan') for s, w in out.cpu().tolist()]
+
+
+def group_value_metrics(score: torch.Tensor, label: torch.Tensor, group_index: torch.Tensor, n_groups: int, names: Iterable[str]):
+    """`value_metrics` per group of rows: {'<name>': [n_groups values]}.  The rows are sorted by group once; every group's
+    contiguous slice goes through the kernels of `value_metrics`.  A group with one label class: AUC NaN; an empty group: NaN."""
+    names = [n.lower() for n in names]
+    score, label = score.reshape(-1), label.reshape(-1)
+    perm, start = _group_segments(group_index, n_groups)
+    score, label = score[perm], label[perm]
+    bounds = start.cpu().tolist()
+    res = {n: [] for n in names}
+    for g in range(n_groups):
+        lo, hi = bounds[g], bounds[g + 1]
+        one = value_metrics(score[lo:hi], label[lo:hi], names) if hi > lo else {n: float('nan') for n in names}
+        for n in names:
+            res[n].append(one[n])
+    return res
+
+
+def _value_name(v: float) -> str:
+    return str(int(v)) if float(v).is_integer() else repr(float(v))
+
+
 class Evaluator:
     """recbole/evaluator/evaluator.py: metric names from `config['metrics']` -> one result dict."""
 
@@ -332,6 +404,8 @@ class Evaluator:
         if ranking and self.mode == 'labeled':
             raise ValueError(f"ranking metrics {ranking} need eval_args.mode full / uniN / popN, not 'labeled'")
         self.intersections = self._intersections(config['sst_intersections'], list(config['sst_attr_list'] or []))
+        from .collector import utility_attrs
+        self.utility = utility_attrs(config['utility_by_group'], list(config['sst_attr_list'] or []))
 
     @staticmethod
     def _intersections(entries, attrs):
@@ -389,4 +463,48 @@ class Evaluator:
             for k, v in fair.items():
                 if any(k.startswith(p) for m, p in want.items() if m in self.metrics):
                     res[k] = v
+        if self.utility:
+            res.update(self._utility_by_group(collected))
         return {k: round(v, self.decimal_place) for k, v in res.items()}
+
+    def _utility_by_group(self, collected) -> Dict[str, float]:
+        """`utility_by_group`: every requested top-k / gauc / value metric per group of each selected attribute, and of each
+        `sst_intersections` entry whose attributes are all selected: '<m> of <A>=<value>' per group, '<m> gap | std | min of
+        sensitive attribute <A>' (max - min, population std, worst group; float64 on the host, NaN if a group is NaN)."""
+        import numpy as np
+        labeled = self.mode == 'labeled'
+        prefix = 'data.' if labeled else 'data.user.'
+        index, values, groups = {}, {}, []
+        for name in self.utility:
+            col = collected[prefix + name].reshape(-1)
+            vals, inv = torch.unique(col, sorted=True, return_inverse=True)
+            index[name], values[name] = inv.to(torch.int64), [_value_name(v) for v in vals.cpu().tolist()]
+            groups.append((name, inv, values[name]))
+        for names in self.intersections:
+            if all(n in index for n in names):
+                # equal tuples of group indices <=> equal tuples of values (as fairness_metrics)
+                tuples, inv = torch.unique(torch.stack([index[n] for n in names], dim=1), dim=0, return_inverse=True)
+                labels = ['&'.join(values[n][j] for n, j in zip(names, row)) for row in tuples.cpu().tolist()]
+                groups.append(('&'.join(names), inv, labels))
+        res = {}
+        for name, gidx, labels in groups:
+            G = len(labels)
+            if G < 2:
+                raise ValueError(f'there is only one value for {name} sensitive attribute')
+            by_group = {}
+            if labeled:
+                by_group.update(group_value_metrics(collected['rec.score'], collected['data.label'], gidx, G,
+                                                    [m for m in self.metrics if m in self.VALUE]))
+            if "gauc" in self.metrics:
+                by_group['gauc'] = group_gauc(collected['rec.meanrank'], gidx, G)
+            if self.TOPK & set(self.metrics):
+                allk = group_topk_metrics(collected['rec.topk'], gidx, G, self.topk)
+                by_group.update({k: v for k, v in allk.items() if k.split('@')[0] in self.metrics})
+            for m, per_group in by_group.items():
+                v = np.asarray(per_group, dtype=np.float64)
+                for label, x in zip(labels, per_group):
+                    res[f'{m} of {name}={label}'] = float(x)
+                res[f'{m} gap of sensitive attribute {name}'] = float(v.max() - v.min())
+                res[f'{m} std of sensitive attribute {name}'] = float(v.std())
+                res[f'{m} min of sensitive attribute {name}'] = float(v.min())
+        return res
