@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <initializer_list>
 
 #include "common.hpp"
 #include "kernels.hpp"
@@ -370,6 +371,31 @@ using namespace fr;
 
 static inline int act_ok(int act) { return act >= ACT_NONE && act <= ACT_TANH; }
 
+// FAIRREC_LINEAR_NO_GLDS / FAIRREC_LINEAR_SLOW (read once per process): the LDS-DMA forms of mlp_glds.hip are switched off
+static bool lds_dma_off() {
+    static const bool off = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr || getenv("FAIRREC_LINEAR_SLOW") != nullptr;
+    return off;
+}
+
+static inline bool aligned16(std::initializer_list<const void*> ptrs) {      // a null pointer counts as aligned
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    return (bits & 15) == 0;
+}
+
+// The fast form of the backward products (mlp_glds.hip: whole 32 x 32 tiles and 32-element reduction chunks, 16-byte rows):
+// the ONE statement of the rule for fr_linear_bwd_input, its three epilogue entries, fr_linear_bwd_weight and every job of
+// fr_linear_bwd_weight_multi.  `ptrs`: the operands the kernel reads or writes in 16-byte pieces.  The caller adds what is
+// its own (no mask, no activation left to differentiate).  fairrec/model/layers.py::_fast_form mirrors shape and alignment.
+static bool bwd_fast_form(int N, int K, int k0, std::initializer_list<const void*> ptrs) {
+    return !lds_dma_off() && N % 32 == 0 && K % 32 == 0 && k0 % 32 == 0 && aligned16(ptrs);
+}
+
+// ... and of the forward product, which clamps ragged column tiles: any N >= 8 (no mask: the caller's)
+static bool fwd_fast_form(int N, int K, int k0, std::initializer_list<const void*> ptrs) {
+    return !lds_dma_off() && N >= 8 && K % 32 == 0 && k0 % 32 == 0 && aligned16(ptrs);
+}
+
 // ---- layers with ONE output (the last layer of a scorer / discriminator: recbole/model/layers.py MLPLayers([..., 1])) ------
 // A [M, K] x [K] product is a row-wise dot: the matrix tiles above spend a 64 x 64 tile (and three launches in the backward
 // pass) on a single column.  16 lanes per row, one float4 each per 64 columns; K % 64 == 0, K <= 512.
@@ -487,8 +513,7 @@ extern "C" int fr_linear_fwd(const float* x0, int32_t k0, const float* x1, int32
     const bool aligned = K % 4 == 0 && k0 % 4 == 0 && k1 % 4 == 0 && ((uintptr_t)x0 & 15) == 0 && ((uintptr_t)W & 15) == 0 &&
                          (!x1 || ((uintptr_t)x1 & 15) == 0) && (!mask || ((uintptr_t)mask & 3) == 0);
     static const bool slow_only = getenv("FAIRREC_LINEAR_SLOW") != nullptr;
-    static const bool no_glds = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr;
-    if (aligned && !slow_only && !no_glds && !mask && K % 32 == 0 && k0 % 32 == 0 && N >= 8) {
+    if (!mask && fwd_fast_form(N, K, k0, {x0, x1, W})) {
         // LDS-DMA kernels (mlp_glds.hip): no dropout mask, 32-element reduction chunks
         return glds_linear_fwd(GlMat{x0, x1, k0, k1, k0}, W, bias, M, (int)N, K, (int)act, Y, stream);
     }
@@ -518,9 +543,7 @@ extern "C" int fr_linear_bwd_input(const float* dY, const float* Y, int32_t act,
     const int K = k0 + k1;
     prof_work(K_LINEAR_BWD_INPUT, 2.0 * (double)M * N * K);
     CatOut dX{dx0, dx1, k0, k1};
-    static const bool no_glds = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr || getenv("FAIRREC_LINEAR_SLOW") != nullptr;
-    if (!no_glds && !mask && act == ACT_NONE && N % 32 == 0 && K % 32 == 0 && k0 % 32 == 0 && ((uintptr_t)dY & 15) == 0 &&
-        ((uintptr_t)W & 15) == 0)
+    if (!mask && act == ACT_NONE && bwd_fast_form(N, K, k0, {dY, W}))
         return glds_linear_bwd_input(dY, W, M, (int)N, K, dx0, k0, dx1, k1, stream);
     ProfScope prof(K_LINEAR_BWD_INPUT, stream);
     FR_LAUNCH(prof, linear_bwd_input_kernel, dim3((unsigned)((M + TM - 1) / TM), (unsigned)((K + TN - 1) / TN)), dim3(256),
@@ -529,57 +552,54 @@ extern "C" int fr_linear_bwd_input(const float* dY, const float* Y, int32_t act,
     return FR_OK;
 }
 
+// What the three entries below share: they exist in the fast form only (one input block K wide) and refuse everything else
+// with FR_EUNSUPPORTED before anything is counted or launched -- the caller then takes fr_linear_bwd_input and the launches
+// the epilogue stood for.  `bnb` (fr_linear_bwd_input_bnstats) also needs dX in 16-byte rows, 32-row statistics chunks, the
+// macro-tile kernels and a BatchNorm apply launch that folds these partials itself (both switches are read per call).
+static int bwd_input_epilogue(const char* entry, const float* dY, const float* W, int64_t M, int32_t N, int32_t K, float* dX,
+                              void* stream, const float* src, float scale, int src_act, const GlBnb* bnb = nullptr) {
+    const bool ok = bwd_fast_form(N, K, K, {dY, W, bnb ? dX : nullptr}) &&
+                    (!bnb || (M <= 32768 && glds_shared_form() && getenv("FAIRREC_BN_FOLD_SEPARATE") == nullptr));
+    if (!ok) {
+        set_error("%s: not in the fast form (N %% 32 == 0, K %% 32 == 0, 16-byte aligned operands%s)", entry,
+                  bnb ? ", M <= 32768, macro-tile kernels, fold inside the apply launch" : "");
+        return FR_EUNSUPPORTED;
+    }
+    prof_work(K_LINEAR_BWD_INPUT, 2.0 * (double)M * N * K);
+    return glds_linear_bwd_input(dY, W, M, (int)N, (int)K, dX, (int)K, nullptr, 0, (hipStream_t)stream, src, scale, src_act, bnb);
+}
+
 // dA = (dY W) o scale o [Xd > 0]: the input gradient of a layer whose input Xd [M, K] is the previous layer's ReLU output
 // dropped in place, taken on through that ReLU in the epilogue (fr_linear_bwd_input + fr_act_bwd_dropped in one launch).
-// Fast form only: FR_EUNSUPPORTED unless N % 32 == 0, K % 32 == 0 and the operands are 16-byte aligned.
 extern "C" int fr_linear_bwd_input_relu(const float* dY, const float* W, int64_t M, int32_t N, int32_t K, const float* Xd,
                                         float scale, float* dA, void* stream_) {
     FR_CHECK_ARG(dY && W && Xd && dA && M >= 1 && N >= 1 && K >= 1 && scale > 0.f, "fr_linear_bwd_input_relu: bad argument");
-    prof_work(K_LINEAR_BWD_INPUT, 2.0 * (double)M * N * K);
-    static const bool no_glds = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr || getenv("FAIRREC_LINEAR_SLOW") != nullptr;
-    if (no_glds || N % 32 != 0 || K % 32 != 0 || (((uintptr_t)dY | (uintptr_t)W) & 15) != 0) {
-        set_error("fr_linear_bwd_input_relu: shape not supported (N %% 32 == 0, K %% 32 == 0, 16-byte aligned operands)");
-        return FR_EUNSUPPORTED;
-    }
-    return glds_linear_bwd_input(dY, W, M, (int)N, (int)K, dA, (int)K, nullptr, 0, (hipStream_t)stream_, Xd, scale);
+    return bwd_input_epilogue("fr_linear_bwd_input_relu", dY, W, M, N, K, dA, stream_, Xd, scale, 0);
 }
 
 // dA = (dY W) o act'(Yin): the input gradient of a layer whose input Yin [M, K] is the previous layer's activation output,
 // taken on through that activation in the epilogue (fr_linear_bwd_input + the next layer's fr_act_bwd in one launch: one
 // pass over an [M, K] tensor and one launch less per hidden layer of an MLP's backward pass; the product is rounded to
-// fp32 and then multiplied, exactly as the two launches do).  Fast form only, like fr_linear_bwd_input_relu.
+// fp32 and then multiplied, exactly as the two launches do).
 extern "C" int fr_linear_bwd_input_act(const float* dY, const float* W, int64_t M, int32_t N, int32_t K, const float* Yin,
                                        int32_t act, float* dA, void* stream_) {
     FR_CHECK_ARG(dY && W && Yin && dA && M >= 1 && N >= 1 && K >= 1 && act >= 1 && act <= 4, "fr_linear_bwd_input_act: bad argument");
-    prof_work(K_LINEAR_BWD_INPUT, 2.0 * (double)M * N * K);
-    static const bool no_glds = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr || getenv("FAIRREC_LINEAR_SLOW") != nullptr;
-    if (no_glds || N % 32 != 0 || K % 32 != 0 || (((uintptr_t)dY | (uintptr_t)W) & 15) != 0) {
-        set_error("fr_linear_bwd_input_act: shape not supported (N %% 32 == 0, K %% 32 == 0, 16-byte aligned operands)");
-        return FR_EUNSUPPORTED;
-    }
-    return glds_linear_bwd_input(dY, W, M, (int)N, (int)K, dA, (int)K, nullptr, 0, (hipStream_t)stream_, Yin, 1.f, (int)act);
+    return bwd_input_epilogue("fr_linear_bwd_input_act", dY, W, M, N, K, dA, stream_, Yin, 1.f, (int)act);
 }
 
 // dX = (dY W) o keep, stored, AND the backward statistics of the BatchNorm layer whose (dropped) output X is: per 32-row tile
 // and column sum dA and sum dA xhat (dA = dX o act'(Yb)) into bn_ws, exactly where fr_bn_bwd's statistics launch leaves its
 // per-chunk sums -- fr_bn_bwd_ex(have_stats = 1) then runs the apply launch alone.  One launch instead of three (product,
-// dropout, statistics) per BatchNorm layer of a backward pass.  p = 0: no dropout between the layers.  Fast form only
-// (N % 32 == 0, K % 32 == 0, aligned operands, the macro-tile kernels, M <= 32768): FR_EUNSUPPORTED otherwise.
+// dropout, statistics) per BatchNorm layer of a backward pass.  p = 0: no dropout between the layers.
 extern "C" int fr_linear_bwd_input_bnstats(const float* dY, const float* W, int64_t M, int32_t N, int32_t K, float* dX,
                                            const float* Yb, const float* xhat_b, int32_t act_b, void* bn_ws, size_t bn_ws_bytes,
                                            float p, uint64_t seed, uint64_t offset, const int64_t* used, void* stream_) {
     FR_CHECK_ARG(dY && W && dX && Yb && xhat_b && bn_ws && M >= 1 && N >= 1 && K >= 1 && act_ok(act_b) &&
                      bn_ws_bytes >= fr_bn_workspace_bytes(M, K), "fr_linear_bwd_input_bnstats: bad argument");
     FR_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || (used && offset % 4 == 0)), "fr_linear_bwd_input_bnstats: bad dropout arguments");
-    prof_work(K_LINEAR_BWD_INPUT, 2.0 * (double)M * N * K);
-    static const bool no_glds = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr || getenv("FAIRREC_LINEAR_SLOW") != nullptr;
-    if (no_glds || N % 32 != 0 || K % 32 != 0 || (((uintptr_t)dY | (uintptr_t)W | (uintptr_t)dX) & 15) != 0 || M > 32768) {
-        set_error("fr_linear_bwd_input_bnstats: shape not supported (N %% 32 == 0, K %% 32 == 0, 16-byte aligned operands, M <= 32768)");
-        return FR_EUNSUPPORTED;
-    }
     const GlBnb bnb{(float*)bn_ws, Yb, xhat_b, (int)act_b, p, (unsigned long long)seed, (unsigned long long)offset,
                     (const unsigned long long*)used};
-    return glds_linear_bwd_input(dY, W, M, (int)N, (int)K, dX, (int)K, nullptr, 0, (hipStream_t)stream_, nullptr, 1.f, 0, &bnb);
+    return bwd_input_epilogue("fr_linear_bwd_input_bnstats", dY, W, M, N, K, dX, stream_, nullptr, 1.f, 0, &bnb);
 }
 
 // row splits of the weight gradient (slab bounded by 64 MiB)
@@ -614,9 +634,7 @@ extern "C" int fr_linear_bwd_weight(const float* dY, const float* Y, int32_t act
     CatMat X{x0, x1, k0, k1};
     float* slab = (float*)ws;
     float* bslab = db ? slab + (size_t)splits * N * K : nullptr;
-    static const bool no_glds = getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr || getenv("FAIRREC_LINEAR_SLOW") != nullptr;
-    if (!no_glds && !mask && act == ACT_NONE && N % 32 == 0 && K % 32 == 0 && k0 % 32 == 0 && ((uintptr_t)dY & 15) == 0 &&
-        ((uintptr_t)x0 & 15) == 0 && (!x1 || ((uintptr_t)x1 & 15) == 0)) {
+    if (!mask && act == ACT_NONE && bwd_fast_form(N, K, k0, {dY, x0, x1})) {
         int rc = glds_linear_bwd_weight(dY, GlMat{x0, x1, k0, k1, k0}, M, (int)N, K, (int)splits, rows_per_split, slab, bslab,
                                         stream);
         if (rc) return rc;
@@ -635,7 +653,8 @@ extern "C" int fr_linear_bwd_weight(const float* dY, const float* Y, int32_t act
 }
 
 // The weight gradients of several layers of one backward pass in two launches (all the products, then all the slab sums)
-// instead of two per layer.  Jobs in the fast form only (N, K, k0 multiples of 32, no mask, dY already at the pre-activation);
+// instead of two per layer.  Jobs in the fast form only (bwd_fast_form, no mask, dY already at the pre-activation):
+// FR_EUNSUPPORTED otherwise, also with the LDS-DMA forms switched off -- the caller then takes fr_linear_bwd_weight job by job;
 // a job with dY == NULL only sums `n_parts` partial results [n_parts][N * K] that somebody else wrote (`parts`).
 extern "C" size_t fr_linear_bwd_weight_multi_workspace_bytes(const fr_wgrad_job* jobs, int32_t n, int64_t M) {
     size_t tot = 0;
@@ -661,9 +680,9 @@ extern "C" int fr_linear_bwd_weight_multi(const fr_wgrad_job* jobs, int32_t n, i
             q[j] = GlWJob{nullptr, GlMat{}, f.N, K, f.n_parts, 0, const_cast<float*>(f.parts), nullptr, f.dW, nullptr};
             continue;
         }
-        if (f.N % 32 || K % 32 || f.k0 % 32 || ((uintptr_t)f.dY & 15) || ((uintptr_t)f.x0 & 15) || (f.x1 && ((uintptr_t)f.x1 & 15)) ||
-            !f.x0 || (f.k1 > 0 && !f.x1)) {
-            set_error("fr_linear_bwd_weight_multi: job %d is not in the fast form (N, K, k0 multiples of 32, 16-byte aligned)", j);
+        if (!f.x0 || (f.k1 > 0 && !f.x1) || !bwd_fast_form(f.N, K, f.k0, {f.dY, f.x0, f.x1})) {
+            set_error("fr_linear_bwd_weight_multi: job %d is not in the fast form (N, K, k0 multiples of 32, 16-byte aligned, "
+                      "LDS-DMA forms not switched off)", j);
             return FR_EUNSUPPORTED;
         }
         const long long splits = bwd_weight_splits(M, f.N, K);
@@ -787,17 +806,120 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_stats_kernel(const float* _
     }
 }
 
-// Y = act(gamma * (Z - mean) / sqrt(var + eps) + beta); xhat and invstd are kept for the backward;
-// running_mean / running_var follow torch (momentum, unbiased variance).
-// fin[2n], fin[2n+1] = mean and 1/sqrt(var + eps) of column n; running statistics and invstd_out updated here.
-// Two passes over the chunk partials (count_c, mean_c, M2_c): mean = sum count_c mean_c / M, then
-// M2 = sum [M2_c + count_c (mean_c - mean)^2] -- the exact decomposition of the two-pass variance, as plain sums (four
-// waves take a quarter of the chunks each in ascending order, the quarters are added in order: a fixed tree).  A wave's
-// chain is a compensated sum (bn_sum_comp: what each addition rounds away is kept and added at the chain's end): in a plain
-// chain a chunk with an outlier (M2_c ~ 2^40) swallowed the terms behind it, each half a spacing of the running sum -- 1/std
-// of a [32768, N] column with one entry 2^20 came out 45 ulp off.  A chain of one or two chunks (M <= 256) keeps its bits: a
-// single addition has nothing to compensate.  The
+// ---- the folds: per-chunk partials -> column statistics ------------------------------------------------------------------------
+// Each fold is ONE device function, called by the fold kernel (FAIRREC_BN_FOLD_SEPARATE) and by the apply kernel that folds its
+// own columns (the default), so the two forms have the same bits by construction.  The four waves of a workgroup take a quarter
+// of the chunks each in ascending order, lane = column; the quarters are added in order (a fixed tree).
+//
+// BnQuarter: a wave's quarter of one column's partials.  A quarter of up to QMAX chunks is requested at once and kept in
+// registers: ONE memory latency in a fold, which is nothing but a latency chain (7.6 us at 256 chunks with the forward's two
+// passes loading eight at a time).  A longer quarter (HELD = false) is read as it is walked.  each(f) calls f(chunk, partial)
+// in ascending chunk order either way, so a fold writes its chain once, for both.
+constexpr int BN_QMAX = 64;
+__device__ __forceinline__ bool bn_quarter_held(int chunks) { return (chunks + BN_WAVES - 1) / BN_WAVES <= BN_QMAX; }
+
+template <bool HELD>
+struct BnQuarter {
+    const float2* part;         // the partial of (chunk c, column n) is part[c * N + n]
+    int N, nn, c0, c1;
+    float2 pv[HELD ? BN_QMAX : 1];
+    __device__ __forceinline__ BnQuarter(const float* __restrict__ part_, int chunks, int N_, int n)
+        : part(reinterpret_cast<const float2*>(part_)), N(N_), nn(n < N_ ? n : N_ - 1) {
+        const int q = (chunks + BN_WAVES - 1) / BN_WAVES;
+        c0 = (int)(threadIdx.x >> 6) * q;
+        c1 = min(chunks, c0 + q);
+        if constexpr (HELD) {
+#pragma unroll
+            for (int k = 0; k < BN_QMAX; ++k)
+                if (c0 + k < c1) pv[k] = part[(size_t)(c0 + k) * N + nn];
+        }
+    }
+    template <class F>
+    __device__ __forceinline__ void each(F&& f) const {
+        if constexpr (HELD) {
+#pragma unroll
+            for (int k = 0; k < BN_QMAX; ++k)
+                if (c0 + k < c1) f(c0 + k, pv[k]);
+        } else {
+#pragma unroll 8
+            for (int c = c0; c < c1; ++c) f(c, part[(size_t)c * N + nn]);
+        }
+    }
+};
+
+// Forward: (mean, M2) of column n from the chunk partials (mean_c, M2_c), valid in every wave; `sh` may be reused on return.
+// Two passes over the partials: mean = sum count_c mean_c / M, then M2 = sum [M2_c + count_c (mean_c - mean)^2] -- the exact
+// decomposition of the two-pass variance, as plain sums.  A wave's chain is a compensated sum (bn_sum_comp: what each
+// addition rounds away is kept and added at the chain's end): in a plain chain a chunk with an outlier (M2_c ~ 2^40) swallowed
+// the terms behind it, each half a spacing of the running sum -- 1/std of a [32768, N] column with one entry 2^20 came out 45
+// ulp off.  A chain of one or two chunks (M <= 256) keeps its bits: a single addition has nothing to compensate.  The
 // sequential Chan update it replaces was a chain of 2 divisions per chunk: 20 us for 256 chunks.
+template <bool HELD>
+__device__ __forceinline__ float2 bn_fold_stats_of(const float* __restrict__ part, int chunks, int M, int N, int rc, int n,
+                                                   float (*sh)[64]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const BnQuarter<HELD> Q(part, chunks, N, n);
+    const auto rows = [&](int c) { return (float)(min(M, (c + 1) * rc) - c * rc); };
+    float s = 0.f, m2 = 0.f, mc = 0.f;     // mc: what the additions into m2 rounded away
+    Q.each([&](int c, const float2& p) { s = fmaf(rows(c), p.x, s); });
+    sh[wave][lane] = s;
+    __syncthreads();
+    const float mean = (((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane]) / (float)M;
+    __syncthreads();
+    Q.each([&](int c, const float2& p) {
+        const float nb = rows(c);
+        const float d = p.x - mean;
+        bn_sum_comp(fmaf(nb * d, d, p.y), m2, mc);
+    });
+    sh[wave][lane] = m2 + mc;
+    __syncthreads();
+    m2 = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+    __syncthreads();
+    return make_float2(mean, m2);
+}
+__device__ __forceinline__ float2 bn_fold_stats_inline(const float* __restrict__ part, int chunks, int M, int N, int rc, int n,
+                                                       float (*sh)[64]) {
+    return bn_quarter_held(chunks) ? bn_fold_stats_of<true>(part, chunks, M, N, rc, n, sh)
+                                   : bn_fold_stats_of<false>(part, chunks, M, N, rc, n, sh);
+}
+
+// Backward: (sum dA, sum dA xhat) = (dbeta, dgamma) of column n from the chunk sums, valid in every wave (`sh` is not synchronised
+// again on return)
+template <bool HELD>
+__device__ __forceinline__ float2 bn_fold_sums_of(const float* __restrict__ part, int chunks, int N, int n, float (*sh)[2][64]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const BnQuarter<HELD> Q(part, chunks, N, n);
+    float sum_da = 0.f, sum_dax = 0.f;
+    Q.each([&](int, const float2& p) {
+        sum_da += p.x;
+        sum_dax += p.y;
+    });
+    sh[wave][0][lane] = sum_da;
+    sh[wave][1][lane] = sum_dax;
+    __syncthreads();
+    return make_float2(((sh[0][0][lane] + sh[1][0][lane]) + sh[2][0][lane]) + sh[3][0][lane],
+                       ((sh[0][1][lane] + sh[1][1][lane]) + sh[2][1][lane]) + sh[3][1][lane]);
+}
+__device__ __forceinline__ float2 bn_fold_sums_inline(const float* __restrict__ part, int chunks, int N, int n, float (*sh)[2][64]) {
+    return bn_quarter_held(chunks) ? bn_fold_sums_of<true>(part, chunks, N, n, sh) : bn_fold_sums_of<false>(part, chunks, N, n, sh);
+}
+
+// 1/sqrt(var + eps) of a column with the folded sum of squared deviations M2
+__device__ __forceinline__ float bn_invstd(float m2, int M, float eps) { return 1.f / sqrtf(m2 / (float)M + eps); }
+
+// What a forward pass leaves behind once per column: invstd for the backward and the running statistics as torch updates them
+// (momentum, unbiased variance).  st = the folded (mean, M2)
+__device__ __forceinline__ void bn_fwd_leave(float2 st, float invstd, int M, float momentum, int n, float* __restrict__ rmean,
+                                             float* __restrict__ rvar, float* __restrict__ invstd_out) {
+    invstd_out[n] = invstd;
+    if (rmean) {
+        rmean[n] = bn_running(rmean[n], momentum, st.x);
+        rvar[n] = bn_running(rvar[n], momentum, M > 1 ? st.y / (float)(M - 1) : st.y / (float)M);
+    }
+}
+
+// Y = act(gamma * (Z - mean) / sqrt(var + eps) + beta); xhat and invstd are kept for the backward.
+// fin[2n], fin[2n+1] = mean and 1/sqrt(var + eps) of column n for the apply launch behind this one
 __global__ __launch_bounds__(BN_THREADS) void bn_fwd_fold_kernel(const float* __restrict__ part, int chunks, int M, int N, int rc,
                                                                  float eps, float momentum, float* __restrict__ rmean,
                                                                  float* __restrict__ rvar, float* __restrict__ fin,
@@ -806,68 +928,13 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_fold_kernel(const float* __
     __shared__ float sh[BN_WAVES][64];
     // num_batches_tracked += passes of this layer (layers.py's BatchNorm1d bookkeeping) rides here: no launch of its own
     if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += nbt_inc;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + lane;
-    const int q = (chunks + BN_WAVES - 1) / BN_WAVES, c0 = wave * q, c1 = min(chunks, c0 + q);
-    const bool ok = n < N;
-    // A quarter of up to 64 chunks is requested at once and kept in registers for both passes: ONE memory latency in this
-    // launch, which is nothing but a latency chain (7.6 us with the two passes loading eight at a time; same sums, same order).
-    constexpr int QMAX = 64;
-    const int nn = ok ? n : N - 1;
-    float s = 0.f, m2 = 0.f, mc = 0.f;     // mc: what the additions into m2 rounded away (bn_sum_comp)
-    if (q <= QMAX) {
-        float2 pv[QMAX];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) pv[k] = reinterpret_cast<const float2*>(part)[(size_t)(c0 + k) * N + nn];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) s = fmaf((float)(min(M, (c0 + k + 1) * rc) - (c0 + k) * rc), pv[k].x, s);
-        sh[wave][lane] = s;
-        __syncthreads();
-        const float mean_ = (((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane]) / (float)M;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) {
-                const float nb = (float)(min(M, (c0 + k + 1) * rc) - (c0 + k) * rc);
-                const float d = pv[k].x - mean_;
-                bn_sum_comp(fmaf(nb * d, d, pv[k].y), m2, mc);
-            }
-        s = mean_;
-    } else {
-#pragma unroll 8
-        for (int c = c0; c < c1; ++c) {
-            const float nb = (float)(min(M, (c + 1) * rc) - c * rc);
-            s = fmaf(nb, part[((size_t)c * N + nn) * 2], s);
-        }
-        sh[wave][lane] = s;
-        __syncthreads();
-        const float mean_ = (((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane]) / (float)M;
-        __syncthreads();
-#pragma unroll 8
-        for (int c = c0; c < c1; ++c) {
-            const float nb = (float)(min(M, (c + 1) * rc) - c * rc);
-            const float2 p = reinterpret_cast<const float2*>(part)[(size_t)c * N + nn];
-            const float d = p.x - mean_;
-            bn_sum_comp(fmaf(nb * d, d, p.y), m2, mc);
-        }
-        s = mean_;
-    }
-    const float mean = s;
-    sh[wave][lane] = m2 + mc;
-    __syncthreads();
-    if (wave != 0 || !ok) return;
-    m2 = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
-    const float var = m2 / (float)M;
-    const float invstd = 1.f / sqrtf(var + eps);
-    fin[2 * n] = mean;
+    const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float2 st = bn_fold_stats_inline(part, chunks, M, N, rc, n, sh);
+    if (threadIdx.x >= 64 || n >= N) return;
+    const float invstd = bn_invstd(st.y, M, eps);
+    fin[2 * n] = st.x;
     fin[2 * n + 1] = invstd;
-    invstd_out[n] = invstd;
-    if (rmean) {
-        rmean[n] = bn_running(rmean[n], momentum, mean);
-        rvar[n] = bn_running(rvar[n], momentum, M > 1 ? m2 / (float)(M - 1) : var);
-    }
+    bn_fwd_leave(st, invstd, M, momentum, n, rmean, rvar, invstd_out);
 }
 
 __global__ __launch_bounds__(BN_THREADS) void bn_fwd_apply_kernel(const float* __restrict__ Z, const float* __restrict__ fin,
@@ -942,49 +1009,18 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_stats_kernel(const float* _
     }
 }
 
-// fin[2n], fin[2n+1] = sum dA, sum dA * xhat of column n = dbeta, dgamma (four waves sum a quarter of the chunks each in
-// ascending order, wave 0 adds the quarters in order)
+// fin[2n], fin[2n+1] = sum dA, sum dA * xhat of column n = dbeta, dgamma, for the apply launch behind this one
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_fold_kernel(const float* __restrict__ part, int chunks, int N,
                                                                  float* __restrict__ fin, float* __restrict__ dgamma,
                                                                  float* __restrict__ dbeta) {
     __shared__ float sh[BN_WAVES][2][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + lane;
-    const int q = (chunks + BN_WAVES - 1) / BN_WAVES, c0 = wave * q, c1 = min(chunks, c0 + q);
-    float sum_da = 0.f, sum_dax = 0.f;
-    constexpr int QMAX = 64;         // as bn_fwd_fold_kernel: a quarter of up to 64 chunks in one round of requests
-    const int nn = n < N ? n : N - 1;
-    if (q <= QMAX) {
-        float2 pv[QMAX];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) pv[k] = reinterpret_cast<const float2*>(part)[(size_t)(c0 + k) * N + nn];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) {
-                sum_da += pv[k].x;
-                sum_dax += pv[k].y;
-            }
-    } else {
-#pragma unroll 8
-        for (int c = c0; c < c1; ++c) {
-            const float2 p = reinterpret_cast<const float2*>(part)[(size_t)c * N + nn];
-            sum_da += p.x;
-            sum_dax += p.y;
-        }
-    }
-    sh[wave][0][lane] = sum_da;
-    sh[wave][1][lane] = sum_dax;
-    __syncthreads();
-    if (wave != 0 || n >= N) return;
-    for (int w = 1; w < BN_WAVES; ++w) {
-        sum_da += sh[w][0][lane];
-        sum_dax += sh[w][1][lane];
-    }
-    fin[2 * n] = sum_da;
-    fin[2 * n + 1] = sum_dax;
-    dgamma[n] = sum_dax;
-    dbeta[n] = sum_da;
+    const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float2 t = bn_fold_sums_inline(part, chunks, N, n, sh);
+    if (threadIdx.x >= 64 || n >= N) return;
+    fin[2 * n] = t.x;
+    fin[2 * n + 1] = t.y;
+    dgamma[n] = t.y;
+    dbeta[n] = t.x;
 }
 
 // dZ = invstd * gamma * (dA - mean(dA) - xhat * mean(dA * xhat))
@@ -1011,58 +1047,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const float* _
 // ---- the fold INSIDE the apply launch ------------------------------------------------------------------------------------------
 // A fold launch is 5-8 us of latency for 64 KB of partials per block of 64 columns, and the apply launch behind it cannot start
 // before it ends.  Here every apply workgroup -- 64 columns x a band of rows -- folds its own columns first (the chunk partials of a
-// quarter requested at once: one memory latency; the same chains as the fold kernels, so the same bits) and goes straight on to
+// quarter requested at once: one memory latency; the fold kernels' own device functions, so the same bits) and goes straight on to
 // its rows; the band is tall enough (>= 128 rows at [8192, 256]) that the partials are re-read by ~64 workgroups per column
 // block out of L2, 32 MB per launch.  The workgroups of the first band write what the fold kernel wrote (invstd, running
 // statistics, batch counter; dgamma / dbeta).  One launch per BatchNorm operator less, forward and backward.
-__device__ __forceinline__ float2 bn_fold_stats_inline(const float* __restrict__ part, int chunks, int M, int N, int rc, int n,
-                                                       float (*sh)[64]) {      // (mean, M2) of column n, valid in every wave
-    constexpr int QMAX = 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = (chunks + BN_WAVES - 1) / BN_WAVES, c0 = wave * q, c1 = min(chunks, c0 + q);
-    const int nn = n < N ? n : N - 1;
-    float s = 0.f, m2 = 0.f, mc = 0.f, mean;
-    if (q <= QMAX) {
-        float2 pv[QMAX];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) pv[k] = reinterpret_cast<const float2*>(part)[(size_t)(c0 + k) * N + nn];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) s = fmaf((float)(min(M, (c0 + k + 1) * rc) - (c0 + k) * rc), pv[k].x, s);
-        sh[wave][lane] = s;
-        __syncthreads();
-        mean = (((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane]) / (float)M;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) {
-                const float nb = (float)(min(M, (c0 + k + 1) * rc) - (c0 + k) * rc);
-                const float d = pv[k].x - mean;
-                bn_sum_comp(fmaf(nb * d, d, pv[k].y), m2, mc);
-            }
-    } else {
-#pragma unroll 8
-        for (int c = c0; c < c1; ++c) s = fmaf((float)(min(M, (c + 1) * rc) - c * rc), part[((size_t)c * N + nn) * 2], s);
-        sh[wave][lane] = s;
-        __syncthreads();
-        mean = (((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane]) / (float)M;
-        __syncthreads();
-#pragma unroll 8
-        for (int c = c0; c < c1; ++c) {
-            const float nb = (float)(min(M, (c + 1) * rc) - c * rc);
-            const float2 p = reinterpret_cast<const float2*>(part)[(size_t)c * N + nn];
-            const float d = p.x - mean;
-            bn_sum_comp(fmaf(nb * d, d, p.y), m2, mc);
-        }
-    }
-    sh[wave][lane] = m2 + mc;
-    __syncthreads();
-    m2 = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
-    __syncthreads();
-    return make_float2(mean, m2);
-}
-
 template <bool DROP>
 __global__ __launch_bounds__(BN_THREADS) void bn_fwd_apply_fold_kernel(
     const float* __restrict__ Z, const float* __restrict__ part, int chunks, int M, int N, int rc, float eps, float momentum,
@@ -1078,17 +1066,11 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_apply_fold_kernel(
     unsigned long long ctr = 0;
     if (DROP) ctr = drop_counter_enter(ctr_src, used_out, tick, &ctr_s, blockIdx.x == 0 && blockIdx.y == 0, gridDim.x * gridDim.y);
     const float2 st = bn_fold_stats_inline(part, chunks, M, N, rc, n, sh);
-    const float var = st.y / (float)M;
-    const float invstd = 1.f / sqrtf(var + eps);
+    const float invstd = bn_invstd(st.y, M, eps);
     if (wave == 0) {
         cst[lane] = n < N ? make_float4(st.x, invstd, gamma[n], beta[n]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (blockIdx.y == 0 && n < N) {     // what bn_fwd_fold_kernel leaves behind, once per column
-            invstd_out[n] = invstd;
-            if (rmean) {
-                rmean[n] = bn_running(rmean[n], momentum, st.x);
-                rvar[n] = bn_running(rvar[n], momentum, M > 1 ? st.y / (float)(M - 1) : var);
-            }
-        }
+        // (the workgroups of the first band leave what bn_fwd_fold_kernel leaves behind)
+        if (blockIdx.y == 0 && n < N) bn_fwd_leave(st, invstd, M, momentum, n, rmean, rvar, invstd_out);
         if (nbt && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) *nbt += nbt_inc;
     }
     __syncthreads();
@@ -1130,48 +1112,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_fold_kernel(const flo
                                                                        int band, float* __restrict__ dgamma,
                                                                        float* __restrict__ dbeta, float* __restrict__ dZ) {
     __shared__ float sh[BN_WAVES][2][64];
-    __shared__ float2 tot[64];
-    constexpr int QMAX = 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + lane, nn = n < N ? n : N - 1;
-    const int q = (chunks + BN_WAVES - 1) / BN_WAVES, c0 = wave * q, c1 = min(chunks, c0 + q);
-    float sum_da = 0.f, sum_dax = 0.f;
-    if (q <= QMAX) {       // bn_bwd_fold_kernel's chains
-        float2 pv[QMAX];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) pv[k] = reinterpret_cast<const float2*>(part)[(size_t)(c0 + k) * N + nn];
-#pragma unroll
-        for (int k = 0; k < QMAX; ++k)
-            if (c0 + k < c1) {
-                sum_da += pv[k].x;
-                sum_dax += pv[k].y;
-            }
-    } else {
-#pragma unroll 8
-        for (int c = c0; c < c1; ++c) {
-            const float2 p = reinterpret_cast<const float2*>(part)[(size_t)c * N + nn];
-            sum_da += p.x;
-            sum_dax += p.y;
-        }
-    }
-    sh[wave][0][lane] = sum_da;
-    sh[wave][1][lane] = sum_dax;
-    __syncthreads();
-    if (wave == 0) {
-        for (int w = 1; w < BN_WAVES; ++w) {
-            sum_da += sh[w][0][lane];
-            sum_dax += sh[w][1][lane];
-        }
-        tot[lane] = make_float2(sum_da, sum_dax);
-        if (blockIdx.y == 0 && n < N) {
-            dgamma[n] = sum_dax;
-            dbeta[n] = sum_da;
-        }
-    }
-    __syncthreads();
+    const int n = blockIdx.x * 64 + lane;
+    const float2 t = bn_fold_sums_inline(part, chunks, N, n, sh);
     if (n >= N) return;
-    const float2 t = tot[lane];
+    if (wave == 0 && blockIdx.y == 0) {     // what bn_bwd_fold_kernel leaves behind, once per column
+        dgamma[n] = t.y;
+        dbeta[n] = t.x;
+    }
     const float isg = __fmul_rn(invstd[n], gamma[n]);
     const float a1 = t.x / (float)M, a2 = t.y / (float)M;
     const int m0 = blockIdx.y * band, m1 = min(M, m0 + band);
@@ -1204,34 +1152,7 @@ static int bn_fwd_impl(const float* Z, const float* gamma, const float* beta, fl
                        float* running_var, int64_t M, int32_t N, int32_t act, float* Y, float* xhat, float* invstd, void* ws,
                        size_t ws_bytes, hipStream_t stream, float* Yd, float p, uint64_t seed, uint64_t offset,
                        const int64_t* counter, int64_t* used_out, int64_t* tick_state, bool have_stats = false,
-                       int64_t* nbt = nullptr, int32_t nbt_inc = 0);
-
-extern "C" int fr_bn_fwd(const float* Z, const float* gamma, const float* beta, float eps, float momentum,
-                         float* running_mean, float* running_var, int64_t M, int32_t N, int32_t act, float* Y,
-                         float* xhat, float* invstd, void* ws, size_t ws_bytes, void* stream_) {
-    return bn_fwd_impl(Z, gamma, beta, eps, momentum, running_mean, running_var, M, N, act, Y, xhat, invstd, ws, ws_bytes,
-                       (hipStream_t)stream_, nullptr, 0.f, 0, 0, nullptr, nullptr, nullptr);
-}
-
-// fr_bn_fwd that also writes Yd = dropout(Y), the next layer's input, in its last launch: what fr_dropout_apply(Y, ...,
-// out = Yd) would give with the same (p, seed, offset, counter, used_out, tick_state); N % 4 == 0.
-extern "C" int fr_bn_fwd_drop(const float* Z, const float* gamma, const float* beta, float eps, float momentum,
-                              float* running_mean, float* running_var, int64_t M, int32_t N, int32_t act, float* Y,
-                              float* xhat, float* invstd, void* ws, size_t ws_bytes, float* Yd, float p, uint64_t seed,
-                              uint64_t offset, const int64_t* counter, int64_t* used_out, int64_t* tick_state,
-                              void* stream_) {
-    FR_CHECK_ARG(Yd && counter && N % 4 == 0 && p >= 0.f && p < 1.f && offset % 4 == 0 &&
-                     (((uintptr_t)Z | (uintptr_t)Y | (uintptr_t)Yd | (uintptr_t)xhat | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0,
-                 "fr_bn_fwd_drop: bad argument (N % 4 == 0, 16-byte aligned tensors)");
-    return bn_fwd_impl(Z, gamma, beta, eps, momentum, running_mean, running_var, M, N, act, Y, xhat, invstd, ws, ws_bytes,
-                       (hipStream_t)stream_, Yd, p, seed, offset, counter, used_out, tick_state);
-}
-
-static int bn_fwd_impl(const float* Z, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
-                       float* running_var, int64_t M, int32_t N, int32_t act, float* Y, float* xhat, float* invstd, void* ws,
-                       size_t ws_bytes, hipStream_t stream, float* Yd, float p, uint64_t seed, uint64_t offset,
-                       const int64_t* counter, int64_t* used_out, int64_t* tick_state, bool have_stats, int64_t* nbt,
-                       int32_t nbt_inc) {
+                       int64_t* nbt = nullptr, int32_t nbt_inc = 0) {
     FR_CHECK_ARG(Z && gamma && beta && Y && xhat && invstd && ws && M >= 1 && N >= 1 && act_ok(act) &&
                      ws_bytes >= fr_bn_workspace_bytes(M, N), "fr_bn_fwd: bad argument");
     const int rc = bn_chunk_rows(M);
@@ -1275,6 +1196,27 @@ static int bn_fwd_impl(const float* Z, const float* gamma, const float* beta, fl
     return FR_OK;
 }
 
+extern "C" int fr_bn_fwd(const float* Z, const float* gamma, const float* beta, float eps, float momentum,
+                         float* running_mean, float* running_var, int64_t M, int32_t N, int32_t act, float* Y,
+                         float* xhat, float* invstd, void* ws, size_t ws_bytes, void* stream_) {
+    return bn_fwd_impl(Z, gamma, beta, eps, momentum, running_mean, running_var, M, N, act, Y, xhat, invstd, ws, ws_bytes,
+                       (hipStream_t)stream_, nullptr, 0.f, 0, 0, nullptr, nullptr, nullptr);
+}
+
+// fr_bn_fwd that also writes Yd = dropout(Y), the next layer's input, in its last launch: what fr_dropout_apply(Y, ...,
+// out = Yd) would give with the same (p, seed, offset, counter, used_out, tick_state); N % 4 == 0.
+extern "C" int fr_bn_fwd_drop(const float* Z, const float* gamma, const float* beta, float eps, float momentum,
+                              float* running_mean, float* running_var, int64_t M, int32_t N, int32_t act, float* Y,
+                              float* xhat, float* invstd, void* ws, size_t ws_bytes, float* Yd, float p, uint64_t seed,
+                              uint64_t offset, const int64_t* counter, int64_t* used_out, int64_t* tick_state,
+                              void* stream_) {
+    FR_CHECK_ARG(Yd && counter && N % 4 == 0 && p >= 0.f && p < 1.f && offset % 4 == 0 &&
+                     (((uintptr_t)Z | (uintptr_t)Y | (uintptr_t)Yd | (uintptr_t)xhat | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0,
+                 "fr_bn_fwd_drop: bad argument (N % 4 == 0, 16-byte aligned tensors)");
+    return bn_fwd_impl(Z, gamma, beta, eps, momentum, running_mean, running_var, M, N, act, Y, xhat, invstd, ws, ws_bytes,
+                       (hipStream_t)stream_, Yd, p, seed, offset, counter, used_out, tick_state);
+}
+
 // Z = X W^T + b for a layer with BatchNorm behind it, the BatchNorm's per-chunk statistics written by the product's own
 // epilogue into `bn_ws` (fr_bn_workspace_bytes(M, N): what fr_bn_fwd's first launch would leave there): follow with
 // fr_bn_fwd_ex(..., have_stats = 1).  Fast form only (K, k0 multiples of 32, no mask, 32-row chunks, i.e. M <= 32768, the
@@ -1284,10 +1226,8 @@ extern "C" int fr_linear_fwd_bnstats(const float* x0, int32_t k0, const float* x
     FR_CHECK_ARG(x0 && W && Z && bn_ws && M >= 1 && N >= 1 && k0 >= 1 && k1 >= 0 && (k1 == 0 || x1), "fr_linear_fwd_bnstats: bad argument");
     FR_CHECK_ARG(bn_ws_bytes >= fr_bn_workspace_bytes(M, N), "fr_linear_fwd_bnstats: BatchNorm workspace too small");
     const int K = k0 + k1;
-    static const bool off = getenv("FAIRREC_LINEAR_SLOW") != nullptr || getenv("FAIRREC_LINEAR_NO_GLDS") != nullptr ||
-                            getenv("FAIRREC_BN_STATS_LAUNCH") != nullptr;
-    const bool aligned = ((uintptr_t)x0 & 15) == 0 && ((uintptr_t)W & 15) == 0 && (!x1 || ((uintptr_t)x1 & 15) == 0);
-    if (off || !aligned || K % 32 != 0 || k0 % 32 != 0 || N < 8 || bn_chunk_rows(M) != 32 || !glds_shared_form()) {
+    static const bool stats_launch = getenv("FAIRREC_BN_STATS_LAUNCH") != nullptr;
+    if (stats_launch || !fwd_fast_form(N, K, k0, {x0, x1, W}) || bn_chunk_rows(M) != 32 || !glds_shared_form()) {
         set_error("fr_linear_fwd_bnstats: not in the fast form");
         return FR_EUNSUPPORTED;
     }

@@ -920,12 +920,9 @@ int glds_linear_bwd_input(const float* dY, const float* W, int64_t M, int N, int
     return launch_mode<GL_BWD_IN>(g, (ntiles + tpb - 1) / tpb, stream, K_LINEAR_BWD_INPUT);
 }
 
-int glds_linear_bwd_weight(const float* dY, const GlMat& X, int64_t M, int N, int K, int splits, int rows_per_split,
-                           float* slab, float* bslab, hipStream_t stream) {
-    if (!X.b || X.split >= K) {
-        int rc;
-        if (stream_linear_bwd_weight(dY, X.a, M, N, K, splits, rows_per_split, slab, bslab, stream, &rc)) return rc;
-    }
+// one weight-gradient job as the kernels see it: slab[s] = dY[rows of s]^T X[rows of s]
+static GlArgs wgrad_args(const float* dY, const GlMat& X, int64_t M, int N, int K, int splits, int rows_per_split, float* slab,
+                         float* bslab) {
     GlArgs g{};
     g.A = GlMat{dY, nullptr, N, 0, N};
     g.B = X;
@@ -940,6 +937,16 @@ int glds_linear_bwd_weight(const float* dY, const GlMat& X, int64_t M, int N, in
     g.bslab = bslab;
     g.out_rows = N;
     g.out_cols = K;
+    return g;
+}
+
+int glds_linear_bwd_weight(const float* dY, const GlMat& X, int64_t M, int N, int K, int splits, int rows_per_split,
+                           float* slab, float* bslab, hipStream_t stream) {
+    if (!X.b || X.split >= K) {
+        int rc;
+        if (stream_linear_bwd_weight(dY, X.a, M, N, K, splits, rows_per_split, slab, bslab, stream, &rc)) return rc;
+    }
+    const GlArgs g = wgrad_args(dY, X, M, N, K, splits, rows_per_split, slab, bslab);
     if (use_shared()) return launch_shared<GL_BWD_W>(g, stream, K_LINEAR_BWD_WEIGHT);
     const long long nw = (long long)g.tiles_i * g.tiles_j * splits;
     return launch_mode<GL_BWD_W>(g, (nw + GL_WAVES - 1) / GL_WAVES, stream, K_LINEAR_BWD_WEIGHT);
@@ -971,20 +978,7 @@ int glds_linear_bwd_weight_multi(const GlWJob* jobs, int n, int64_t M, hipStream
             }
         }
         GlArgs& g = m.g[ng];
-        g = GlArgs{};
-        g.A = GlMat{q.dY, nullptr, q.N, 0, q.N};
-        g.B = q.X;
-        g.R = (int)M;
-        g.rowsA = g.rowsB = (int)M;
-        g.tiles_i = q.N / 32;
-        g.tiles_j = q.K / 32;
-        g.ks = 1;
-        g.parts = q.splits;
-        g.chunks_per_part = q.rows_per_split / 32;
-        g.slab = q.slab;
-        g.bslab = q.bslab;
-        g.out_rows = q.N;
-        g.out_cols = q.K;
+        g = wgrad_args(q.dY, q.X, M, q.N, q.K, q.splits, q.rows_per_split, q.slab, q.bslab);
         m.first[ng] = blocks;
         blocks += (unsigned)(((g.tiles_i + 1) / 2) * ((g.tiles_j + 1) / 2)) * (unsigned)q.splits;
         ++ng;

@@ -89,6 +89,14 @@ class _Drop:
                                            g.data_ptr(), _C.current_stream()), "fr_dropout_apply")
 
 
+def _fast_form(N, K, k0, *tensors):
+    """The fast form of the backward products, shape and 16-byte alignment, as csrc/mlp.hip::bwd_fast_form states it (the
+    library's off-switches are its own).  The backward pass asks the library by calling it and takes the general call when an
+    entry answers FR_EUNSUPPORTED; this copy serves the two decisions that are needed BEFORE any call: which weight gradients
+    wait for the joint launch, and whether a layer differentiates its activation in a pass of its own."""
+    return N % 32 == 0 and K % 32 == 0 and k0 % 32 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
+
+
 class _HipMLP(torch.autograd.Function):
     """y = MLP([x0 | x1]) on the HIP kernels: per layer [dropout ->] fr_linear_fwd [-> fr_bn_fwd] with the activation fused
     into the last of the two; saves the post-activation outputs and the BatchNorm statistics.
@@ -240,17 +248,16 @@ class _HipMLP(torch.autograd.Function):
         at_z = ctx.top_at_z   # dY already is the gradient at this layer's pre-activation (folded into the layer above / the consumer)
         # A BatchNorm layer's backward statistics may come out of the epilogue of the product above it, which then also takes
         # the gradient through the dropout between the two layers (fr_linear_bwd_input_bnstats: one launch for product,
-        # dropout and statistics; FAIRREC_BN_BWD_SEPARATE=1: the three launches).  `bn_stats`: the workspace they are in.
+        # dropout and statistics; FAIRREC_BN_BWD_SEPARATE=1, or the entry's own FR_EUNSUPPORTED: the three launches).
+        # `bn_stats`: the workspace they are in.
         bn_stats = None
-        bn_fuse = (ctx.use_bn and M <= 32768 and ctx.masks is None and os.environ.get("FAIRREC_BN_BWD_SEPARATE") is None
-                   and os.environ.get("FAIRREC_LINEAR_NO_GLDS") is None and os.environ.get("FAIRREC_LINEAR_SLOW") is None
-                   and os.environ.get("FAIRREC_LINEAR_NO_SHARED") is None and os.environ.get("FAIRREC_BN_FOLD_SEPARATE") is None)
+        bn_fuse = ctx.use_bn and ctx.masks is None and os.environ.get("FAIRREC_BN_BWD_SEPARATE") is None
         # weight gradients in the fast form wait here and go out together at the end: every product in ONE launch and every
         # slab sum in a second (fr_linear_bwd_weight_multi) instead of two launches per layer -- the same kernels' bodies on
         # the same arguments, so the same bits
         deferred = []
-        defer_ok = (os.environ.get("FAIRREC_LINEAR_NO_GLDS") is None and os.environ.get("FAIRREC_LINEAR_SLOW") is None
-                    and os.environ.get("FAIRREC_WGRAD_PER_LAYER") is None)
+        defer_ok = os.environ.get("FAIRREC_WGRAD_PER_LAYER") is None
+        first_block = lambda l: x0.shape[1] if l == 0 else params[per * l].shape[1]      # k0 of layer l
         for l in range(L - 1, -1, -1):
             W = params[per * l].contiguous()
             Y = outs[l]
@@ -291,7 +298,7 @@ class _HipMLP(torch.autograd.Function):
                 if ctx.needs_input_grad[7 + per * l + 2] or ctx.needs_input_grad[7 + per * l + 3]:
                     grads[per * l + 2], grads[per * l + 3] = dg, dbt
                 dY, Y, act = dZ, dZ, 0
-            elif act != 0 and mk is None and N % 32 == 0 and K % 32 == 0 and k0 % 32 == 0:
+            elif act != 0 and mk is None and _fast_form(N, K, k0):
                 # one pass through the activation's derivative, shared by the two products (which then take their fast form)
                 dA = torch.empty_like(Y)
                 _C.check(lib.fr_act_bwd(dY.data_ptr(), Y.data_ptr(), act, M * N, dA.data_ptr(), st), "fr_act_bwd")
@@ -313,8 +320,7 @@ class _HipMLP(torch.autograd.Function):
                                               ctx.scale if at_z else 0.0, _C.ptr(da), dW.data_ptr(), db.data_ptr(),
                                               ws.data_ptr(), ws.numel(), st), "fr_linear_n1_bwd")
             else:
-                if need_w and defer_ok and act == 0 and mk is None and scale == 1.0 and N % 32 == 0 and K % 32 == 0 and k0 % 32 == 0 \
-                        and (dY.data_ptr() | a.data_ptr() | (c.data_ptr() if c is not None else 0)) % 16 == 0:
+                if need_w and defer_ok and act == 0 and mk is None and scale == 1.0 and _fast_form(N, K, k0, dY, a, c):
                     deferred.append((dY, a, k0, c, k1, N, dW, db))
                 elif need_w:
                     _C.check(lib.fr_linear_bwd_weight(dY.data_ptr(), Y.data_ptr(), act, a.data_ptr(), k0, _C.ptr(c), k1,
@@ -324,37 +330,43 @@ class _HipMLP(torch.autograd.Function):
                     da = torch.empty((M, k0), dtype=torch.float32, device=dev)
                     dc = torch.empty((M, k1), dtype=torch.float32, device=dev) if k1 else None
                     drop_here = drop is not None and ctx.premul[l]
-                    if (bn_fuse and l > 0 and k1 == 0 and act == 0 and mk is None and scale == 1.0 and N % 32 == 0 and K % 32 == 0
-                            and not ctx.dropped_out[l - 1] and (drop_here or (drop is None and not ctx.premul[l]))
-                            and (not drop_here or ctx.drop_off[l][0] % 4 == 0)
-                            and (dY.data_ptr() | W.data_ptr() | da.data_ptr()) % 16 == 0):
-                        bn_stats = torch.empty(lib.fr_bn_workspace_bytes(M, K), dtype=torch.uint8, device=dev)
-                        _C.check(lib.fr_linear_bwd_input_bnstats(
+                    # An entry that takes the gradient on through what lies below this layer, where the host's own conditions
+                    # allow one; each serves the fast form only and says FR_EUNSUPPORTED otherwise: the general call then,
+                    # and the launches the epilogue stood for.
+                    rc, entry = _C.EUNSUPPORTED, None
+                    if (bn_fuse and l > 0 and act == 0 and mk is None and scale == 1.0 and not ctx.dropped_out[l - 1]
+                            and (drop_here or (drop is None and not ctx.premul[l]))):
+                        entry = "fr_linear_bwd_input_bnstats"
+                        ws_bn = torch.empty(lib.fr_bn_workspace_bytes(M, K), dtype=torch.uint8, device=dev)
+                        rc = lib.fr_linear_bwd_input_bnstats(
                             dY.data_ptr(), W.data_ptr(), M, N, K, da.data_ptr(), outs[l - 1].data_ptr(), xhats[l - 1].data_ptr(),
-                            ctx.act, bn_stats.data_ptr(), bn_stats.numel(), drop.p if drop_here else 0.0,
+                            ctx.act, ws_bn.data_ptr(), ws_bn.numel(), drop.p if drop_here else 0.0,
                             drop.seed if drop_here else 0, ctx.drop_off[l][0] if drop_here else 0,
-                            drop.used.data_ptr() if drop_here else None, st), "fr_linear_bwd_input_bnstats")
-                        fused_here = True
-                    elif l > 0 and ctx.dropped_out[l - 1] and act == 0 and N % 32 == 0 and K % 32 == 0 and \
-                            os.environ.get("FAIRREC_LINEAR_NO_GLDS") is None and os.environ.get("FAIRREC_LINEAR_SLOW") is None:
+                            drop.used.data_ptr() if drop_here else None, st)
+                        if rc == 0:
+                            bn_stats, fused_here = ws_bn, True
+                    elif l > 0 and ctx.dropped_out[l - 1] and act == 0:
                         # the input is the dropped ReLU output of the layer below: on through it in the epilogue
-                        _C.check(lib.fr_linear_bwd_input_relu(dY.data_ptr(), W.data_ptr(), M, N, K, a.data_ptr(), ctx.scale,
-                                                              da.data_ptr(), st), "fr_linear_bwd_input_relu")
-                        at_z = True
+                        entry = "fr_linear_bwd_input_relu"
+                        rc = lib.fr_linear_bwd_input_relu(dY.data_ptr(), W.data_ptr(), M, N, K, a.data_ptr(), ctx.scale,
+                                                          da.data_ptr(), st)
+                        at_z = rc == 0
                     elif (l > 0 and not ctx.use_bn and ctx.act != 0 and act == 0 and mk is None and scale == 1.0 and drop is None
-                          and ctx.masks is None and not ctx.premul[l] and not ctx.dropped_out[l - 1] and k1 == 0
-                          and N % 32 == 0 and K % 32 == 0 and params[per * (l - 1)].shape[1] % 32 == 0
-                          and (l - 1 > 0 or x1 is None or x0.shape[1] % 32 == 0)
-                          and os.environ.get("FAIRREC_LINEAR_NO_GLDS") is None and os.environ.get("FAIRREC_LINEAR_SLOW") is None
-                          and os.environ.get("FAIRREC_ACT_BWD_SEPARATE") is None):
-                        # the input is the activation output of the layer below: on through act' in the epilogue, so that layer
-                        # starts from the gradient at its pre-activation (no fr_act_bwd pass of its own; same bits)
-                        _C.check(lib.fr_linear_bwd_input_act(dY.data_ptr(), W.data_ptr(), M, N, K, a.data_ptr(), ctx.act,
-                                                             da.data_ptr(), st), "fr_linear_bwd_input_act")
-                        at_z = True
-                    else:
+                          and ctx.masks is None and not ctx.premul[l] and not ctx.dropped_out[l - 1]
+                          and os.environ.get("FAIRREC_ACT_BWD_SEPARATE") is None
+                          and _fast_form(*params[per * (l - 1)].shape, first_block(l - 1))):
+                        # the input is the activation output of the layer below, which would otherwise differentiate it in a
+                        # pass of its own (the last condition: that layer's N, K and k0 have the fast form): on through act' in
+                        # the epilogue, so that layer starts from the gradient at its pre-activation (same bits)
+                        entry = "fr_linear_bwd_input_act"
+                        rc = lib.fr_linear_bwd_input_act(dY.data_ptr(), W.data_ptr(), M, N, K, a.data_ptr(), ctx.act,
+                                                         da.data_ptr(), st)
+                        at_z = rc == 0
+                    if rc == _C.EUNSUPPORTED:
                         _C.check(lib.fr_linear_bwd_input(dY.data_ptr(), Y.data_ptr(), act, W.data_ptr(), _C.ptr(mk), scale,
                                                          M, N, da.data_ptr(), k0, _C.ptr(dc), k1, st), "fr_linear_bwd_input")
+                    else:
+                        _C.check(rc, entry)
             grads[per * l], grads[per * l + 1] = dW, db
             if (need0 or need1) and not fused_here:
                 if drop is not None and ctx.premul[l]:      # back through this layer's input dropout: the pattern again
@@ -378,8 +390,14 @@ class _HipMLP(torch.autograd.Function):
                 _C.FrWgradJob(dy.data_ptr(), a.data_ptr(), k0, _C.ptr(c), k1, N, dW.data_ptr(), db.data_ptr(), None, 0)
                 for (dy, a, k0, c, k1, N, dW, db) in chunk])
             wsm = torch.empty(lib.fr_linear_bwd_weight_multi_workspace_bytes(jobs, len(chunk), M), dtype=torch.uint8, device=dev)
-            _C.check(lib.fr_linear_bwd_weight_multi(jobs, len(chunk), M, wsm.data_ptr(), wsm.numel(), st),
-                     "fr_linear_bwd_weight_multi")
+            rc = lib.fr_linear_bwd_weight_multi(jobs, len(chunk), M, wsm.data_ptr(), wsm.numel(), st)
+            if rc != _C.EUNSUPPORTED:
+                _C.check(rc, "fr_linear_bwd_weight_multi")
+                continue
+            for (dy, a, k0, c, k1, N, dW, db) in chunk:       # (the LDS-DMA forms are switched off): job by job
+                ws = torch.empty(lib.fr_linear_bwd_weight_workspace_bytes(M, N, k0 + k1), dtype=torch.uint8, device=dev)
+                _C.check(lib.fr_linear_bwd_weight(dy.data_ptr(), dy.data_ptr(), 0, a.data_ptr(), k0, _C.ptr(c), k1, None, 1.0, M, N,
+                                                  dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), st), "fr_linear_bwd_weight")
         return (dx0, dx1, None, None, None, None, None, *grads)
 
 

@@ -30,7 +30,8 @@ Which case reaches which kernel:
   linear_n1_bwd_kernel            test_one_output_backward
   bn_fwd_stats_kernel, bn_fwd_apply_fold_kernel<false>, bn_bwd_stats_kernel, bn_bwd_apply_fold_kernel   test_batchnorm[inline-*]
   bn_fwd_fold_kernel, bn_fwd_apply_kernel, bn_bwd_fold_kernel, bn_bwd_apply_kernel   test_batchnorm[separate-*]
-                                  (both rows also: test_batchnorm_planted_rows)
+                                  (both rows also: test_batchnorm_planted_rows; one against the other, bit for bit:
+                                  test_batchnorm_fold_forms_agree)
   bn_fwd_apply_fold_kernel<true> / bn_fwd_apply_drop_kernel   test_batchnorm_forward_with_dropout[inline / separate]
   the statistics epilogues of linear_glds64_kernel<FWD> and <BWD_IN_BN>   test_forward_statistics_epilogue,
                                                                           test_backward_statistics_epilogue
@@ -439,6 +440,47 @@ def test_weight_gradient_multi_refuses_a_ninth_job_and_a_job_outside_the_fast_fo
     assert o.ok() and bool(torch.isnan(dW).all())             # nothing was written
 
 
+def test_backward_fast_form_edges(monkeypatch):
+    """The one rule of the backward fast form (csrc/mlp.hip::bwd_fast_form) at its edges, through the entries that exist in
+    that form only -- the three epilogue entries and a one-job fr_linear_bwd_weight_multi -- at M = 33: (N, K) = (32, 32) is
+    served; N = 31, K = 33, K = 48 and a dY 4 bytes off a 16-byte boundary are FR_EUNSUPPORTED; layers._fast_form, the host's
+    copy of the rule, answers each case alike.  fr_linear_bwd_input_bnstats also refuses when the BatchNorm apply launch
+    would not fold the partials it leaves (FAIRREC_BN_FOLD_SEPARATE)."""
+    from fairrec import _C
+    from fairrec.model.layers import _fast_form
+    lib, M = _lib(), 33
+    z = lambda *shape: torch.zeros(*shape, device="cuda")
+
+    def calls(N, K, shift):
+        dY = z(M * N + 1)[1:].view(M, N) if shift else z(M, N)
+        W, src, X = z(N, K), z(M, K), z(M, K)
+        o = _Outs()
+        dA, dX, dW = o.new(M, K), o.new(M, K), o.new(N, K)
+        ws = _ws(lib.fr_bn_workspace_bytes(M, K))
+        job = (_C.FrWgradJob * 1)(_C.FrWgradJob(dY.data_ptr(), X.data_ptr(), K, None, 0, N, dW.data_ptr(), None, None, 0))
+        wsm = _ws(lib.fr_linear_bwd_weight_multi_workspace_bytes(job, 1, M))
+        rcs = dict(
+            relu=lib.fr_linear_bwd_input_relu(dY.data_ptr(), W.data_ptr(), M, N, K, src.data_ptr(), 2.0, dA.data_ptr(), _st()),
+            act=lib.fr_linear_bwd_input_act(dY.data_ptr(), W.data_ptr(), M, N, K, src.data_ptr(), 1, dA.data_ptr(), _st()),
+            bnstats=lib.fr_linear_bwd_input_bnstats(dY.data_ptr(), W.data_ptr(), M, N, K, dX.data_ptr(), src.data_ptr(), src.data_ptr(), 0,
+                                                    ws.data_ptr(), ws.numel(), 0.0, 0, 0, None, _st()),
+            multi=lib.fr_linear_bwd_weight_multi(job, 1, M, wsm.data_ptr(), wsm.numel(), _st()))
+        assert o.ok(), (N, K, shift)
+        return rcs, _fast_form(N, K, K, dY, W) and _fast_form(N, K, K, dY, X), (dA, dX, dW)
+
+    rcs, host, outs = calls(32, 32, False)
+    assert host and all(rc == 0 for rc in rcs.values()), rcs
+    assert all(bool((t == 0).all()) for t in outs)                  # zeros in: every output written, as zeros
+    for N, K, shift in ((31, 32, False), (32, 33, False), (64, 48, False), (32, 32, True)):
+        rcs, host, outs = calls(N, K, shift)
+        assert not host and all(rc == EUNSUPPORTED for rc in rcs.values()), (N, K, shift, rcs)
+        assert all(bool(torch.isnan(t).all()) for t in outs), (N, K, shift)      # nothing was written
+    monkeypatch.setenv("FAIRREC_BN_FOLD_SEPARATE", "1")
+    rcs, host, outs = calls(32, 32, False)
+    assert host and rcs == dict(relu=0, act=0, bnstats=EUNSUPPORTED, multi=0), rcs
+    assert bool(torch.isnan(outs[1]).all())
+
+
 @pytest.mark.parametrize("parts", [1, 3, 5])
 def test_parts_sum(parts):
     for n in (1, 63, 64, 65, 4097):
@@ -653,6 +695,52 @@ def test_batchnorm_forward_with_dropout(fold, monkeypatch):
                               inv.data_ptr(), ws.data_ptr(), ws.numel(), 0, Yd.data_ptr(), p, seed, 0, state.data_ptr(), None, None, None,
                               0, _st())
         assert rc == EINVAL
+
+
+def _bn_both_ways(c, act, M, N):
+    """fr_bn_fwd and fr_bn_bwd on the case's data: every output, on the host"""
+    Zd, gd, bd, dYd = _d(c.Z), _d(c.gamma), _d(c.beta), _d(c.dY)
+    Y, xh, inv, rm, rv = _bn_fwd(Zd, gd, bd, c.eps, c.momentum, _d(c.rmean), _d(c.rvar), act, M, N)
+    dZ, dg, db = _bn_bwd(dYd, Y, act, xh, inv, gd, M, N)
+    return dict(Y=Y.cpu(), xhat=xh.cpu(), invstd=inv.cpu(), running_mean=rm.cpu(), running_var=rv.cpu(),
+                dZ=torch.from_numpy(dZ), dgamma=torch.from_numpy(dg), dbeta=torch.from_numpy(db))
+
+
+def _bn_drop_outputs(c, M, N):
+    """fr_bn_fwd_ex with the next layer's dropout (p = 0.5, counter 41): every output, on the host"""
+    lib = _lib()
+    Zd, gd, bd = _d(c.Z), _d(c.gamma), _d(c.beta)
+    o = _Outs()
+    Y, xh, Yd, inv, rm, rv = o.new(M, N), o.new(M, N), o.new(M, N), o.new(N), o.new(N), o.new(N)
+    rm.copy_(_d(c.rmean))
+    rv.copy_(_d(c.rvar))
+    state = torch.tensor([41, 0], dtype=torch.int64, device="cuda")
+    ws = _ws(lib.fr_bn_workspace_bytes(M, N))
+    rc = lib.fr_bn_fwd_ex(Zd.data_ptr(), gd.data_ptr(), bd.data_ptr(), c.eps, c.momentum, rm.data_ptr(), rv.data_ptr(), M, N, 2,
+                          Y.data_ptr(), xh.data_ptr(), inv.data_ptr(), ws.data_ptr(), ws.numel(), 0, Yd.data_ptr(), 0.5, 77, 64,
+                          state.data_ptr(), None, None, None, 0, _st())
+    assert rc == 0 and o.ok(), (rc, M, N)
+    return dict(Y=Y.cpu(), xhat=xh.cpu(), Yd=Yd.cpu(), invstd=inv.cpu(), running_mean=rm.cpu(), running_var=rv.cpu())
+
+
+@pytest.mark.parametrize("M", [1, 33, 8192, 8193, 32769])
+def test_batchnorm_fold_forms_agree(M, monkeypatch):
+    """The fold inside the apply launch and the fold launch of its own run the same device functions (bn_fold_stats_inline,
+    bn_fold_sums_inline), so every output of fr_bn_fwd and fr_bn_bwd -- Y, xhat, invstd, both running statistics, dZ, dgamma,
+    dbeta -- and Yd of fr_bn_fwd_ex with dropout must be EQUAL between the two forms, bit for bit.  M = 8192 is the last batch
+    whose quarter of the chunks (64 of 256) is held in registers, 8193 the first that walks them in a loop, 32769 has 64-row
+    chunks; N = 1, 65, 100: a lone column, a second column block of one column, a ragged one."""
+    cases = [(N, act) for N in (1, 65, 100) for act in (0, 2)]
+    got = {}
+    for fold in ("inline", "separate"):
+        if fold == "separate":
+            monkeypatch.setenv("FAIRREC_BN_FOLD_SEPARATE", "1")
+        got[fold] = [_bn_both_ways(D.bn_case(M, N, seed=act), act, M, N) for N, act in cases]
+        if M == 33:
+            got[fold].append(_bn_drop_outputs(D.bn_case(33, 36, seed=36), 33, 36))
+    for i, (a, b) in enumerate(zip(got["inline"], got["separate"])):
+        for name in a:
+            assert _bits(a[name], b[name]), (M, cases[i] if i < len(cases) else "dropout [33, 36]", name)
 
 
 # ---- statistics from a product's epilogue -----------------------------------------------------------------------------------

@@ -636,3 +636,32 @@ def test_bn_backward_statistics_from_the_product_epilogue_are_the_three_launches
     assert float(res["fused"]["x"].abs().max()) > 0
     for n in res["fused"]:
         assert torch.equal(res["fused"][n], res["separate"][n]), n
+
+
+def test_mlp_backward_falls_back(monkeypatch):
+    """The backward pass calls fr_linear_bwd_input_bnstats wherever the host's own conditions allow it and takes the three
+    launches (product, dropout, statistics) when the entry answers FR_EUNSUPPORTED -- here because FAIRREC_LINEAR_NO_SHARED,
+    which the library reads per call, selects kernels without that epilogue.  The gradients must EQUAL, bit for bit, those of
+    FAIRREC_BN_BWD_SEPARATE=1 under the same switch, where the host never calls the entry."""
+    from fairrec.model.layers import MLPLayers
+    monkeypatch.setenv("FAIRREC_LINEAR_NO_SHARED", "1")
+    torch.manual_seed(5)
+    M, widths = 33, [64, 64, 32]
+    mlp = MLPLayers(widths, dropout=0.5, bn=True).cuda().train()
+    x = (torch.randn(M, widths[0], device="cuda") * 0.1).requires_grad_()
+    tgt = torch.randn(M, widths[-1], device="cuda")
+    st = mlp._drop_state(x.device)
+    st0 = st.clone()
+    res = {}
+    for mode in ("fallback", "separate"):
+        if mode == "separate":
+            monkeypatch.setenv("FAIRREC_BN_BWD_SEPARATE", "1")
+        st.copy_(st0)
+        for q in mlp.parameters():
+            q.grad = None
+        x.grad = None
+        ((mlp(x) - tgt) ** 2).mean().backward()
+        res[mode] = {"x": x.grad.clone(), **{n: q.grad.clone() for n, q in mlp.named_parameters()}}
+    assert float(res["fallback"]["x"].abs().max()) > 0
+    for n in res["fallback"]:
+        assert torch.equal(res["fallback"][n], res["separate"][n]), n
