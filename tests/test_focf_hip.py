@@ -230,7 +230,7 @@ def test_in_launch_prepare_equals_sorted_prepare(objective, dim):
         for k, eng in enumerate(engs):
             loss, _ = eng.forward(u[t], i[t], r[t], s[t], next_batch=nxt or None)
             eng.backward_adam()
-            assert eng._prev is not None and eng._prev[3] == (k == 1)
+            assert eng._prev is not None and eng._prev.staged == (k == 1)
             losses[k].append(loss)
         for eng in engs:      # (every step: which steps of a row's replay run in one stretch depends on when the sweeper
             eng.flush()       # meets the row, and that on how far ahead its stamps were written -- a few ulp otherwise)
@@ -686,8 +686,8 @@ def test_lookahead_stamps_are_the_apply_steps(staged):
             queue = [(b[0], b[1], b[3], b[2]) for b in batches[t + 1:t + 21]] or None
             eng.forward(u, i, r, s, next_batch=queue)
             assert eng._stash is not None, "the one-launch step must be taken"
-            stamp = eng._stash[6]
-            seen.append((stamp[0] if staged else stamp, eng.U.step + 1))      # (staged: stamp and generation of row words)
+            assert (eng._stash.gen is not None) == staged                    # (staged: a generation of row words as well)
+            seen.append((eng._stash.stamp, eng.U.step + 1))
             eng.backward_adam()
         eng.flush()
     eng.check_device_errors()
@@ -928,3 +928,181 @@ def test_pipelined_runs_step_at_full_batch_size():
             # (19 M elements, some of them crossing zero: a floor of 1e-7 of the largest weight; a missed step is 1e-3)
             torch.testing.assert_close(x, y, rtol=2e-5, atol=1e-7 * float(y.abs().max()) + 1e-12)
         np.testing.assert_allclose(o.loss_acc.cpu().numpy()[:4], ref.loss_acc.cpu().numpy()[:4], rtol=1e-5)
+
+
+class _CallRecorder:
+    """Stands in for the loaded library: every `fr_focf_*` entry point and `fr_loss_accumulate` is noted by name, followed
+    by the ring index (position in `eng.ws`) of every workspace the call is handed -- as a pointer argument, in a
+    fr_focf_batch record passed by reference, or in an array of such records -- in argument order; then the call goes
+    through."""
+
+    def __init__(self, lib, eng, calls):
+        self._lib, self._eng, self._calls = lib, eng, calls
+
+    def _slots(self, name, args):
+        from fairrec import _C
+        import ctypes
+        slot = {w.data_ptr(): k for k, w in enumerate(self._eng.ws) if w is not None}
+        records = []
+        if name == "fr_focf_prepare_step":
+            records = [args[0][q] for q in range(args[2])]
+        elif name == "fr_focf_prepare_many":
+            records = [args[0][q] for q in range(args[1])]
+        elif name in ("fr_focf_steps_many", "fr_focf_runs_many"):
+            arr = ctypes.cast(args[3], ctypes.POINTER(_C.FrFocfBatch))
+            records = [arr[q] for q in range(args[4])]
+        out = [slot.get(b.ws, -1) for b in records]
+        for a in args:
+            if isinstance(a, int) and not isinstance(a, bool) and a in slot:
+                out.append(slot[a])
+            elif isinstance(getattr(a, "_obj", None), _C.FrFocfBatch):
+                out.append(slot.get(a._obj.ws, -1))
+        return out
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not (name.startswith("fr_focf_") or name == "fr_loss_accumulate"):
+            return fn
+
+        def call(*args):
+            self._calls.append(name)
+            self._calls.extend(self._slots(name, args))
+            return fn(*args)
+        return call
+
+
+def _every_path_data():
+    """18 uniform batches of 300-520 rows held back to back in one set of columns (so that a run of them can go to
+    steps_many), two more that are announced and never applied, and 11 item-complete batches, four of them back to back."""
+    n_users, n_items, D = 3001, 501, 64
+    g = torch.Generator().manual_seed(41)
+    sizes = [int(x) for x in torch.randint(300, 521, (20,), generator=g)]
+    tot = sum(sizes)
+    u = torch.randint(1, n_users, (tot,), generator=g)
+    cols = (u.cuda(), torch.randint(1, n_items, (tot,), generator=g).cuda(),
+            torch.randint(1, 6, (tot,), generator=g).float().cuda(),
+            torch.randint(0, 2, (n_users,), generator=g).float()[u].cuda())
+    start = [0] + [int(x) for x in np.cumsum(sizes)]
+    uniform = [tuple(c[start[t]:start[t + 1]] for c in cols) for t in range(20)]
+    items = _item_complete_batches(n_users, n_items, 11, 400, 43)
+    run = tuple(torch.cat([b[j] for b in items[6:10]]).contiguous() for j in range(4))
+    cut = [0] + [int(x) for x in np.cumsum([b[0].numel() for b in items[6:10]])]
+    items[6:10] = [tuple(c[cut[k]:cut[k + 1]] for c in run) for k in range(4)]
+    return {"seq": uniform[:18] + items, "never": uniform[18:],
+            "uniform_run": (tuple(c[start[12]:start[17]] for c in cols), sizes[12:17]),
+            "item_run": (run, [cut[k + 1] - cut[k] for k in range(4)]),
+            "U0": (torch.randn(n_users, D, generator=g) * 0.05).cuda(),
+            "I0": (torch.randn(n_items, D, generator=g) * 0.05).cuda(), "clip_at": (10, 11)}
+
+
+def _every_path_engine(data):
+    from fairrec.model.fair_recommender.focf import FocfEngine
+    from fairrec.optim import FusedLazyAdam
+    eng = FocfEngine(data["U0"].clone(), data["I0"].clone(), "value", 0.5, 5.0)
+    FusedLazyAdam(eng, lr=5e-3, weight_decay=1e-3, sweep_period=5)
+    return eng
+
+
+def _drive_through_every_path(eng, data):
+    """One engine through every step form and every hand-over between them; returns the number of steps taken."""
+    seq = data["seq"]
+    announce = lambda bs: [(b[0], b[1], b[3], b[2]) for b in bs] or None
+
+    def step(t, nxt=None, clip=False, want_pred=False):
+        u, i, r, s = seq[t]
+        eng.forward(u, i, r, s, want_pred=want_pred, next_batch=nxt)
+        if clip:
+            eng.clip_grad_norm(1.0)
+        eng.backward_adam()
+
+    eng.defer_loss = True
+    for t in range(4):                                  # 1. staged, the next two batches announced
+        step(t, announce(seq[t + 1:t + 3]))
+    step(4, announce(data["never"]))                    # 2. ... two batches that never come, then nothing announced
+    step(5)
+    eng.staged = False                                  # 3. the sorted prepare, ten batches ahead on the side stream
+    for t in range(6, 10):
+        step(t, announce(seq[t + 1:min(t + 11, 18)]))
+    assert data["clip_at"] == (10, 11)
+    step(10, clip=True)                                 # 4. a sorted stash, then a staged one, falling to the chain
+    eng.staged = True
+    step(11, clip=True)
+    cols, sizes = data["uniform_run"]                   # 5. the library's loop over ragged batches, then a staged step
+    assert eng.steps_many(*cols, sizes) == 5
+    step(17)
+    eng.item_runs = True                                # 6. pipelined item runs ...
+    for t in range(18, 21):
+        step(t, announce(seq[t + 1:t + 3]))
+    step(21, want_pred=True)                            #    ... the chain with item runs pending ...
+    eng.PIPE = False
+    step(22)                                            #    ... the two-launch form ...
+    step(23)
+    eng.PIPE = True
+    cols, sizes = data["item_run"]                      #    ... the library's loop (fr_focf_runs_many) ...
+    assert eng.steps_many(*cols, sizes) == 4
+    step(28)                                            #    ... and a pipelined step again
+    eng.predict(seq[28][0], seq[28][1])                 # 7.
+    eng.flush()
+    eng.check_device_errors()
+    return len(seq)
+
+
+# the calls _drive_through_every_path makes (recorded on an MI355X from the engine whose state was still positional tuples;
+# names and ring indices only)
+_EVERY_PATH_CALLS = [
+    "fr_focf_workspace_bytes", "fr_focf_row_words", "fr_focf_stage", 1, "fr_focf_stage", 1, "fr_focf_workspace_bytes",
+    "fr_focf_stage", 0, "fr_focf_workspace_bytes", "fr_focf_step_staged", 1, 2, 0, "fr_focf_workspace_bytes",
+    "fr_focf_step_staged", 0, 1, 3, 2, "fr_focf_workspace_bytes", "fr_focf_step_staged", 2, 0, 1, 3,
+    "fr_focf_workspace_bytes", "fr_focf_step_staged", 3, 2, 0, 1, "fr_focf_workspace_bytes", "fr_focf_stage", 0,
+    "fr_focf_workspace_bytes", "fr_focf_step_staged", 1, 3, 2, 0, "fr_focf_stage", 0, "fr_focf_stage", 0,
+    "fr_focf_step_staged", 0, 1, "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_workspace_bytes",
+    "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_workspace_bytes",
+    "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_workspace_bytes",
+    "fr_focf_prepare_step", 2, 3, 4, 5, 6, 7, 8, 9, "fr_focf_prepare_step", 10, 11, "fr_focf_prepare_step", 1,
+    "fr_focf_step_finish_staged", 0, "fr_focf_step", 1, "fr_focf_step", 2, 1, "fr_focf_step", 3, 2, "fr_focf_step", 4, 3,
+    "fr_focf_forward", 5, "fr_focf_clip_grad_norm", 5, "fr_focf_backward_adam", 5, "fr_loss_accumulate",
+    "fr_focf_stage", 0, "fr_focf_stage", 0, "fr_focf_forward", 0, "fr_focf_clip_grad_norm", 0,
+    "fr_focf_backward_adam", 0, "fr_loss_accumulate", "fr_focf_step_finish", 4, "fr_focf_steps_many", 0, 1, 2, 3, 4,
+    "fr_focf_workspace_bytes", "fr_focf_stage", 0, "fr_focf_stage", 0, "fr_focf_step_staged", 0, 4,
+    "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_workspace_bytes", "fr_focf_prepare_step", 11, 12,
+    "fr_focf_prepare_step", 1, "fr_focf_step_finish_staged", 0, "fr_focf_step_runs_pipe", 1, "fr_focf_workspace_bytes",
+    "fr_focf_prepare_step", 13, "fr_focf_step_runs_pipe", 11, 1, "fr_focf_workspace_bytes", "fr_focf_prepare_step", 14,
+    "fr_focf_step_runs_pipe", 12, 11, 1, "fr_focf_step_runs_pipe", 12, 11, "fr_focf_step_finish", 12,
+    "fr_focf_forward", 13, "fr_focf_backward_adam", 13, "fr_loss_accumulate", "fr_focf_prepare_step", 13,
+    "fr_focf_step_runs", 13, "fr_focf_workspace_bytes", "fr_focf_prepare_step", 14, "fr_focf_step_runs", 14, 13,
+    "fr_focf_runs_many", 0, 1, 2, 3, "fr_focf_workspace_bytes", "fr_focf_prepare_step", 4,
+    "fr_focf_step_runs_pipe", 4, 3, 2, "fr_focf_step_runs_pipe", 4, 3, "fr_focf_step_finish", 4, "fr_focf_predict",
+]
+
+
+def test_one_engine_through_every_change_of_path(monkeypatch):
+    """The hand-overs between the step forms on ONE engine -- staged, a queue cut short, the sorted prepare on the side
+    stream, both kinds of stash falling to the chain under clip_grad_norm, the library's loops, pipelined and two-launch
+    item runs, the chain with item runs pending -- against an engine that takes the same batches through the three-launch
+    chain: (a) tables and moments at the tolerance of schedules that split a row's replay differently, (b) the running loss
+    total, (c) the library calls, by name and workspace index, equal to the recorded list."""
+    from fairrec import _C
+    data = _every_path_data()
+    plain = _every_path_engine(data)
+    losses = []
+    for t, (u, i, r, s) in enumerate(data["seq"]):
+        loss, _ = plain.forward(u, i, r, s)
+        losses.append(loss[0].clone())
+        if t in data["clip_at"]:
+            plain.clip_grad_norm(1.0)
+        plain.backward_adam()
+    plain.flush()
+    plain.check_device_errors()
+    eng = _every_path_engine(data)
+    calls = []
+    recorder = _CallRecorder(_C.lib(), eng, calls)
+    with monkeypatch.context() as m:
+        m.setattr(_C, "lib", lambda: recorder)
+        T = _drive_through_every_path(eng, data)
+    for x, y in ((eng.U.weight, plain.U.weight), (eng.I.weight, plain.I.weight), (eng.U.m, plain.U.m), (eng.U.v, plain.U.v),
+                 (eng.I.m, plain.I.m), (eng.I.v, plain.I.v)):
+        torch.testing.assert_close(x, y, rtol=1e-4, atol=1e-6 * float(y.abs().max()) + 1e-12)
+    acc = eng.loss_acc.cpu().numpy()
+    np.testing.assert_allclose(float(acc[0]), float(torch.stack(losses).double().sum()), rtol=1e-4)
+    assert acc[3] == T and acc[4] == 0
+    assert calls == _EVERY_PATH_CALLS
