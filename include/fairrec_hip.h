@@ -1082,6 +1082,40 @@ FR_API int fr_topk_metrics_grouped(const int32_t* rec_topk, const int64_t* perm,
 FR_API size_t fr_gauc_grouped_workspace_bytes(int64_t n_users, int64_t n_groups);
 FR_API int fr_gauc_grouped(const int64_t* meanrank, const int64_t* perm, const int64_t* group_start, int64_t n_users,
                            int64_t n_groups, double* out, int64_t* kept, void* ws, size_t ws_bytes, void* stream);
+/* fr_exposure_grouped: the sums of the six exposure metrics (GiniIndex, ItemCoverage, ShannonEntropy, PopularityPercentage,
+ * TailPercentage, AveragePopularity @ k, metrics.py:438-821) per GROUP of users, for n_k cut-offs, in one chain; memory is
+ * O(entries), no [groups, items] table.
+ *   keys_sorted int64 [n_entries], n_entries = n_users * k_cols: the entry at rank r (0-based) of a user of group g with item i is
+ *   the key (g * n_items + i) * k_cols + r; the keys ascend.  Equal keys may occur; the sort need not be stable.  A CELL is the run
+ *   of entries with equal key / k_cols, one (group, item) pair; its count at cut-off ks[j] is c_j = the entries with r < ks[j],
+ *   found by a search for the key cell * k_cols + min(ks[j], k_cols), never by a walk of the cell.
+ *   group_start int64 [n_groups + 1] on the device: the users per group, cumulative; n_g = group_start[g+1] - group_start[g],
+ *   T_gj = n_g * ks[j] (ks[j] as given, also beyond k_cols).  ks: a HOST array, read by the entry, strictly ascending, >= 1,
+ *   1 <= n_k <= 8.  popular, tail uint8 [n_items] (any non-zero value is a flag), count_items int64 [n_items]: each may be NULL,
+ *   and its sum is then 0.
+ *   out_i int64 [n_groups][n_k][5] = { m, S, pop, tl, cnt }: m = the cells with c_j > 0 (distinct recommended items); S = the Gini
+ *   numerator, the sum over the n_items items of the catalogue sorted ascending by their count c_j in the group (the items without
+ *   an entry first, ties in any order) of (2 idx - n_items - 1) * c_j, idx 1-based, an exact integer; pop, tl, cnt = the sums over
+ *   the group's entries with r < ks[j] of popular[i] != 0, tail[i] != 0, count_items[i].  A count above n_g (a padded list repeats
+ *   item 0) is counted as it is, never clamped.
+ *   out_entropy double [n_groups][n_k] = sum over the cells of -p log(p), p = c_j / T_gj.  SUMMATION ORDER (a contract): with
+ *   h[c] = the cells of count c, term(c) = (double)h[c] * (-(q * log(q))), q = (double)c / ((double)n_g * (double)ks[j]), and +0.0
+ *   where h[c] = 0; the counts 1 .. n_g are cut into chunks of 256 consecutive counts, lane = count within the chunk; a chunk is
+ *   reduced per wave of 64 lanes by the xor butterfly (offsets 32, 16, .., 1) and its four wave sums are added in ascending wave
+ *   order; the chunk sums are added in ascending chunk order from 0.0; then the cells with c > n_g, sorted ascending by c, are
+ *   added one by one, each as 1.0 * (-(q * log(q))).
+ *   An empty group: five zeros and NaN.  Integer sums by integer atomics, the entropy without atomics: the same input gives the
+ *   same bits on every call.  Malformed keys (unsorted, group part >= n_groups) and a malformed group_start are clamped: unspecified
+ *   values, no access outside the arrays.
+ *   FR_EINVAL before anything is launched or written: a null pointer other than popular / tail / count_items, a size below 1,
+ *   n_entries no multiple of k_cols or >= 2^32, n_k outside 1..8, ks not strictly ascending or below 1, n_groups * n_items * k_cols
+ *   >= 2^63 (the key), n_items * n_users * k_cols >= 2^62 (the bound on |S|), ws below fr_exposure_grouped_workspace_bytes(n_users,
+ *   k_cols, n_groups, n_k), which is 0 for arguments out of range. */
+FR_API size_t fr_exposure_grouped_workspace_bytes(int64_t n_users, int32_t k_cols, int64_t n_groups, int32_t n_k);
+FR_API int fr_exposure_grouped(const int64_t* keys_sorted, int64_t n_entries, int64_t n_items, int32_t k_cols,
+                               const int64_t* group_start, int64_t n_groups, const int32_t* ks, int32_t n_k,
+                               const uint8_t* popular, const uint8_t* tail, const int64_t* count_items, int64_t* out_i,
+                               double* out_entropy, void* ws, size_t ws_bytes, void* stream);
 FR_API int fr_group_sums(const int64_t* perm, const int64_t* seg_start, int64_t n_segments, const int32_t* group,
                          const float* value, const float* wtrue, int32_t n_groups, double* stats, void* stream);
 FR_API size_t fr_fair_metrics_workspace_bytes(int64_t n_segments);

@@ -193,6 +193,9 @@ _PROTOS = {
                                         c_void_p]),
     "fr_gauc_grouped_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "fr_gauc_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_exposure_grouped_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64, c_int32]),
+    "fr_exposure_grouped": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, POINTER(c_int32), c_int32, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_group_sums": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "fr_fair_metrics_workspace_bytes": (c_size_t, [c_int64]),
     "fr_fair_metrics_from_stats": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -11,8 +11,9 @@ With 'gauc' among the metrics the three ranking branches also gather `rec.meanra
 tied rank is a half); without it they collect and launch what they did before.  `eval_args.mode: labeled` keeps `rec.score`
 and `data.label` per batch (eval_batch_collect_labeled).
 
-With `utility_by_group` set, every ranking branch also keeps `data.user.<attr>` -- the selected attributes, one value per row of
-`rec.topk` -- and the labeled branch `data.<attr>` per row; without the key the collected keys are what they were.
+With `utility_by_group` or `exposure_by_group` set, every ranking branch also keeps `data.user.<attr>` -- the attributes either
+key selects, one value per row of `rec.topk` -- and (`utility_by_group`) the labeled branch `data.<attr>` per row; without the
+keys the collected keys are what they were.
 
 `full_sort_eval: fused` feeds `eval_batch_collect_fused` the model's factors instead of the matrix (same keys, same values).
 """
@@ -25,18 +26,18 @@ import torch
 from .. import _C
 
 
-def utility_attrs(value, attrs) -> List[str]:
-    """`utility_by_group`: None / False = off ([]), True = every attribute of `sst_attr_list`, a list of names = those, each out
-    of `sst_attr_list`."""
+def utility_attrs(value, attrs, key='utility_by_group') -> List[str]:
+    """`utility_by_group` / `exposure_by_group` (`key`: the name the error messages use): None / False = off ([]), True = every
+    attribute of `sst_attr_list`, a list of names = those, each out of `sst_attr_list`."""
     if value is None or value is False:
         return []
     if value is True:
         return list(attrs)
     if not isinstance(value, (list, tuple)) or not all(isinstance(n, str) for n in value):
-        raise ValueError(f'utility_by_group must be True or a list of attribute names out of sst_attr_list, not {value!r}')
+        raise ValueError(f'{key} must be True or a list of attribute names out of sst_attr_list, not {value!r}')
     strangers = [n for n in value if n not in attrs]
     if strangers:
-        raise ValueError(f'utility_by_group: {strangers} not in sst_attr_list {list(attrs)}')
+        raise ValueError(f'{key}: {strangers} not in sst_attr_list {list(attrs)}')
     return list(dict.fromkeys(value))
 
 
@@ -46,7 +47,10 @@ class Collector:
         topk = config['topk'] or [10]
         self.topk = [topk] if isinstance(topk, int) else list(topk)
         self.sst = list(config['sst_attr_list'] or [])
-        self.utility = utility_attrs(config['utility_by_group'], self.sst)     # attributes kept per USER (`data.user.<attr>`)
+        self.utility = utility_attrs(config['utility_by_group'], self.sst)
+        self.exposure = utility_attrs(config['exposure_by_group'], self.sst, 'exposure_by_group')
+        # attributes kept per USER (`data.user.<attr>`): what either key selects
+        self.user_attrs = list(dict.fromkeys(self.utility + self.exposure))
         self.full = 'full' in (config['eval_args'] or {}).get('mode', 'full')
         self.meanrank = 'gauc' in [m.lower() for m in (config['metrics'] or [])]
         self._parts: Dict[str, List[torch.Tensor]] = {}
@@ -79,13 +83,14 @@ class Collector:
 
     def _attr(self, interaction, name):
         if name not in interaction:
-            raise ValueError(f"utility_by_group: the evaluation batches carry no column '{name}'")
+            raise ValueError(f"utility_by_group / exposure_by_group: the evaluation batches carry no column '{name}'")
         return interaction[name]
 
     def _add_user_attrs(self, interaction, dev, row_idx=None, n_users=None):
-        """`utility_by_group`: `data.user.<attr>`, one value per row of the batch's `rec.topk`.  `interaction` has one row per
-        user, or (row_idx given) one per candidate: every row of a user carries the user's value, scattered to its row."""
-        for s in self.utility:
+        """`utility_by_group` / `exposure_by_group`: `data.user.<attr>`, one value per row of the batch's `rec.topk`.  `interaction`
+        has one row per user, or (row_idx given) one per candidate: every row of a user carries the user's value, scattered to
+        its row."""
+        for s in self.user_attrs:
             col = self._attr(interaction, s).to(dev).reshape(-1)
             if row_idx is not None:
                 col = torch.zeros(n_users, dtype=col.dtype, device=dev).index_put_((row_idx,), col)

@@ -15,6 +15,10 @@ intersection of attributes (`sst_intersections`), with more than eight values).
 '<m> of <A>=<value>', and their '<m> gap | std | min of sensitive attribute <A>': group_topk_metrics (fr_topk_metrics_grouped),
 group_gauc (fr_gauc_grouped), group_value_metrics (the value kernels on each group's slice of the rows sorted by group).
 
+`exposure_by_group` (off by default) adds the six exposure metrics per group in the same key form, with '<m> max of sensitive
+attribute <A>' as well: group_exposure_metrics (csrc/exposure.hip: fr_exposure_grouped, every group and every k in one chain after
+ONE torch.sort of the keys (group, item, rank); no [groups, items] table).
+
 `eval_args.mode: labeled` is evaluation by value: 'auc', 'logloss', 'mae', 'rmse' of `rec.score` (what `predict` returned)
 against `data.label` (LABEL_FIELD), every row of the evaluation set (fr_value_metrics, fr_auc_sorted).  'gauc' is a ranking
 metric: it reads `rec.meanrank` (fr_eval_meanrank_segments) in the full / uniN / popN modes.
@@ -186,19 +190,36 @@ def gini_index(rec_items: torch.Tensor, num_items: int, topk) -> Dict[str, float
     return res
 
 
-def popularity_percentage(rec_items: torch.Tensor, count_items: torch.Tensor, topk, popularity_ratio=None) -> Dict[str, float]:
-    """PopularityPercentage@k (metrics.py:749-821): popular = top `ratio` fraction of the items that occur in training,
-    ordered by (count, id) descending, or the items with count >= ratio when ratio > 1."""
+def _popular_mask(count_items: torch.Tensor, popularity_ratio=None) -> torch.Tensor:
+    """bool [items]: the popular items of PopularityPercentage (see popularity_percentage)"""
     ratio = 0.1 if popularity_ratio is None or popularity_ratio <= 0 else popularity_ratio
     present = torch.nonzero(count_items > 0).view(-1)
     if ratio > 1:
-        popular = count_items >= ratio
+        return count_items >= ratio
+    cnt = count_items[present]
+    order = torch.sort(cnt * (count_items.numel() + 1) + present, descending=True).indices   # (count, id) descending
+    popular = torch.zeros_like(count_items, dtype=torch.bool)
+    popular[present[order[:max(int(present.numel() * ratio), 1)]]] = True
+    return popular
+
+
+def _tail_mask(count_items: torch.Tensor, tail_ratio=None) -> torch.Tensor:
+    """bool [items]: the long-tail items of TailPercentage (see tail_percentage)"""
+    ratio = 0.1 if tail_ratio is None or tail_ratio <= 0 else tail_ratio
+    present = torch.nonzero(count_items > 0).view(-1)
+    tail = torch.zeros_like(count_items, dtype=torch.bool)
+    if ratio > 1:
+        tail[present[count_items[present] <= ratio]] = True
     else:
-        cnt = count_items[present]
-        order = torch.sort(cnt * (count_items.numel() + 1) + present, descending=True).indices   # (count, id) descending
-        popular = torch.zeros_like(count_items, dtype=torch.bool)
-        popular[present[order[:max(int(present.numel() * ratio), 1)]]] = True
-    hit = popular[rec_items].to(torch.float64)
+        order = torch.sort(count_items[present] * (count_items.numel() + 1) + present).indices       # (count, id) ascending
+        tail[present[order[:max(int(present.numel() * ratio), 1)]]] = True
+    return tail
+
+
+def popularity_percentage(rec_items: torch.Tensor, count_items: torch.Tensor, topk, popularity_ratio=None) -> Dict[str, float]:
+    """PopularityPercentage@k (metrics.py:749-821): popular = top `ratio` fraction of the items that occur in training,
+    ordered by (count, id) descending, or the items with count >= ratio when ratio > 1."""
+    hit = _popular_mask(count_items, popularity_ratio)[rec_items].to(torch.float64)
     avg = (hit.cumsum(dim=1) / torch.arange(1, hit.shape[1] + 1, device=hit.device, dtype=torch.float64)).mean(dim=0).cpu()
     return {f'popularitypercentage@{k}': float(avg[k - 1]) for k in topk}
 
@@ -234,15 +255,7 @@ def shannon_entropy(rec_items, topk) -> Dict[str, float]:
 def tail_percentage(rec_items, count_items, topk, tail_ratio=None) -> Dict[str, float]:
     """TailPercentage@k (metrics.py:664-747): share of long-tail items; tail = the bottom `ratio` fraction of the items
     that occur in training ordered by (count, id) ascending, or the items with count <= ratio when ratio > 1."""
-    ratio = 0.1 if tail_ratio is None or tail_ratio <= 0 else tail_ratio
-    present = torch.nonzero(count_items > 0).view(-1)
-    tail = torch.zeros_like(count_items, dtype=torch.bool)
-    if ratio > 1:
-        tail[present[count_items[present] <= ratio]] = True
-    else:
-        order = torch.sort(count_items[present] * (count_items.numel() + 1) + present).indices       # (count, id) ascending
-        tail[present[order[:max(int(present.numel() * ratio), 1)]]] = True
-    return _mean_at_k(tail[rec_items], 'tailpercentage', topk)
+    return _mean_at_k(_tail_mask(count_items, tail_ratio)[rec_items], 'tailpercentage', topk)
 
 
 def value_metrics(score: torch.Tensor, label: torch.Tensor, names: Iterable[str]) -> Dict[str, float]:
@@ -370,6 +383,76 @@ def group_value_metrics(score: torch.Tensor, label: torch.Tensor, group_index: t
     return res
 
 
+EXPOSURE_NAMES = ("giniindex", "itemcoverage", "shannonentropy", "popularitypercentage", "tailpercentage", "averagepopularity")
+EXPOSURE_MAX_K = 8     # cut-offs per fr_exposure_grouped call
+
+
+def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n_groups: int, num_items: int, count_items,
+                           topk: Iterable[int], names: Iterable[str], popularity_ratio=None, tail_ratio=None):
+    """The exposure metrics of `names` per group of users: {'<name>@<k>': [n_groups values]}, what gini_index, item_coverage,
+    shannon_entropy, popularity_percentage, tail_percentage and average_popularity give on each group's rows of `rec_items`.
+    group_index[u] in [0, n_groups) is the group of row u.  ONE sort of the keys (group * num_items + item) * K + rank, then one
+    library call for every group, metric and k (fr_exposure_grouped; up to EXPOSURE_MAX_K cut-offs a call): exact integer sums
+    and the entropy sum per (group, k), finished in float64 on the host with the operations of the ungrouped functions.  No host
+    read of the group sizes for the launch; memory is O(list entries).  An empty group: NaN everywhere."""
+    lib = _C.lib()
+    names = [n.lower() for n in names]
+    stranger = [n for n in names if n not in EXPOSURE_NAMES]
+    if stranger:
+        raise ValueError(f'group_exposure_metrics: {stranger} are no exposure metrics {EXPOSURE_NAMES}')
+    items = rec_items.to(torch.int64)
+    U, K = items.shape
+    G, N = int(n_groups), int(num_items)
+    if group_index.numel() != U:
+        raise ValueError(f'group_exposure_metrics: {group_index.numel()} group indices for {U} rows')
+    if G * N * K >= 2 ** 63:
+        raise ValueError(f'group_exposure_metrics: {G} groups x {N} items x {K} ranks do not fit the int64 sort key')
+    dev = items.device
+    gidx = group_index.reshape(-1).to(torch.int64)
+    keys = torch.sort((((gidx[:, None] * N + items) * K) + torch.arange(K, device=dev, dtype=torch.int64)).reshape(-1)).values
+    start = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(gidx, minlength=G)[:G], 0, out=start[1:])
+    popular = _popular_mask(count_items, popularity_ratio).to(torch.uint8).contiguous() if 'popularitypercentage' in names else None
+    tail = _tail_mask(count_items, tail_ratio).to(torch.uint8).contiguous() if 'tailpercentage' in names else None
+    counts = count_items.to(torch.int64).contiguous() if 'averagepopularity' in names else None
+    ks = sorted(set(int(k) for k in topk))
+    sums, entropy = {}, {}
+    for lo in range(0, len(ks), EXPOSURE_MAX_K):
+        part = ks[lo:lo + EXPOSURE_MAX_K]
+        n_k = len(part)
+        out_i = torch.empty((G, n_k, 5), dtype=torch.int64, device=dev)
+        out_e = torch.empty((G, n_k), dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.fr_exposure_grouped_workspace_bytes(U, K, G, n_k), dtype=torch.uint8, device=dev)
+        _C.check(lib.fr_exposure_grouped(keys.data_ptr(), U * K, N, K, start.data_ptr(), G, (_C.c_int32 * n_k)(*part), n_k,
+                                         _C.ptr(popular), _C.ptr(tail), _C.ptr(counts), out_i.data_ptr(), out_e.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _C.current_stream()), "fr_exposure_grouped")
+        out_i, out_e = out_i.cpu().tolist(), out_e.cpu().tolist()
+        for j, k in enumerate(part):
+            sums[k] = [out_i[g][j] for g in range(G)]
+            entropy[k] = [out_e[g][j] for g in range(G)]
+    bounds = start.cpu().tolist()
+    nan = float('nan')
+    res = {}
+    for name in names:
+        for k in topk:
+            vals = []
+            for g in range(G):
+                n_g = bounds[g + 1] - bounds[g]
+                m, S, pop, tl, cnt = sums[int(k)][g]
+                if n_g == 0:
+                    vals.append(nan)
+                elif name == 'giniindex':
+                    vals.append(float(S) / float(n_g * k) / N)
+                elif name == 'itemcoverage':
+                    vals.append(m / N)
+                elif name == 'shannonentropy':
+                    vals.append(entropy[int(k)][g] / m if m else nan)
+                else:       # Python integers: the one division is correctly rounded
+                    vals.append({'popularitypercentage': pop, 'tailpercentage': tl, 'averagepopularity': cnt}[name] / (n_g * k))
+            res[f'{name}@{k}'] = vals
+    return res
+
+
 def _value_name(v: float) -> str:
     return str(int(v)) if float(v).is_integer() else repr(float(v))
 
@@ -406,6 +489,10 @@ class Evaluator:
         self.intersections = self._intersections(config['sst_intersections'], list(config['sst_attr_list'] or []))
         from .collector import utility_attrs
         self.utility = utility_attrs(config['utility_by_group'], list(config['sst_attr_list'] or []))
+        self.exposure = utility_attrs(config['exposure_by_group'], list(config['sst_attr_list'] or []), 'exposure_by_group')
+        if self.exposure and self.mode == 'labeled':
+            raise ValueError("exposure_by_group needs eval_args.mode full / uniN / popN, not 'labeled': the exposure metrics "
+                             "read the ranked lists")
 
     @staticmethod
     def _intersections(entries, attrs):
@@ -465,17 +552,48 @@ class Evaluator:
                     res[k] = v
         if self.utility:
             res.update(self._utility_by_group(collected))
+        if self.exposure:
+            res.update(self._exposure_by_group(collected))
         return {k: round(v, self.decimal_place) for k, v in res.items()}
 
     def _utility_by_group(self, collected) -> Dict[str, float]:
         """`utility_by_group`: every requested top-k / gauc / value metric per group of each selected attribute, and of each
         `sst_intersections` entry whose attributes are all selected: '<m> of <A>=<value>' per group, '<m> gap | std | min of
         sensitive attribute <A>' (max - min, population std, worst group; float64 on the host, NaN if a group is NaN)."""
-        import numpy as np
         labeled = self.mode == 'labeled'
-        prefix = 'data.' if labeled else 'data.user.'
+        res = {}
+        for name, gidx, labels in self._groups(collected, self.utility, 'data.' if labeled else 'data.user.'):
+            G = len(labels)
+            by_group = {}
+            if labeled:
+                by_group.update(group_value_metrics(collected['rec.score'], collected['data.label'], gidx, G,
+                                                    [m for m in self.metrics if m in self.VALUE]))
+            if "gauc" in self.metrics:
+                by_group['gauc'] = group_gauc(collected['rec.meanrank'], gidx, G)
+            if self.TOPK & set(self.metrics):
+                allk = group_topk_metrics(collected['rec.topk'], gidx, G, self.topk)
+                by_group.update({k: v for k, v in allk.items() if k.split('@')[0] in self.metrics})
+            self._report_groups(res, name, labels, by_group, ('gap', 'std', 'min'))
+        return res
+
+    def _exposure_by_group(self, collected) -> Dict[str, float]:
+        """`exposure_by_group`: every requested exposure metric and k per group of each selected attribute, and of each
+        `sst_intersections` entry whose attributes are all selected, in the key form of `_utility_by_group`, and '<m>@<k> max of
+        sensitive attribute <A>' as well (for most of these metrics the larger value is the worse one)."""
+        names = [m for m in EXPOSURE_NAMES if m in self.metrics]
+        res = {}
+        for name, gidx, labels in self._groups(collected, self.exposure, 'data.user.'):
+            by_group = group_exposure_metrics(collected['rec.items'], gidx, len(labels), collected['data.num_items'],
+                                              collected.get('data.count_items'), self.topk, names, self.config['popularity_ratio'],
+                                              self.config['tail_ratio']) if names else {}
+            self._report_groups(res, name, labels, by_group, ('gap', 'std', 'min', 'max'))
+        return res
+
+    def _groups(self, collected, selected, prefix):
+        """[(name, group index per row, value labels)] of the `selected` attributes (columns `prefix + name`) and of every
+        `sst_intersections` entry whose attributes are all selected; an attribute or intersection with one value is refused."""
         index, values, groups = {}, {}, []
-        for name in self.utility:
+        for name in selected:
             col = collected[prefix + name].reshape(-1)
             vals, inv = torch.unique(col, sorted=True, return_inverse=True)
             index[name], values[name] = inv.to(torch.int64), [_value_name(v) for v in vals.cpu().tolist()]
@@ -486,25 +604,21 @@ class Evaluator:
                 tuples, inv = torch.unique(torch.stack([index[n] for n in names], dim=1), dim=0, return_inverse=True)
                 labels = ['&'.join(values[n][j] for n, j in zip(names, row)) for row in tuples.cpu().tolist()]
                 groups.append(('&'.join(names), inv, labels))
-        res = {}
-        for name, gidx, labels in groups:
-            G = len(labels)
-            if G < 2:
+        for name, _, labels in groups:
+            if len(labels) < 2:
                 raise ValueError(f'there is only one value for {name} sensitive attribute')
-            by_group = {}
-            if labeled:
-                by_group.update(group_value_metrics(collected['rec.score'], collected['data.label'], gidx, G,
-                                                    [m for m in self.metrics if m in self.VALUE]))
-            if "gauc" in self.metrics:
-                by_group['gauc'] = group_gauc(collected['rec.meanrank'], gidx, G)
-            if self.TOPK & set(self.metrics):
-                allk = group_topk_metrics(collected['rec.topk'], gidx, G, self.topk)
-                by_group.update({k: v for k, v in allk.items() if k.split('@')[0] in self.metrics})
-            for m, per_group in by_group.items():
-                v = np.asarray(per_group, dtype=np.float64)
-                for label, x in zip(labels, per_group):
-                    res[f'{m} of {name}={label}'] = float(x)
-                res[f'{m} gap of sensitive attribute {name}'] = float(v.max() - v.min())
-                res[f'{m} std of sensitive attribute {name}'] = float(v.std())
-                res[f'{m} min of sensitive attribute {name}'] = float(v.min())
+        return groups
+
+    @staticmethod
+    def _report_groups(res, name, labels, by_group, summaries):
+        """'<m> of <A>=<value>' per group and '<m> <summary> of sensitive attribute <A>': max - min, population std, the
+        smallest, the largest group value; float64 on the host, NaN if a group is NaN"""
+        import numpy as np
+        for m, per_group in by_group.items():
+            v = np.asarray(per_group, dtype=np.float64)
+            for label, x in zip(labels, per_group):
+                res[f'{m} of {name}={label}'] = float(x)
+            for what in summaries:
+                res[f'{m} {what} of sensitive attribute {name}'] = float(
+                    {'gap': v.max() - v.min(), 'std': v.std(), 'min': v.min(), 'max': v.max()}[what])
         return res
