@@ -7,8 +7,8 @@ G <= 8) on the same positives.
 Positives: item ids Zipf-distributed (probability of the r-th most popular item ~ 1 / r) over ids 1 .. items - 1, group
 indices uniform, scores uniform in [0, 1), all from one seeded generator.  Device events around each part, 5 warm calls, then
 the median of 20.  Prints one JSON line per G.  The steps are the wrapper's own (fairrec/evaluator/metrics.py `_df_wide` /
-`_group_sums` + `_from_stats`), restated here so that an event can stand between them; the script checks that the restated
-steps return the wrapper's result bit for bit before it times anything.
+`_item_sums` + `_from_stats`), split here so that an event can stand between the index work and the kernels; the script checks
+that the split steps return the wrapper's result bit for bit before it times anything.
 """
 import argparse
 import json
@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "recbole-fairrec_amd"))
 
 from fairrec import _C                                        # noqa: E402
 from fairrec.evaluator import metrics as M                    # noqa: E402
+from fairrec.evaluator.groups import item_segments            # noqa: E402
 
 
 def positives(n, n_items, G, seed=0):
@@ -36,50 +37,38 @@ def positives(n, n_items, G, seed=0):
 
 
 def wide_parts(items, gidx, value, G):
-    lib, dev = _C.lib(), value.device
+    dev = value.device
 
     def index():
         skey, perm = torch.sort(items.to(torch.int64) * G + gidx.to(torch.int64), stable=True)
         item_of = torch.div(skey, G, rounding_mode='floor')
-        _, counts = torch.unique_consecutive(item_of, return_counts=True)
-        K = counts.numel()
-        item_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=item_start[1:])
+        K, item_start = item_segments(item_of)
         return K, item_start, (skey - item_of * G).to(torch.int32), value[perm].contiguous()
 
     def kernel(K, item_start, group, val):
         out = torch.empty(1, dtype=torch.float64, device=dev)
-        ws = torch.empty(lib.fr_df_cells_workspace_bytes(K), dtype=torch.uint8, device=dev)
-        _C.check(lib.fr_df_cells(0, item_start.data_ptr(), K, group.data_ptr(), val.data_ptr(), G, out.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), _C.current_stream()), "fr_df_cells")
+        _C.call('df_cells', 0, item_start.data_ptr(), K, group.data_ptr(), val.data_ptr(), G, out.data_ptr(), ws=(K,), device=dev)
         return out
 
     return index, kernel, lambda: M._df_wide(items, gidx, value, G)
 
 
 def dense_parts(items, gidx, value, G):
-    lib, dev = _C.lib(), value.device
+    dev = value.device
 
     def index():
         keys, perm = torch.sort(items, stable=True)
-        _, counts = torch.unique_consecutive(keys, return_counts=True)
-        K = counts.numel()
-        seg_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=seg_start[1:])
+        K, seg_start = item_segments(keys)
         return K, seg_start, perm
 
     def kernel(K, seg_start, perm):
-        stats = torch.empty((K, G, 3), dtype=torch.float64, device=dev)
-        _C.check(lib.fr_group_sums(perm.data_ptr(), seg_start.data_ptr(), K, gidx.data_ptr(), value.data_ptr(), 0, G,
-                                   stats.data_ptr(), _C.current_stream()), "fr_group_sums")
+        stats = M._group_sums(perm, seg_start, K, gidx, value, None, G)
         out = torch.empty(5, dtype=torch.float64, device=dev)
-        ws = torch.empty(lib.fr_fair_metrics_workspace_bytes(K), dtype=torch.uint8, device=dev)
-        _C.check(lib.fr_fair_metrics_from_stats(stats.data_ptr(), K, G, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _C.current_stream()), "fr_fair_metrics_from_stats")
+        _C.call('fair_metrics_from_stats', stats.data_ptr(), K, G, out.data_ptr(), ws=(K,), ws_of='fair_metrics', device=dev)
         return out[4:]
 
     def wrapper():
-        st, K = M._group_sums(items, gidx, value, None, G)
+        st, K = M._item_sums(items, gidx, value, None, G)
         return float(M._from_stats(st, K, G)[4])
 
     return index, kernel, wrapper

@@ -44,6 +44,22 @@ __device__ __forceinline__ float wave_sum(float x) {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
     return x;  // every lane holds the total; fixed butterfly order => deterministic
 }
+// the same butterfly for the evaluation kernels' accumulators (metrics.hip, exposure.hip)
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+__device__ __forceinline__ int wave_sum(int x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+__device__ __forceinline__ long long wave_sum(long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
 
 template <int W>
 __device__ __forceinline__ float group_sum(float x) {  // sum over aligned groups of W lanes

@@ -15,7 +15,7 @@
 //
 // Every cross-thread sum is an integer (atomics, order-independent); the entropy is summed in a fixed order without atomics:
 // the same input gives the same bits on every call.
-#include "common.hpp"
+#include "eval_common.hpp"
 
 namespace fr {
 
@@ -27,28 +27,6 @@ constexpr int EX_SKIP = 8;          // fold: chunks of 256 counts loaded per bar
 struct ExCuts {
     int k[EX_MAX_K];
 };
-
-__device__ __forceinline__ long long ex_wave_sum_ll(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ int ex_wave_sum_i(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// group g's range of users, clamped into [0, U] (a malformed table: unspecified values, no access outside the arrays)
-__device__ __forceinline__ void ex_group_range(const int64_t* __restrict__ group_start, long long g, long long U, long long& lo,
-                                               long long& n) {
-    long long a = group_start[g], b = group_start[g + 1];
-    a = a < 0 ? 0 : (a > U ? U : a);
-    b = b < 0 ? 0 : (b > U ? U : b);
-    lo = a;
-    n = b > a ? b - a : 0;
-}
 
 // the first position in [lo, n) whose key is >= target, galloping from lo: O(log(distance)) loads
 __device__ __forceinline__ long long ex_lower_bound_from(const int64_t* __restrict__ keys, long long lo, long long n,
@@ -121,7 +99,9 @@ __global__ __launch_bounds__(EX_THREADS) void exposure_heads_kernel(
                     }
             }
             cur = g;
-            ex_group_range(group_start, g, U, cur_seg, cur_ng);
+            long long hi;
+            group_range(group_start, g, U, cur_seg, hi);
+            cur_ng = hi - cur_seg;
             cur_seg += g;
         }
         const int pv = (popular && popular[item] ? 1 : 0) | (tail && tail[item] ? 1 << 16 : 0);
@@ -159,9 +139,9 @@ __global__ __launch_bounds__(EX_THREADS) void exposure_heads_kernel(
 #pragma unroll
         for (int j = 0; j < EX_MAX_K; ++j)
             if (j < n_k) {
-                const int spt = ex_wave_sum_i(mine ? pt[j] : 0);       // at most 64 * EX_PER_THREAD < 2^16 per half
-                const long long scn = ex_wave_sum_ll(mine ? cn[j] : 0);
-                const int sn1 = ex_wave_sum_i(mine ? n1[j] : 0);
+                const int spt = wave_sum(mine ? pt[j] : 0);       // at most 64 * EX_PER_THREAD < 2^16 per half
+                const long long scn = wave_sum(mine ? cn[j] : 0);
+                const int sn1 = wave_sum(mine ? n1[j] : 0);
                 if (lane == leader) {
                     unsigned long long* a = acc + (gl * n_k + j) * 3;
                     if (spt & 0xffff) atomicAdd(a, (unsigned long long)(spt & 0xffff));
@@ -188,8 +168,9 @@ __global__ __launch_bounds__(EX_THREADS) void exposure_fold_kernel(
 #pragma unroll
     for (int q = 0; q < EX_MAX_K; ++q)
         if (q == j) kj = ks.k[q];
-    long long lo, n_g;
-    ex_group_range(group_start, g, U, lo, n_g);
+    long long lo, hi;
+    group_range(group_start, g, U, lo, hi);
+    const long long n_g = hi - lo;
     if (n_g == 0) {                         // an empty group: five zeros, NaN entropy
         if (t < 5) out_i[b * 5 + t] = 0;
         if (t == 5) out_entropy[b] = __longlong_as_double(0x7ff8000000000000LL);
@@ -203,7 +184,7 @@ __global__ __launch_bounds__(EX_THREADS) void exposure_fold_kernel(
     // m: the distinct items
     long long mine = 0;
     for (long long c = 1 + t; c <= n_g; c += EX_THREADS) mine += seg[c];
-    mine = ex_wave_sum_ll(mine);
+    mine = wave_sum(mine);
     if (lane == 0) sh_ll[wave] = mine;
     __syncthreads();
     const long long m = sh_ll[0] + sh_ll[1] + sh_ll[2] + sh_ll[3] + n_ovf;
@@ -255,7 +236,7 @@ __global__ __launch_bounds__(EX_THREADS) void exposure_fold_kernel(
             H += ((sh_d[0] + sh_d[1]) + sh_d[2]) + sh_d[3];
         }
     }
-    S = ex_wave_sum_ll(S);
+    S = wave_sum(S);
     __syncthreads();
     if (lane == 0) sh_ll[wave] = S;
     __syncthreads();

@@ -23,15 +23,22 @@
 //   * DifferentialFairness: a pair of table entries one of whose float32 logarithms is NaN (a non-positive entry, from a
 //     negative score sum) does not enter the item's maximum, and the result stays finite; numpy's maximum in the
 //     reference's formula would return NaN there (oracle.metrics.differential_fairness does).
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "kernels.hpp"
 
 namespace fr {
 
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
+// A block of four waves adds up through LDS: every wave leaves its total in red4[wave] (wave_sum_to_lds), and after the
+// caller's barrier block_sum4 folds the four in wave order, ((w0 + w1) + w2) + w3 -- the one association every block sum here has.
+template <class T>
+__device__ __forceinline__ void wave_sum_to_lds(T v, T* __restrict__ red4) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+}
+
+template <class T>
+__device__ __forceinline__ T block_sum4(const T* __restrict__ red4) {
+    return ((red4[0] + red4[1]) + red4[2]) + red4[3];
 }
 
 // The per-user terms of the six top-k metrics of one wave of 64 rows and their butterfly sums: lane = one row of `rec_topk`
@@ -64,8 +71,8 @@ __device__ __forceinline__ void topk_wave_terms(const int32_t* __restrict__ rec_
         // MAP (metrics.py:100-139): sum over the hits so far of Precision@j, over min(k + 1, min(positives, K))
         if (hit) sum_pre += (double)csum / (double)(k + 1);
         const double v5 = ok && ilen > 0 ? sum_pre / (double)(k + 1 < ilen ? k + 1 : ilen) : 0.0;
-        const double s0 = wave_sum_d(v0), s1 = wave_sum_d(v1), s2 = wave_sum_d(v2), s3 = wave_sum_d(v3),
-                     s4 = wave_sum_d(v4), s5 = wave_sum_d(v5);
+        const double s0 = wave_sum(v0), s1 = wave_sum(v1), s2 = wave_sum(v2), s3 = wave_sum(v3),
+                     s4 = wave_sum(v4), s5 = wave_sum(v5);
         if (lane == 0) {
             out[0 * K + k] = s0;
             out[1 * K + k] = s1;
@@ -89,16 +96,9 @@ __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restr
 // Group g's members are the rows perm[group_start[g] .. group_start[g+1]) (perm NULL: identity).  Its range is cut into chunks
 // of 64 consecutive positions; chunk_start[g] = number of chunks of the groups before g, so chunk c of group g is block
 // chunk_start[g] + c of the main grid, which has ceil(U / 64) + G blocks -- at least as many as there are chunks -- and finds
-// its (group, chunk) by binary search.  Everything read from group_start and perm is clamped into [0, U]: a malformed table gives
-// unspecified values, never an address outside the inputs or the workspace (chunk_start is clamped to the grid as well).
-__device__ __forceinline__ long long clamp_ll(long long x, long long lo, long long hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-__device__ __forceinline__ void group_range(const int64_t* __restrict__ group_start, long long g, long long U, long long& lo,
-                                            long long& hi) {
-    lo = clamp_ll(group_start[g], 0, U);
-    hi = clamp_ll(group_start[g + 1], lo, U);
-}
-
+// its (group, chunk) by binary search.  Everything read from group_start (group_range, eval_common.hpp) and perm is clamped into
+// [0, U]: a malformed table gives unspecified values, never an address outside the inputs or the workspace (chunk_start is clamped
+// to the grid as well).
 static constexpr int CS_THREADS = 256;
 
 // chunk_start[0 .. G]: the exclusive scan of ceil(n_g / 64), by ONE block (a thread scans a contiguous run of groups)
@@ -185,12 +185,6 @@ __global__ __launch_bounds__(256) void group_fold_kernel(const double* __restric
     out[t] = a;
 }
 
-__device__ __forceinline__ int wave_sum_i(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // GAUC's sums per chunk from the `rec.meanrank` triples { 2 * pos_rank_sum, user_len, pos_len }: a user with a positive and a
 // negative adds auc_u * pos_len and pos_len, auc_u = pair / ((user_len - pos_len) * pos_len) with pair = (user_len + 1) *
 // pos_len - pos_len * (pos_len + 1) / 2 - pos_rank_sum (evaluator.gauc); numerator and denominator are integers (both doubled),
@@ -216,8 +210,8 @@ __global__ __launch_bounds__(64) void gauc_grouped_kernel(const int64_t* __restr
         weight = (double)pos_len;
         term = auc_u * weight;
     }
-    const double s0 = wave_sum_d(term), s1 = wave_sum_d(weight);
-    const int n0 = wave_sum_i(keep ? 1 : 0), n1 = wave_sum_i(no_pos ? 1 : 0), n2 = wave_sum_i(no_neg ? 1 : 0);
+    const double s0 = wave_sum(term), s1 = wave_sum(weight);
+    const int n0 = wave_sum(keep ? 1 : 0), n1 = wave_sum(no_pos ? 1 : 0), n2 = wave_sum(no_neg ? 1 : 0);
     if (lane == 0) {
         part_d[(size_t)blockIdx.x * 2] = s0;
         part_d[(size_t)blockIdx.x * 2 + 1] = s1;
@@ -357,17 +351,11 @@ __global__ __launch_bounds__(256) void fair_from_stats_kernel(const double* __re
         }
         t[4] = (double)eps;
     }
-    __shared__ double red[4][5];
+    __shared__ double red[5][4];
 #pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        const double w = wave_sum_d(t[q]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = w;
-    }
+    for (int q = 0; q < 5; ++q) wave_sum_to_lds(t[q], red[q]);
     __syncthreads();
-    if (threadIdx.x < 5) {
-        const int q = threadIdx.x;
-        part[(size_t)blockIdx.x * 5 + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-    }
+    if (threadIdx.x < 5) part[(size_t)blockIdx.x * 5 + threadIdx.x] = block_sum4(red[threadIdx.x]);
 }
 
 // ---- DifferentialFairness for any number of groups: a walk over the sorted (item, group) cells, no items x groups table ----------
@@ -588,12 +576,6 @@ __global__ __launch_bounds__(256) void eval_lookup_segments_kernel(const int64_t
 // Reference: recbole/evaluator/metrics.py AUC / MAE / RMSE / LogLoss over the concatenated (score, label) columns.
 constexpr int VM_THREADS = 256, VM_ROWS = 2048, VM_MAXBLOCKS = 2048;
 
-__device__ __forceinline__ long long wave_sum_ll(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // block b walks rows b*256 + t, + blocks*256, ... in that order (a fixed assignment for a given n): part_d[b][0..2] = sum |e|, sum e^2, LogLoss
 // sum of its rows, part_i[b] = its number of rows with label == 1
 __global__ __launch_bounds__(VM_THREADS) void value_partials_kernel(const float* __restrict__ score, const float* __restrict__ label,
@@ -622,24 +604,15 @@ __global__ __launch_bounds__(VM_THREADS) void value_partials_kernel(const float*
             pos += y == 1.0 ? 1 : 0;
         }
     }
-    __shared__ double red_d[4][3];
+    __shared__ double red_d[3][4];
     __shared__ long long red_i[4];
-    a = wave_sum_d(a);
-    q = wave_sum_d(q);
-    l = wave_sum_d(l);
-    pos = wave_sum_ll(pos);
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        red_d[w][0] = a;
-        red_d[w][1] = q;
-        red_d[w][2] = l;
-        red_i[w] = pos;
-    }
+    wave_sum_to_lds(a, red_d[0]);
+    wave_sum_to_lds(q, red_d[1]);
+    wave_sum_to_lds(l, red_d[2]);
+    wave_sum_to_lds(pos, red_i);
     __syncthreads();
-    if (threadIdx.x < 3)
-        part_d[(size_t)blockIdx.x * 3 + threadIdx.x] =
-            ((red_d[0][threadIdx.x] + red_d[1][threadIdx.x]) + red_d[2][threadIdx.x]) + red_d[3][threadIdx.x];
-    if (threadIdx.x == 3) part_i[blockIdx.x] = ((red_i[0] + red_i[1]) + red_i[2]) + red_i[3];
+    if (threadIdx.x < 3) part_d[(size_t)blockIdx.x * 3 + threadIdx.x] = block_sum4(red_d[threadIdx.x]);
+    if (threadIdx.x == 3) part_i[blockIdx.x] = block_sum4(red_i);
 }
 
 // one block: thread t folds partials t, t + 256, ... in that order, then the fixed butterfly; counts = n, positives
@@ -654,23 +627,16 @@ __global__ __launch_bounds__(VM_THREADS) void value_fold_kernel(const double* __
         v[2] += part_d[(size_t)b * 3 + 2];
         pos += part_i[b];
     }
-    __shared__ double red_d[4][3];
+    __shared__ double red_d[3][4];
     __shared__ long long red_i[4];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = wave_sum_d(v[c]);
-    pos = wave_sum_ll(pos);
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        red_d[w][0] = v[0];
-        red_d[w][1] = v[1];
-        red_d[w][2] = v[2];
-        red_i[w] = pos;
-    }
+    for (int c = 0; c < 3; ++c) wave_sum_to_lds(v[c], red_d[c]);
+    wave_sum_to_lds(pos, red_i);
     __syncthreads();
-    if (threadIdx.x < 3) out[threadIdx.x] = ((red_d[0][threadIdx.x] + red_d[1][threadIdx.x]) + red_d[2][threadIdx.x]) + red_d[3][threadIdx.x];
+    if (threadIdx.x < 3) out[threadIdx.x] = block_sum4(red_d[threadIdx.x]);
     if (threadIdx.x == 3) {
         counts[0] = n;
-        counts[1] = ((red_i[0] + red_i[1]) + red_i[2]) + red_i[3];
+        counts[1] = block_sum4(red_i);
     }
 }
 
@@ -694,7 +660,7 @@ __device__ __forceinline__ int block_excl_scan(int v, int* total, int* lds4) {
     __syncthreads();
     int base = 0;
     for (int q = 0; q < w; ++q) base += lds4[q];
-    *total = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+    *total = block_sum4(lds4);
     __syncthreads();
     return base + inc - v;
 }
@@ -776,10 +742,9 @@ __global__ __launch_bounds__(AUC_THREADS) void auc_runs_kernel(const float* __re
         acc += ((e - j) - (ce - cs)) * (cs + ce);
     }
     __shared__ long long red[4];
-    acc = wave_sum_ll(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    wave_sum_to_lds(acc, red);
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (threadIdx.x == 0) part[blockIdx.x] = block_sum4(red);
 }
 
 // out = 2U (the tiles' parts in tile order per thread, then the fixed butterfly), P, Nn
@@ -788,12 +753,11 @@ __global__ __launch_bounds__(AUC_THREADS) void auc_fold_kernel(const long long* 
     long long acc = 0;
     for (long long b = threadIdx.x; b < tiles; b += AUC_THREADS) acc += part[b];
     __shared__ long long red[4];
-    acc = wave_sum_ll(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    wave_sum_to_lds(acc, red);
     __syncthreads();
     if (threadIdx.x == 0) {
         const long long nn = C[n];
-        out[0] = ((red[0] + red[1]) + red[2]) + red[3];
+        out[0] = block_sum4(red);
         out[1] = n - nn;
         out[2] = nn;
     }
@@ -852,8 +816,8 @@ __global__ __launch_bounds__(256) void eval_meanrank_segments_kernel(const int64
             if ((!items || first[j]) && sc > -INFINITY) pairs += (sc > sp ? 2 : 0) + (sc == sp ? 1 : 0);
         }
     }
-    user_len = wave_sum_ll(user_len);
-    pairs = wave_sum_ll(pairs);
+    user_len = wave_sum(user_len);
+    pairs = wave_sum(pairs);
     if (lane == 0) {
         out[u * 3 + 0] = pairs + pos_len;
         out[u * 3 + 1] = user_len;

@@ -402,6 +402,18 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def call(name: str, *args, ws=None, ws_of=None, device=None):
+    """fr_<name>(*args[, workspace, its bytes], the current stream), checked.  `ws`: the size arguments of
+    fr_<ws_of or name>_workspace_bytes.  The workspace is a torch allocation on `device`, released when this returns: torch's allocator
+    hands it out again in the order of the stream the kernels were launched on."""
+    handle = lib()
+    if ws is not None:
+        import torch
+        buf = torch.empty(getattr(handle, f"fr_{ws_of or name}_workspace_bytes")(*ws), dtype=torch.uint8, device=device)
+        args += (buf.data_ptr(), buf.numel())
+    check(getattr(handle, "fr_" + name)(*args, current_stream()), "fr_" + name)
+
+
 _SIDE = {}
 
 

@@ -16,6 +16,8 @@ key selects, one value per row of `rec.topk` -- and (`utility_by_group`) the lab
 keys the collected keys are what they were.
 
 `full_sort_eval: fused` feeds `eval_batch_collect_fused` the model's factors instead of the matrix (same keys, same values).
+
+The three ranking branches differ in how they rank; each ends in `_finish_ranking` (the hit flags and the keys every branch adds).
 """
 from __future__ import annotations
 
@@ -108,20 +110,15 @@ class Collector:
     def _meanrank(self, seg, items, scores, pos_keys, n_items):
         """`rec.meanrank` of a batch: one launch, a wave per user (items None: dense rows); pos_keys = the sorted keys
         row * n_items + item of the batch's positives, as fr_eval_hits takes them."""
-        lib = _C.lib()
         U, n_rows = seg.numel() - 1, scores.numel()
-        pos_keys = pos_keys.contiguous()
         out = torch.empty((U, 3), dtype=torch.int64, device=scores.device)
-        ws = None if items is None else torch.empty(lib.fr_eval_meanrank_workspace_bytes(n_rows), dtype=torch.uint8,
+        ws = None if items is None else torch.empty(_C.lib().fr_eval_meanrank_workspace_bytes(n_rows), dtype=torch.uint8,
                                                     device=scores.device)
-        _C.check(lib.fr_eval_meanrank_segments(seg.data_ptr(), U, _C.ptr(items), scores.data_ptr(), pos_keys.data_ptr(),
-                                               pos_keys.numel(), n_items, n_rows, out.data_ptr(), _C.ptr(ws),
-                                               0 if ws is None else ws.numel(), _C.current_stream()),
-                 "fr_eval_meanrank_segments")
+        _C.call('eval_meanrank_segments', seg.data_ptr(), U, _C.ptr(items), scores.data_ptr(), pos_keys.data_ptr(), pos_keys.numel(),
+                n_items, n_rows, out.data_ptr(), _C.ptr(ws), 0 if ws is None else ws.numel())
         self._add('rec.meanrank', out)
 
     def eval_batch_collect(self, scores: torch.Tensor, interaction, positive_u: torch.Tensor, positive_i: torch.Tensor):
-        lib = _C.lib()
         U, n_items = scores.shape
         K = min(max(self.topk), n_items)
         positive_u, positive_i = positive_u.to(scores.device, torch.int64), positive_i.to(scores.device, torch.int64)
@@ -132,20 +129,12 @@ class Collector:
         if tied.numel():
             topk_idx[tied] = self._host_topk(scores[tied], K).to(scores.device)
         keys = torch.sort(positive_u * n_items + positive_i).values
-        rec = torch.empty((U, K + 1), dtype=torch.int32, device=scores.device)
-        _C.check(lib.fr_eval_hits(topk_idx.data_ptr(), U, K, n_items, keys.data_ptr(), keys.numel(), rec.data_ptr(),
-                                  _C.current_stream()), "fr_eval_hits")
         if self.meanrank:
             # the dense masked rows as they are: row u * n_items + i is the cell of item i
             seg = torch.arange(U + 1, device=scores.device, dtype=torch.int64) * n_items
             self._meanrank(seg, None, scores.to(torch.float32).contiguous().view(-1), keys, n_items)
-        self._add('rec.topk', rec)
-        self._add('rec.items', topk_idx)
-        self._add('rec.positive_score', scores[positive_u, positive_i])
-        self._add('data.positive_i', positive_i)
-        for s in self.sst:
-            if s in interaction:
-                self._add('data.' + s, interaction[s].to(scores.device)[positive_u])
+        self._finish_ranking(topk_idx, keys, scores[positive_u, positive_i], positive_i, interaction, positive_u, K, n_items, U,
+                             scores.device)
         self._add_user_attrs(interaction, scores.device)
 
     def eval_batch_collect_fused(self, factors, interaction, hist_indptr: torch.Tensor, hist_items: torch.Tensor,
@@ -159,7 +148,6 @@ class Collector:
         the cells against them tile by tile (fr_recommend_meanrank)."""
         from ..functional import recommend_cells, recommend_meanrank, recommend_topk
         from ..utils.case_study import DENSE_ROWS_BYTES, history_csr
-        lib = _C.lib()
         X, W = factors['X'], factors['W']
         ub = factors.get('user_bias')
         kw = dict(item_bias=factors.get('item_bias'), bias0=factors.get('bias0', 0.0), epilogue=factors.get('epilogue', 0),
@@ -182,20 +170,12 @@ class Collector:
                                    hist_items=hi, want_scores=True, **kw)[2]
             topk_idx[rows] = self._host_topk(dense, K).to(dev)
         keys = torch.sort(positive_u * n_items + positive_i).values
-        rec = torch.empty((U, K + 1), dtype=torch.int32, device=dev)
-        _C.check(lib.fr_eval_hits(topk_idx.data_ptr(), U, K, n_items, keys.data_ptr(), keys.numel(), rec.data_ptr(),
-                                  _C.current_stream()), "fr_eval_hits")
         if self.meanrank:
             self._add('rec.meanrank', recommend_meanrank(X, W, keys, self._err, user_bias=ub, hist_indptr=hist_indptr,
                                                          hist_items=hist_items, **kw))
-        self._add('rec.topk', rec)
-        self._add('rec.items', topk_idx)
-        self._add('rec.positive_score', recommend_cells(X, W, positive_u, positive_i, self._err, user_bias=ub,
-                                                        hist_indptr=hist_indptr, hist_items=hist_items, **kw))
-        self._add('data.positive_i', positive_i)
-        for s in self.sst:
-            if s in interaction:
-                self._add('data.' + s, interaction[s].to(dev)[positive_u])
+        cells = recommend_cells(X, W, positive_u, positive_i, self._err, user_bias=ub, hist_indptr=hist_indptr, hist_items=hist_items,
+                                **kw)
+        self._finish_ranking(topk_idx, keys, cells, positive_i, interaction, positive_u, K, n_items, U, dev)
         self._add_user_attrs(interaction, dev)
 
     def check_device_errors(self):
@@ -214,7 +194,6 @@ class Collector:
         -- including the ones that land on -inf -- is a binary search (missing = -inf).  `rec.negative_score` /
         `data.negative_i` / `data.<sst>` follow the reference's row arithmetic literally: rows [P, 2P) of the batch and
         the first P rows, P = number of positives in the batch."""
-        lib = _C.lib()
         dev = origin_scores.device
         iid = self.config['ITEM_ID_FIELD']
         items = interaction[iid].to(dev, torch.int64)
@@ -222,6 +201,8 @@ class Collector:
         positive_u, positive_i = positive_u.to(dev, torch.int64), positive_i.to(dev, torch.int64)
         U = int(positive_u[-1].item()) + 1                                    # batch_user_num, trainer.py:453
         K = max(self.topk)
+        P = positive_u.numel()
+        pos_keys = torch.sort(positive_u * n_items + positive_i).values
         self._add_user_attrs(interaction, dev, row_idx, U)
         if K <= 62 and (row_idx.numel() < 2 or bool((row_idx[1:] >= row_idx[:-1]).all())):
             # The evaluation loaders emit a batch user by user: a user's candidates are a contiguous segment, and the whole
@@ -232,29 +213,30 @@ class Collector:
             seg = torch.searchsorted(row_idx, torch.arange(U + 1, device=dev, dtype=torch.int64)).contiguous()
             topk_idx = torch.empty((U, K), dtype=torch.int64, device=dev)
             flags = torch.empty(U, dtype=torch.int32, device=dev)
-            st = _C.current_stream()
-            _C.check(lib.fr_eval_topk_segments(seg.data_ptr(), U, items.data_ptr(), sc.data_ptr(), K, topk_idx.data_ptr(),
-                                               flags.data_ptr(), st), "fr_eval_topk_segments")
+            _C.call('eval_topk_segments', seg.data_ptr(), U, items.data_ptr(), sc.data_ptr(), K, topk_idx.data_ptr(), flags.data_ptr())
             # users whose list hangs on an exact tie (or who have fewer than K + 1 distinct candidates): their rows of the reference's
             # dense -inf matrix are ranked on the host, in torch.topk's CPU order (csrc/topk_host.hip)
-            tied = flags.nonzero().view(-1)
-            if tied.numel():
-                slot = torch.full((U,), -1, dtype=torch.int64, device=dev)
-                slot[tied] = torch.arange(tied.numel(), device=dev)
-                sel = slot[row_idx] >= 0
-                dense = torch.full((tied.numel(), n_items), -float('inf'), dtype=torch.float32, device=dev)
-                dense[slot[row_idx[sel]], items[sel]] = sc[sel]
-                topk_idx[tied] = self._host_topk(dense, K).to(dev)
+            self._rank_tied_on_host(topk_idx, flags.nonzero().view(-1), row_idx, items, sc, n_items, K)
 
             def lookup(rows, its):
                 rows, its = rows.contiguous(), its.contiguous()
                 out = torch.empty(rows.numel(), dtype=torch.float32, device=dev)
-                _C.check(lib.fr_eval_lookup_segments(seg.data_ptr(), U, items.data_ptr(), sc.data_ptr(), rows.data_ptr(),
-                                                     its.data_ptr(), rows.numel(), out.data_ptr(), st), "fr_eval_lookup_segments")
+                _C.call('eval_lookup_segments', seg.data_ptr(), U, items.data_ptr(), sc.data_ptr(), rows.data_ptr(), its.data_ptr(),
+                        rows.numel(), out.data_ptr())
                 return out.to(origin_scores.dtype)
             if self.meanrank:
-                self._meanrank(seg, items, sc, torch.sort(positive_u * n_items + positive_i).values, n_items)
-            return self._finish_candidates(topk_idx, lookup, interaction, items, positive_u, positive_i, n_items, U, K, dev)
+                self._meanrank(seg, items, sc, pos_keys, n_items)
+        else:
+            topk_idx, lookup = self._rank_candidates_general(origin_scores, row_idx, items, pos_keys, n_items, U, K)
+        self._finish_ranking(topk_idx, pos_keys, lookup(positive_u, positive_i), positive_i, interaction, slice(P), K, n_items, U, dev)
+        neg_items = items[P:2 * P]
+        self._add('rec.negative_score', lookup(positive_u[:neg_items.numel()], neg_items))
+        self._add('data.negative_i', neg_items)
+
+    def _rank_candidates_general(self, origin_scores, row_idx, items, pos_keys, n_items, U, K):
+        """The general form of `eval_batch_collect_candidates`, for a batch whose rows are not grouped by user, or K > 62: the
+        lists [U, K] and the lookup in the (row, item) -> score map; adds `rec.meanrank` when it is collected."""
+        dev = origin_scores.device
         keys, order = torch.sort(row_idx * n_items + items, stable=True)
         first = torch.ones_like(keys, dtype=torch.bool)
         first[1:] = keys[1:] != keys[:-1]
@@ -265,7 +247,6 @@ class Collector:
             p = torch.searchsorted(ckeys, q).clamp_(max=ckeys.numel() - 1)
             return torch.where(ckeys[p] == q, cscore[p], torch.full_like(cscore[p], -float('inf')))
 
-        # (the general form, for a batch whose rows are not grouped by user, or K > 62)
         # ranking among a user's candidates: stable sort by score (descending) inside each row
         o1 = torch.sort(cscore, descending=True, stable=True).indices
         o2 = torch.sort((ckeys // n_items)[o1], stable=True).indices
@@ -283,17 +264,23 @@ class Collector:
         pair = (rrow[1:] == rrow[:-1]) & (sr[1:] == sr[:-1]) & (rank[1:] <= K)
         cnt = torch.bincount(rrow, minlength=U)
         tied = torch.unique(torch.cat([rrow[1:][pair], (cnt < min(K + 1, n_items)).nonzero().view(-1)]))
-        if tied.numel():
-            slot = torch.full((U,), -1, dtype=torch.int64, device=dev)
-            slot[tied] = torch.arange(tied.numel(), device=dev)
-            crow = ckeys // n_items
-            sel = slot[crow] >= 0
-            dense = torch.full((tied.numel(), n_items), -float('inf'), dtype=torch.float32, device=dev)
-            dense[slot[crow[sel]], (ckeys % n_items)[sel]] = cscore[sel].to(torch.float32)
-            topk_idx[tied] = self._host_topk(dense, K).to(dev)
+        self._rank_tied_on_host(topk_idx, tied, ckeys // n_items, ckeys % n_items, cscore, n_items, K)
         if self.meanrank:
-            self._add('rec.meanrank', self._meanrank_general(ckeys, cscore, positive_u * n_items + positive_i, n_items, U))
-        return self._finish_candidates(topk_idx, lookup, interaction, items, positive_u, positive_i, n_items, U, K, dev)
+            self._add('rec.meanrank', self._meanrank_general(ckeys, cscore, pos_keys, n_items, U))
+        return topk_idx, lookup
+
+    def _rank_tied_on_host(self, topk_idx, tied, rows, items, scores, n_items, K):
+        """the lists of the `tied` users, in place: their candidates (user row rows[r], item items[r], score scores[r]) scattered
+        into their rows of the reference's dense -inf matrix, ranked in torch.topk's CPU order (_host_topk)"""
+        if not tied.numel():
+            return
+        dev = topk_idx.device
+        slot = torch.full((topk_idx.shape[0],), -1, dtype=torch.int64, device=dev)
+        slot[tied] = torch.arange(tied.numel(), device=dev)
+        sel = slot[rows] >= 0
+        dense = torch.full((tied.numel(), n_items), -float('inf'), dtype=torch.float32, device=dev)
+        dense[slot[rows[sel]], items[sel]] = scores[sel].to(torch.float32)
+        topk_idx[tied] = self._host_topk(dense, K).to(dev)
 
     @staticmethod
     def _meanrank_general(ckeys, cscore, pos_keys, n_items, U):
@@ -319,23 +306,19 @@ class Collector:
         out[:, 2] = torch.bincount(r[pos], minlength=U)
         return out
 
-    def _finish_candidates(self, topk_idx, lookup, interaction, items, positive_u, positive_i, n_items, U, K, dev):
-        lib = _C.lib()
-        pos_keys = torch.sort(positive_u * n_items + positive_i).values
+    def _finish_ranking(self, topk_idx, pos_keys, positive_score, positive_i, interaction, sst_rows, K, n_items, U, dev):
+        """Where a ranking batch is finished, whichever branch ranked it: the hit flags of the lists against the SORTED positive keys
+        row * n_items + item (fr_eval_hits), then `rec.topk`, `rec.items`, `rec.positive_score`, `data.positive_i` and `data.<sst>`
+        (rows `sst_rows` of the batch's columns: the positives' user rows, or the reference's [:P] in the candidates branch)."""
         rec = torch.empty((U, K + 1), dtype=torch.int32, device=dev)
-        _C.check(lib.fr_eval_hits(topk_idx.data_ptr(), U, K, n_items, pos_keys.data_ptr(), pos_keys.numel(), rec.data_ptr(),
-                                  _C.current_stream()), "fr_eval_hits")
-        P = positive_u.numel()
+        _C.call('eval_hits', topk_idx.data_ptr(), U, K, n_items, pos_keys.data_ptr(), pos_keys.numel(), rec.data_ptr())
         self._add('rec.topk', rec)
         self._add('rec.items', topk_idx)
-        self._add('rec.positive_score', lookup(positive_u, positive_i))
+        self._add('rec.positive_score', positive_score)
         self._add('data.positive_i', positive_i)
-        neg_items = items[P:2 * P]
-        self._add('rec.negative_score', lookup(positive_u[:neg_items.numel()], neg_items))
-        self._add('data.negative_i', neg_items)
         for s in self.sst:
             if s in interaction:
-                self._add('data.' + s, interaction[s].to(dev)[:P])
+                self._add('data.' + s, interaction[s].to(dev)[sst_rows])
 
     def get_data_struct(self) -> Dict[str, torch.Tensor]:
         out = {k: torch.cat(v, dim=0) for k, v in self._parts.items()}

@@ -7,7 +7,8 @@ Inputs are the arrays the reference's Collector gathers (collector.py:131-205), 
   pos_score, pos_i                        score and item id of every positive (user, item) pair
   neg_score, neg_i                        (uni100-style modes) the first len(pos) negatives of the batch order
   sst[<name>]                             the user's attribute value per positive pair
-The torch ops here are index plumbing (sort / unique of the id columns); every reduction is a HIP kernel
+The torch ops here are index plumbing (sort / unique of the id columns; the groups of an attribute or intersection and their
+segments are built in groups.py, nowhere else); every reduction is a HIP kernel
 (csrc/metrics.hip: fr_topk_metrics, fr_group_sums, fr_fair_metrics_from_stats; fr_df_cells for an attribute, or an
 intersection of attributes (`sst_intersections`), with more than eight values).
 
@@ -28,76 +29,57 @@ from __future__ import annotations
 from logging import getLogger
 from typing import Dict, Iterable, Optional
 
+import numpy as np
 import torch
 
 from .. import _C
+from .groups import attribute_groups, group_segments, item_segments
 
-
-def topk_metrics(rec_topk: torch.Tensor, topk: Iterable[int]) -> Dict[str, float]:
-    lib = _C.lib()
-    rec = rec_topk.to(torch.int32).contiguous()
-    U, K = rec.shape[0], rec.shape[1] - 1
-    out = torch.empty(6 * K, dtype=torch.float64, device=rec.device)
-    ws = torch.empty(lib.fr_topk_metrics_workspace_bytes(U, K), dtype=torch.uint8, device=rec.device)
-    _C.check(lib.fr_topk_metrics(rec.data_ptr(), U, K, out.data_ptr(), ws.data_ptr(), ws.numel(), _C.current_stream()),
-             "fr_topk_metrics")
-    vals = out.view(6, K).cpu()
-    res = {}
-    for m, name in enumerate(("hit", "mrr", "ndcg", "recall", "precision", "map")):
-        for k in topk:
-            res[f"{name}@{k}"] = float(vals[m, k - 1])
-    return res
-
-
-def _group_index(sst: torch.Tensor):
-    """np.unique(sst_value, return_inverse=True): group index = rank of the value among the values present."""
-    vals, inv = torch.unique(sst, sorted=True, return_inverse=True)
-    return int(vals.numel()), inv.to(torch.int32).contiguous()
-
-
-def _group_sums(items: Optional[torch.Tensor], group, value, wtrue, G):
-    """stats [K, G, 3] over the distinct items (items = None: one segment)."""
-    lib = _C.lib()
-    dev = value.device
-    n = value.numel()
-    if items is None:
-        perm, seg_start, K = None, torch.tensor([0, n], dtype=torch.int64, device=dev), 1
-    else:
-        keys, perm = torch.sort(items, stable=True)
-        _, counts = torch.unique_consecutive(keys, return_counts=True)
-        K = counts.numel()
-        seg_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=seg_start[1:])
-    stats = torch.empty((K, G, 3), dtype=torch.float64, device=dev)
-    _C.check(lib.fr_group_sums(_C.ptr(perm), seg_start.data_ptr(), K, group.data_ptr(), value.contiguous().data_ptr(),
-                               _C.ptr(wtrue), G, stats.data_ptr(), _C.current_stream()), "fr_group_sums")
-    return stats, K
-
-
-def _from_stats(stats, K, G):
-    lib = _C.lib()
-    out = torch.empty(5, dtype=torch.float64, device=stats.device)
-    ws = torch.empty(lib.fr_fair_metrics_workspace_bytes(K), dtype=torch.uint8, device=stats.device)
-    _C.check(lib.fr_fair_metrics_from_stats(stats.data_ptr(), K, G, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _C.current_stream()), "fr_fair_metrics_from_stats")
-    return out.cpu()
-
-
+TOPK_NAMES = ("hit", "mrr", "ndcg", "recall", "precision", "map")
+EXPOSURE_NAMES = ("giniindex", "itemcoverage", "shannonentropy", "popularitypercentage", "tailpercentage", "averagepopularity")
+EXPOSURE_MAX_K = 8     # cut-offs per fr_exposure_grouped call
 NARROW_GROUPS = 8      # fr_group_sums / fr_fair_metrics_from_stats keep a segment's per-group sums in registers: n_groups <= 8
 
 
+def topk_metrics(rec_topk: torch.Tensor, topk: Iterable[int]) -> Dict[str, float]:
+    rec = rec_topk.to(torch.int32).contiguous()
+    U, K = rec.shape[0], rec.shape[1] - 1
+    out = torch.empty(6 * K, dtype=torch.float64, device=rec.device)
+    _C.call('topk_metrics', rec.data_ptr(), U, K, out.data_ptr(), ws=(U, K), device=rec.device)
+    vals = out.view(6, K).cpu()
+    return {f"{name}@{k}": float(vals[m, k - 1]) for m, name in enumerate(TOPK_NAMES) for k in topk}
+
+
+def _group_sums(perm: Optional[torch.Tensor], seg_start, K, group, value, wtrue, G):
+    """stats [K, G, 3] of fr_group_sums over the K segments of `perm` (None: the rows as they are)"""
+    value = value.contiguous()
+    stats = torch.empty((K, G, 3), dtype=torch.float64, device=value.device)
+    _C.call('group_sums', _C.ptr(perm), seg_start.data_ptr(), K, group.data_ptr(), value.data_ptr(), _C.ptr(wtrue), G, stats.data_ptr())
+    return stats
+
+
+def _item_sums(items: Optional[torch.Tensor], group, value, wtrue, G):
+    """stats [K, G, 3] over the distinct items (items = None: one segment), and K"""
+    if items is None:
+        return _group_sums(None, torch.tensor([0, value.numel()], dtype=torch.int64, device=value.device), 1, group, value, wtrue, G), 1
+    keys, perm = torch.sort(items, stable=True)
+    K, seg_start = item_segments(keys)
+    return _group_sums(perm, seg_start, K, group, value, wtrue, G), K
+
+
+def _from_stats(stats, K, G):
+    out = torch.empty(5, dtype=torch.float64, device=stats.device)
+    _C.call('fair_metrics_from_stats', stats.data_ptr(), K, G, out.data_ptr(), ws=(K,), ws_of='fair_metrics',
+            device=stats.device)
+    return out.cpu()
+
+
 def _group_means_wide(gidx, value, G):
-    """the G group means for G > NARROW_GROUPS, from fr_group_sums with the roles swapped: the GROUPS are its segments (a
-    stable argsort of the group index, the G + 1 group boundaries), every member sits in its one group 0."""
-    lib = _C.lib()
-    dev = value.device
-    perm = torch.sort(gidx, stable=True).indices
-    seg_start = torch.zeros(G + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(torch.bincount(gidx.to(torch.int64), minlength=G), 0, out=seg_start[1:])
-    zero = torch.zeros(value.numel(), dtype=torch.int32, device=dev)
-    stats = torch.empty((G, 1, 3), dtype=torch.float64, device=dev)
-    _C.check(lib.fr_group_sums(perm.data_ptr(), seg_start.data_ptr(), G, zero.data_ptr(), value.data_ptr(), 0, 1,
-                               stats.data_ptr(), _C.current_stream()), "fr_group_sums")
+    """the G group means for G > NARROW_GROUPS, from fr_group_sums with the roles swapped: the GROUPS are its segments, every
+    member sits in its one group 0."""
+    perm, seg_start = group_segments(gidx, G)
+    zero = torch.zeros(value.numel(), dtype=torch.int32, device=value.device)
+    stats = _group_sums(perm, seg_start, G, zero, value, None, 1)
     return (stats[:, 0, 0] / stats[:, 0, 1]).cpu()
 
 
@@ -105,20 +87,13 @@ def _df_wide(items, gidx, value, G):
     """DifferentialFairness for G > NARROW_GROUPS: ONE stable sort of the key item * G + group, the item boundaries from the
     sorted keys, then fr_df_cells walks the (item, group) cells -- no [items, G] table.  The members are handed over in sorted
     order (perm = NULL), so the walk reads its two columns front to back."""
-    lib = _C.lib()
-    dev = value.device
     skey, perm = torch.sort(items.to(torch.int64) * G + gidx.to(torch.int64), stable=True)
     item_of = torch.div(skey, G, rounding_mode='floor')
-    _, counts = torch.unique_consecutive(item_of, return_counts=True)
-    K = counts.numel()
-    item_start = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=item_start[1:])
+    K, item_start = item_segments(item_of)
     group = (skey - item_of * G).to(torch.int32)
     val = value[perm].contiguous()
-    out = torch.empty(1, dtype=torch.float64, device=dev)
-    ws = torch.empty(lib.fr_df_cells_workspace_bytes(K), dtype=torch.uint8, device=dev)
-    _C.check(lib.fr_df_cells(0, item_start.data_ptr(), K, group.data_ptr(), val.data_ptr(), G, out.data_ptr(), ws.data_ptr(),
-                             ws.numel(), _C.current_stream()), "fr_df_cells")
+    out = torch.empty(1, dtype=torch.float64, device=value.device)
+    _C.call('df_cells', 0, item_start.data_ptr(), K, group.data_ptr(), val.data_ptr(), G, out.data_ptr(), ws=(K,), device=value.device)
     return float(out.cpu()[0])
 
 
@@ -126,11 +101,11 @@ def _nonparity_and_df(res, name, G, gidx, pos_score, pos_i):
     """the two metrics every attribute (and every intersection of attributes) gets; the path is chosen by G"""
     if G <= NARROW_GROUPS:
         # NonParity (metrics.py:864-882): |difference| of the two group means, population std for more groups
-        st, _ = _group_sums(None, gidx, pos_score, None, G)
+        st, _ = _item_sums(None, gidx, pos_score, None, G)
         means = (st[0, :, 0] / st[0, :, 1]).cpu()
         res[f'NonParity Unfairness of sensitive attribute {name}'] = float(
             (means[0] - means[1]).abs() if G == 2 else means.std(unbiased=False))
-        st, K = _group_sums(pos_i, gidx, pos_score, None, G)
+        st, K = _item_sums(pos_i, gidx, pos_score, None, G)
         res[f'Differential Fairness of sensitive attribute {name}'] = float(_from_stats(st, K, G)[4])
     else:
         means = _group_means_wide(gidx, pos_score, G)
@@ -143,18 +118,13 @@ def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=N
     """NonParity + DifferentialFairness per attribute, any number of values; Value / Absolute / Under / Over unfairness on the
     FIRST attribute (as the reference's classes read `sst_attr_list[0]`, metrics.py:905), which has to be binary.
     `intersections`: lists of attribute names out of `sst`; each adds NonParity + DifferentialFairness 'of sensitive attribute
-    a&b', whose groups are the distinct value tuples present among the rows."""
+    a&b', whose groups are the distinct value tuples present among the rows (groups.attribute_groups)."""
     res = {}
     pos_score = pos_score.to(torch.float32).contiguous()
-    first = True
-    index = {}
-    for name, col in sst.items():
-        G, gidx = _group_index(col)
-        index[name] = gidx
-        if G < 2:
-            raise ValueError(f'there is only one value for {name} sensitive attribute')
+    for n, (name, index, G, _) in enumerate(attribute_groups(sst, intersections)):
+        gidx = index.to(torch.int32).contiguous()
         _nonparity_and_df(res, name, G, gidx, pos_score, pos_i)
-        if first and value_type:
+        if n == 0 and value_type:
             if G != 2:
                 raise ValueError('sensitive attribute must be binary')
             P = pos_score.numel()
@@ -167,15 +137,10 @@ def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=N
                 wtrue = torch.cat([torch.ones(P, device=value.device), torch.zeros(m, device=value.device)])
             else:
                 items, value, group, wtrue = pos_i, pos_score, gidx, torch.ones(P, device=pos_score.device)
-            st, K = _group_sums(items, group.contiguous(), value.contiguous(), wtrue.contiguous(), 2)
+            st, K = _item_sums(items, group.contiguous(), value.contiguous(), wtrue.contiguous(), 2)
             v = _from_stats(st, K, 2)
             for q, label in enumerate(("Value", "Absolute", "Underestimation", "Overestimation")):
                 res[f'{label} Unfairness of sensitive attribute {name}'] = float(v[q])
-        first = False
-    for names in intersections or ():
-        # equal tuples of group indices <=> equal tuples of values
-        tuples, inv = torch.unique(torch.stack([index[n].to(torch.int64) for n in names], dim=1), dim=0, return_inverse=True)
-        _nonparity_and_df(res, '&'.join(names), int(tuples.shape[0]), inv.to(torch.int32).contiguous(), pos_score, pos_i)
     return res
 
 
@@ -262,11 +227,10 @@ def value_metrics(score: torch.Tensor, label: torch.Tensor, names: Iterable[str]
     """metrics.py AUC / LogLoss / MAE / RMSE over the concatenated (score, label) columns.  The sums and the AUC's integer
     counts come from the device (one pass each; the AUC after ONE torch.sort of the score column), the last division and
     square root are float64 on the host.  AUC without a positive or without a negative row: nan and a warning."""
-    lib = _C.lib()
     names = [n.lower() for n in names]
     score = score.reshape(-1).to(torch.float32).contiguous()
     label = label.reshape(-1).to(torch.float32).contiguous()
-    n, dev, st = score.numel(), score.device, _C.current_stream()
+    n, dev = score.numel(), score.device
     if label.numel() != n or n < 1:
         raise ValueError(f'value metrics need as many labels as scores and at least one row (got {n} scores, {label.numel()} labels)')
     if n >= 2 ** 31:
@@ -275,9 +239,7 @@ def value_metrics(score: torch.Tensor, label: torch.Tensor, names: Iterable[str]
     if {'logloss', 'mae', 'rmse'} & set(names):
         out = torch.empty(3, dtype=torch.float64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        ws = torch.empty(lib.fr_value_metrics_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        _C.check(lib.fr_value_metrics(score.data_ptr(), label.data_ptr(), n, out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), st), "fr_value_metrics")
+        _C.call('value_metrics', score.data_ptr(), label.data_ptr(), n, out.data_ptr(), counts.data_ptr(), ws=(n,), device=dev)
         sums = out.cpu().tolist()
         res['mae'] = sums[0] / n
         res['rmse'] = (sums[1] / n) ** 0.5
@@ -285,9 +247,8 @@ def value_metrics(score: torch.Tensor, label: torch.Tensor, names: Iterable[str]
     if 'auc' in names:
         srt, order = torch.sort(score)
         out = torch.empty(3, dtype=torch.int64, device=dev)
-        ws = torch.empty(lib.fr_auc_sorted_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        _C.check(lib.fr_auc_sorted(srt.data_ptr(), label[order].contiguous().data_ptr(), n, out.data_ptr(), ws.data_ptr(),
-                                   ws.numel(), st), "fr_auc_sorted")
+        by_score = label[order].contiguous()     # (named: it has to outlive the call's workspace allocation)
+        _C.call('auc_sorted', srt.data_ptr(), by_score.data_ptr(), n, out.data_ptr(), ws=(n,), device=dev)
         two_u, P, Nn = out.cpu().tolist()
         if P == 0 or Nn == 0:
             getLogger().warning('AUC: the evaluation set has no %s row (label %s 1); the result is nan',
@@ -319,32 +280,17 @@ def gauc(meanrank: torch.Tensor) -> float:
     return float((auc_u * pos_len).sum() / pos_len.sum())
 
 
-TOPK_NAMES = ("hit", "mrr", "ndcg", "recall", "precision", "map")
-
-
-def _group_segments(group_index: torch.Tensor, n_groups: int):
-    """groups as segments (the form of _group_means_wide): perm = a stable sort of the group index, group_start = the cumulative
-    bincount, both on the device"""
-    gidx = group_index.reshape(-1).to(torch.int64)
-    perm = torch.sort(gidx, stable=True).indices.contiguous()
-    start = torch.zeros(n_groups + 1, dtype=torch.int64, device=gidx.device)
-    torch.cumsum(torch.bincount(gidx, minlength=n_groups)[:n_groups], 0, out=start[1:])
-    return perm, start
-
-
 def group_topk_metrics(rec_topk: torch.Tensor, group_index: torch.Tensor, n_groups: int, topk: Iterable[int]):
     """`topk_metrics` per group of users: {'<name>@<k>': [n_groups values]}.  group_index[u] in [0, n_groups) is the group of row
     u of `rec_topk`; one launch chain for all groups (fr_topk_metrics_grouped), no host read of the group sizes."""
-    lib = _C.lib()
     rec = rec_topk.to(torch.int32).contiguous()
     U, K = rec.shape[0], rec.shape[1] - 1
     if group_index.numel() != U:
         raise ValueError(f'group_topk_metrics: {group_index.numel()} group indices for {U} rows')
-    perm, start = _group_segments(group_index, n_groups)
+    perm, start = group_segments(group_index, n_groups)
     out = torch.empty(n_groups * 6 * K, dtype=torch.float64, device=rec.device)
-    ws = torch.empty(lib.fr_topk_metrics_grouped_workspace_bytes(U, K, n_groups), dtype=torch.uint8, device=rec.device)
-    _C.check(lib.fr_topk_metrics_grouped(rec.data_ptr(), perm.data_ptr(), start.data_ptr(), U, K, n_groups, out.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), _C.current_stream()), "fr_topk_metrics_grouped")
+    _C.call('topk_metrics_grouped', rec.data_ptr(), perm.data_ptr(), start.data_ptr(), U, K, n_groups, out.data_ptr(),
+            ws=(U, K, n_groups), device=rec.device)
     vals = out.view(n_groups, 6, K).cpu()
     return {f"{name}@{k}": [float(vals[g, m, k - 1]) for g in range(n_groups)] for m, name in enumerate(TOPK_NAMES) for k in topk}
 
@@ -352,17 +298,15 @@ def group_topk_metrics(rec_topk: torch.Tensor, group_index: torch.Tensor, n_grou
 def group_gauc(meanrank: torch.Tensor, group_index: torch.Tensor, n_groups: int):
     """`gauc` per group of users from `rec.meanrank`: [n_groups values], NaN for a group whose users are all dropped
     (fr_gauc_grouped: the two sums per group on the device, the one quotient in float64 on the host)."""
-    lib = _C.lib()
     mr = meanrank.to(torch.int64).contiguous()
     U = mr.shape[0]
     if group_index.numel() != U:
         raise ValueError(f'group_gauc: {group_index.numel()} group indices for {U} rows')
-    perm, start = _group_segments(group_index, n_groups)
+    perm, start = group_segments(group_index, n_groups)
     out = torch.empty((n_groups, 2), dtype=torch.float64, device=mr.device)
     kept = torch.empty((n_groups, 3), dtype=torch.int64, device=mr.device)
-    ws = torch.empty(lib.fr_gauc_grouped_workspace_bytes(U, n_groups), dtype=torch.uint8, device=mr.device)
-    _C.check(lib.fr_gauc_grouped(mr.data_ptr(), perm.data_ptr(), start.data_ptr(), U, n_groups, out.data_ptr(), kept.data_ptr(),
-                                 ws.data_ptr(), ws.numel(), _C.current_stream()), "fr_gauc_grouped")
+    _C.call('gauc_grouped', mr.data_ptr(), perm.data_ptr(), start.data_ptr(), U, n_groups, out.data_ptr(), kept.data_ptr(),
+            ws=(U, n_groups), device=mr.device)
     return [s / w if w > 0 else float('nan') for s, w in out.cpu().tolist()]
 
 
@@ -371,7 +315,7 @@ def group_value_metrics(score: torch.Tensor, label: torch.Tensor, group_index: t
     contiguous slice goes through the kernels of `value_metrics`.  A group with one label class: AUC NaN; an empty group: NaN."""
     names = [n.lower() for n in names]
     score, label = score.reshape(-1), label.reshape(-1)
-    perm, start = _group_segments(group_index, n_groups)
+    perm, start = group_segments(group_index, n_groups)
     score, label = score[perm], label[perm]
     bounds = start.cpu().tolist()
     res = {n: [] for n in names}
@@ -383,10 +327,6 @@ def group_value_metrics(score: torch.Tensor, label: torch.Tensor, group_index: t
     return res
 
 
-EXPOSURE_NAMES = ("giniindex", "itemcoverage", "shannonentropy", "popularitypercentage", "tailpercentage", "averagepopularity")
-EXPOSURE_MAX_K = 8     # cut-offs per fr_exposure_grouped call
-
-
 def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n_groups: int, num_items: int, count_items,
                            topk: Iterable[int], names: Iterable[str], popularity_ratio=None, tail_ratio=None):
     """The exposure metrics of `names` per group of users: {'<name>@<k>': [n_groups values]}, what gini_index, item_coverage,
@@ -395,7 +335,6 @@ def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n
     library call for every group, metric and k (fr_exposure_grouped; up to EXPOSURE_MAX_K cut-offs a call): exact integer sums
     and the entropy sum per (group, k), finished in float64 on the host with the operations of the ungrouped functions.  No host
     read of the group sizes for the launch; memory is O(list entries).  An empty group: NaN everywhere."""
-    lib = _C.lib()
     names = [n.lower() for n in names]
     stranger = [n for n in names if n not in EXPOSURE_NAMES]
     if stranger:
@@ -410,8 +349,7 @@ def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n
     dev = items.device
     gidx = group_index.reshape(-1).to(torch.int64)
     keys = torch.sort((((gidx[:, None] * N + items) * K) + torch.arange(K, device=dev, dtype=torch.int64)).reshape(-1)).values
-    start = torch.zeros(G + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(torch.bincount(gidx, minlength=G)[:G], 0, out=start[1:])
+    _, start = group_segments(gidx, G, perm=False)
     popular = _popular_mask(count_items, popularity_ratio).to(torch.uint8).contiguous() if 'popularitypercentage' in names else None
     tail = _tail_mask(count_items, tail_ratio).to(torch.uint8).contiguous() if 'tailpercentage' in names else None
     counts = count_items.to(torch.int64).contiguous() if 'averagepopularity' in names else None
@@ -422,10 +360,8 @@ def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n
         n_k = len(part)
         out_i = torch.empty((G, n_k, 5), dtype=torch.int64, device=dev)
         out_e = torch.empty((G, n_k), dtype=torch.float64, device=dev)
-        ws = torch.empty(lib.fr_exposure_grouped_workspace_bytes(U, K, G, n_k), dtype=torch.uint8, device=dev)
-        _C.check(lib.fr_exposure_grouped(keys.data_ptr(), U * K, N, K, start.data_ptr(), G, (_C.c_int32 * n_k)(*part), n_k,
-                                         _C.ptr(popular), _C.ptr(tail), _C.ptr(counts), out_i.data_ptr(), out_e.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), _C.current_stream()), "fr_exposure_grouped")
+        _C.call('exposure_grouped', keys.data_ptr(), U * K, N, K, start.data_ptr(), G, (_C.c_int32 * n_k)(*part), n_k,
+                _C.ptr(popular), _C.ptr(tail), _C.ptr(counts), out_i.data_ptr(), out_e.data_ptr(), ws=(U, K, G, n_k), device=dev)
         out_i, out_e = out_i.cpu().tolist(), out_e.cpu().tolist()
         for j, k in enumerate(part):
             sums[k] = [out_i[g][j] for g in range(G)]
@@ -453,17 +389,25 @@ def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n
     return res
 
 
-def _value_name(v: float) -> str:
-    return str(int(v)) if float(v).is_integer() else repr(float(v))
-
-
 class Evaluator:
     """recbole/evaluator/evaluator.py: metric names from `config['metrics']` -> one result dict."""
 
-    TOPK = {"hit", "mrr", "ndcg", "recall", "precision", "map"}
-    EXPOSURE = {"giniindex", "popularitypercentage", "itemcoverage", "averagepopularity", "shannonentropy", "tailpercentage"}
-    FAIR = {"nonparityunfairness", "valueunfairness", "absoluteunfairness", "underunfairness", "overunfairness",
-            "differentialfairness"}
+    TOPK = frozenset(TOPK_NAMES)
+    EXPOSURE = frozenset(EXPOSURE_NAMES)
+    # the ungrouped exposure metrics in the order of their result keys: name -> function of (collected, topk, config)
+    UNGROUPED_EXPOSURE = {
+        "giniindex": lambda c, topk, cfg: gini_index(c['rec.items'], c['data.num_items'], topk),
+        "popularitypercentage": lambda c, topk, cfg: popularity_percentage(c['rec.items'], c['data.count_items'], topk,
+                                                                          cfg['popularity_ratio']),
+        "itemcoverage": lambda c, topk, cfg: item_coverage(c['rec.items'], c['data.num_items'], topk),
+        "averagepopularity": lambda c, topk, cfg: average_popularity(c['rec.items'], c['data.count_items'], topk),
+        "shannonentropy": lambda c, topk, cfg: shannon_entropy(c['rec.items'], topk),
+        "tailpercentage": lambda c, topk, cfg: tail_percentage(c['rec.items'], c['data.count_items'], topk, cfg['tail_ratio']),
+    }
+    # metric name -> the prefix of its keys among what fairness_metrics reports
+    FAIR_PREFIX = {"nonparityunfairness": "NonParity", "valueunfairness": "Value Unfairness", "absoluteunfairness": "Absolute",
+                   "underunfairness": "Underestimation", "overunfairness": "Overestimation", "differentialfairness": "Differential"}
+    FAIR = frozenset(FAIR_PREFIX)
     RANKING = {"gauc"}                                   # reads `rec.meanrank`; a ranking-type metric in the reference too
     VALUE = {"auc", "logloss", "mae", "rmse"}            # evaluation by value: `eval_args.mode: labeled` only
 
@@ -521,20 +465,9 @@ class Evaluator:
         if self.TOPK & set(self.metrics):
             allk = topk_metrics(collected['rec.topk'], self.topk)
             res.update({k: v for k, v in allk.items() if k.split('@')[0] in self.metrics})
-        if "giniindex" in self.metrics:
-            res.update(gini_index(collected['rec.items'], collected['data.num_items'], self.topk))
-        if "popularitypercentage" in self.metrics:
-            res.update(popularity_percentage(collected['rec.items'], collected['data.count_items'], self.topk,
-                                             self.config['popularity_ratio']))
-        if "itemcoverage" in self.metrics:
-            res.update(item_coverage(collected['rec.items'], collected['data.num_items'], self.topk))
-        if "averagepopularity" in self.metrics:
-            res.update(average_popularity(collected['rec.items'], collected['data.count_items'], self.topk))
-        if "shannonentropy" in self.metrics:
-            res.update(shannon_entropy(collected['rec.items'], self.topk))
-        if "tailpercentage" in self.metrics:
-            res.update(tail_percentage(collected['rec.items'], collected['data.count_items'], self.topk,
-                                       self.config['tail_ratio']))
+        for name, fn in self.UNGROUPED_EXPOSURE.items():
+            if name in self.metrics:
+                res.update(fn(collected, self.topk, self.config))
         if self.FAIR & set(self.metrics):
             sst = {s: collected['data.' + s] for s in self.config['sst_attr_list']}
             extra = {}
@@ -544,11 +477,8 @@ class Evaluator:
                                     collected.get('rec.negative_score'), collected.get('data.negative_i'), self.mode,
                                     value_type=bool({"valueunfairness", "absoluteunfairness", "underunfairness",
                                                      "overunfairness"} & set(self.metrics)), **extra)
-            want = {"nonparityunfairness": "NonParity", "valueunfairness": "Value Unfairness",
-                    "absoluteunfairness": "Absolute", "underunfairness": "Underestimation",
-                    "overunfairness": "Overestimation", "differentialfairness": "Differential"}
             for k, v in fair.items():
-                if any(k.startswith(p) for m, p in want.items() if m in self.metrics):
+                if any(k.startswith(p) for m, p in self.FAIR_PREFIX.items() if m in self.metrics):
                     res[k] = v
         if self.utility:
             res.update(self._utility_by_group(collected))
@@ -562,8 +492,7 @@ class Evaluator:
         sensitive attribute <A>' (max - min, population std, worst group; float64 on the host, NaN if a group is NaN)."""
         labeled = self.mode == 'labeled'
         res = {}
-        for name, gidx, labels in self._groups(collected, self.utility, 'data.' if labeled else 'data.user.'):
-            G = len(labels)
+        for name, gidx, G, labels in self._groups(collected, self.utility, 'data.' if labeled else 'data.user.'):
             by_group = {}
             if labeled:
                 by_group.update(group_value_metrics(collected['rec.score'], collected['data.label'], gidx, G,
@@ -582,38 +511,23 @@ class Evaluator:
         sensitive attribute <A>' as well (for most of these metrics the larger value is the worse one)."""
         names = [m for m in EXPOSURE_NAMES if m in self.metrics]
         res = {}
-        for name, gidx, labels in self._groups(collected, self.exposure, 'data.user.'):
-            by_group = group_exposure_metrics(collected['rec.items'], gidx, len(labels), collected['data.num_items'],
+        for name, gidx, G, labels in self._groups(collected, self.exposure, 'data.user.'):
+            by_group = group_exposure_metrics(collected['rec.items'], gidx, G, collected['data.num_items'],
                                               collected.get('data.count_items'), self.topk, names, self.config['popularity_ratio'],
                                               self.config['tail_ratio']) if names else {}
             self._report_groups(res, name, labels, by_group, ('gap', 'std', 'min', 'max'))
         return res
 
     def _groups(self, collected, selected, prefix):
-        """[(name, group index per row, value labels)] of the `selected` attributes (columns `prefix + name`) and of every
-        `sst_intersections` entry whose attributes are all selected; an attribute or intersection with one value is refused."""
-        index, values, groups = {}, {}, []
-        for name in selected:
-            col = collected[prefix + name].reshape(-1)
-            vals, inv = torch.unique(col, sorted=True, return_inverse=True)
-            index[name], values[name] = inv.to(torch.int64), [_value_name(v) for v in vals.cpu().tolist()]
-            groups.append((name, inv, values[name]))
-        for names in self.intersections:
-            if all(n in index for n in names):
-                # equal tuples of group indices <=> equal tuples of values (as fairness_metrics)
-                tuples, inv = torch.unique(torch.stack([index[n] for n in names], dim=1), dim=0, return_inverse=True)
-                labels = ['&'.join(values[n][j] for n, j in zip(names, row)) for row in tuples.cpu().tolist()]
-                groups.append(('&'.join(names), inv, labels))
-        for name, _, labels in groups:
-            if len(labels) < 2:
-                raise ValueError(f'there is only one value for {name} sensitive attribute')
-        return groups
+        """the Groups (with value labels) of the `selected` attributes (columns `prefix + name`) and of every `sst_intersections`
+        entry whose attributes are all selected"""
+        return attribute_groups({name: collected[prefix + name] for name in selected},
+                                [e for e in self.intersections if all(n in selected for n in e)], labels=True)
 
     @staticmethod
     def _report_groups(res, name, labels, by_group, summaries):
         """'<m> of <A>=<value>' per group and '<m> <summary> of sensitive attribute <A>': max - min, population std, the
         smallest, the largest group value; float64 on the host, NaN if a group is NaN"""
-        import numpy as np
         for m, per_group in by_group.items():
             v = np.asarray(per_group, dtype=np.float64)
             for label, x in zip(labels, per_group):

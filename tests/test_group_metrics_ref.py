@@ -195,3 +195,54 @@ def test_labeled_collector_keeps_the_attributes_only_with_the_key():
     missing = Collector(_config(utility_by_group=["age"], **labeled))
     with pytest.raises(ValueError, match="age"):
         missing.eval_batch_collect_labeled(scores, Interaction({"label": torch.tensor([1.0, 0.0, 1.0])}))
+
+
+# ---- where the groups are built (fairrec/evaluator/groups.py): torch index plumbing, no GPU ------------------------------------------
+
+def test_attribute_groups_are_numpys_unique_inverse():
+    from fairrec.evaluator.groups import attribute_groups
+    rng = np.random.default_rng(11)
+    cols = {"gender": rng.integers(0, 2, 300).astype(np.float32),                       # float column, integer values
+            "age": rng.choice(np.array([18, 25, 35, 45, 56]), 300),                     # int64 column, gaps between the values
+            "score": rng.choice(np.array([0.5, 1.25, -2.0], dtype=np.float32), 300)}    # float column, fractional values
+    both = ["age", "score"]
+    groups = attribute_groups({n: torch.from_numpy(c) for n, c in cols.items()}, [both])
+    assert [g.name for g in groups] == ["gender", "age", "score", "age&score"] and all(g.labels is None for g in groups)
+    inverse = {}
+    for g in groups[:3]:
+        vals, inverse[g.name] = np.unique(cols[g.name], return_inverse=True)
+        assert g.index.dtype == torch.int64 and g.index.numpy().tolist() == inverse[g.name].tolist(), g.name
+        assert g.n_groups == len(vals)
+    tuples, inv = np.unique(np.stack([inverse[n] for n in both], axis=1), axis=0, return_inverse=True)
+    assert len(tuples) == 15 and groups[3].n_groups == 15 and groups[3].index.numpy().tolist() == inv.reshape(-1).tolist()
+    # the labels, only when asked for: value names, '&'-joined along a tuple, in sorted-tuple order
+    named = attribute_groups({n: torch.from_numpy(c) for n, c in cols.items()}, [both], labels=True)
+    assert [g.index.tolist() for g in named] == [g.index.tolist() for g in groups]
+    assert named[0].labels == ["0", "1"] and named[1].labels == ["18", "25", "35", "45", "56"]
+    assert named[2].labels == ["-2", "0.5", "1.25"]
+    assert named[3].labels == [f"{a}&{s}" for a in named[1].labels for s in named[2].labels]
+    # a 2-D column [rows, 1] groups as its flattened values
+    assert attribute_groups({"age": torch.from_numpy(cols["age"])[:, None]})[0].index.tolist() == inverse["age"].tolist()
+
+
+def test_attribute_groups_refuse_a_single_value():
+    from fairrec.evaluator.groups import attribute_groups
+    two, one = torch.tensor([0.0, 1.0, 1.0, 0.0]), torch.full((4,), 7.0)
+    with pytest.raises(ValueError, match="there is only one value for age sensitive attribute"):
+        attribute_groups({"gender": two, "age": one})
+    with pytest.raises(ValueError, match="there is only one value for age sensitive attribute"):
+        attribute_groups({"gender": two, "age": one}, [["gender", "age"]], labels=True)
+
+
+def test_group_segments_with_an_empty_group_in_the_middle():
+    from fairrec.evaluator.groups import group_segments, item_segments
+    gidx = torch.tensor([3, 0, 1, 3, 0, 3, 1, 0, 3], dtype=torch.int32)              # group 2 is empty, 4 groups
+    perm, start = group_segments(gidx, 4)
+    assert start.dtype == torch.int64 and start.tolist() == [0, 3, 5, 5, 9]            # G + 1 entries, the empty group repeats 5
+    assert perm.dtype == torch.int64 and perm.tolist() == [1, 4, 7, 2, 6, 0, 3, 5, 8]  # each group's rows in ascending row order
+    want_perm, want_start = GR.segments(gidx.numpy(), 4)
+    assert perm.tolist() == want_perm.tolist() and start.tolist() == want_start.tolist()
+    none, only_start = group_segments(gidx, 4, perm=False)
+    assert none is None and only_start.tolist() == start.tolist()
+    K, runs = item_segments(torch.tensor([2, 2, 5, 9, 9, 9]))
+    assert K == 3 and runs.dtype == torch.int64 and runs.tolist() == [0, 2, 3, 6]
