@@ -1125,6 +1125,54 @@ FR_API size_t fr_df_cells_workspace_bytes(int64_t n_items);
 FR_API int fr_df_cells(const int64_t* perm, const int64_t* item_start, int64_t n_items, const int32_t* group,
                        const float* value, int32_t n_groups, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- bootstrap over rows: the sampling error of the per-group metrics and of their gaps ----------------------------------------
+ * THE RESAMPLING WEIGHTS (a contract: a CPU reference reproduces them bit for bit).  A Poisson bootstrap: in replicate b row r
+ * counts w(r, b) times, w ~ Poisson(1), independent over rows and replicates.  With
+ *   (x, y, z, t) = philox4x32_10(counter = (r, 0, b >> 2, 0), key = (seed & 0xffffffff, seed >> 32))   (Salmon et al., SC'11)
+ * and word = component b & 3 of it, w(r, b) = the number of j in 0..11 with word >= T[j], T[j] = floor(2^32 e^-1 sum_{i<=j} 1/i!):
+ *   0x5e2d58d8, 0xbc5ab1b1, 0xeb715e1d, 0xfb239797, 0xff1025f5, 0xffd90f3b, 0xfffa8b71, 0xffff540c, 0xffffed1f, 0xfffffe21,
+ *   0xffffffd4, 0xfffffffc;  so w lies in 0..12.  r is the row's index in `values`, not its position within its group: a row
+ * carries the same weight under every grouping, and the sums of groups that refine a grouping add up to its sums.
+ *
+ * fr_bootstrap_group_sums: values double [n_rows][ld] (the first n_cols columns of every row are read); groups as segments, the
+ *   arguments of fr_topk_metrics_grouped: the members of group g are the rows perm[group_start[g] .. group_start[g+1]) (perm int64
+ *   [n_rows], NULL = identity; group_start int64 [n_groups + 1] on the device).
+ *     out_sums   double [n_groups][n_rep][n_cols] = sum over the group's rows r of (double)w(r, b) * values[r][c]
+ *     out_weight int64  [n_groups][n_rep]         = sum over the group's rows of w(r, b)
+ *   Every row's product enters the sum, w = 0 included: a NaN (or infinite) value makes its (group, column) NaN in every replicate,
+ *   as it makes the point estimate NaN.  An empty group: zeros.  No weight is ever stored: a workgroup takes one chunk of one
+ *   group's positions, 1024 replicates and 8 columns; a lane owns four replicates, one Philox call per (row, lane) gives its four
+ *   weights, and the lane adds w * value into its own accumulators row after row (fused multiply-add, ascending position; no
+ *   cross-lane reduction).  The per-chunk partials are added per group in ascending chunk order from 0.0.  No floating-point
+ *   atomics: the same input gives the same bytes on every call.  Any summand passes through at most n_g roundings.
+ *   CHUNKS AND WORKSPACE: chunk length L = 64 * ceil(n_rows / (64 * 2048)) positions, so there are at most
+ *   blocks = ceil(n_rows / L) + n_groups <= 2048 + n_groups chunks, and
+ *     fr_bootstrap_group_sums_workspace_bytes = (blocks * n_rep * (n_cols + 1) + n_groups + 1) * 8
+ *   (partial sums double [blocks][n_rep][n_cols], partial weights int64 [blocks][n_rep], chunk_start int64 [n_groups + 1]): bounded
+ *   by the number of chunks times n_rep * n_cols, never by n_rows * n_rep.
+ *   Limits: 1 <= n_rows < 2^31, 1 <= n_cols <= 64 (FR_BOOTSTRAP_MAX_COLS), n_cols <= ld, 1 <= n_rep <= 65536 (FR_BOOTSTRAP_MAX_REP),
+ *   n_groups >= 1 (and n_groups * n_rep * n_cols within one launch of 2^31 - 1 blocks of 256).  perm and group_start are clamped as
+ *   in the other grouped entries: a malformed table gives unspecified values and no access outside the arrays.
+ *   FR_EINVAL before anything is launched or written: a null pointer other than perm, a size out of range, ld < n_cols, ws below the
+ *   _workspace_bytes value, which is 0 for arguments out of range.
+ * fr_topk_user_terms: out double [n_users][n_cols], out[u][j] = row u's term of top-k metric metric[j] (0..5 = hit, mrr, ndcg,
+ *   recall, precision, map) at cut-off cut[j] (1 <= cut[j] <= k): the per-row terms fr_topk_metrics averages, from the same device
+ *   function, the same bits (a mean over one row is that row's term).  metric, cut: HOST arrays, 1 <= n_cols <= 64
+ *   (FR_USER_TERMS_MAX_COLS).  rec_topk int32 [n_users][k + 1] as fr_topk_metrics.  A zero-positive row: Recall NaN, NDCG and MAP 0.
+ * fr_gauc_user_terms: out double [n_users][2] = (auc_u * pos_len, pos_len) of a kept user, (0, 0) of a dropped one, from the
+ *   `rec.meanrank` triples of fr_gauc_grouped and the device function it uses.
+ *   Both: 1 <= n_users < 2^31; FR_EINVAL (null pointer, size or column out of range) before anything is launched or written. */
+#define FR_BOOTSTRAP_MAX_COLS 64
+#define FR_BOOTSTRAP_MAX_REP 65536
+#define FR_USER_TERMS_MAX_COLS 64
+FR_API size_t fr_bootstrap_group_sums_workspace_bytes(int64_t n_rows, int32_t n_cols, int64_t n_groups, int32_t n_rep);
+FR_API int fr_bootstrap_group_sums(const double* values, int64_t n_rows, int32_t n_cols, int64_t ld, const int64_t* perm,
+                                   const int64_t* group_start, int64_t n_groups, int32_t n_rep, uint64_t seed, double* out_sums,
+                                   int64_t* out_weight, void* ws, size_t ws_bytes, void* stream);
+FR_API int fr_topk_user_terms(const int32_t* rec_topk, int64_t n_users, int32_t k, const int32_t* metric, const int32_t* cut,
+                              int32_t n_cols, double* out, void* stream);
+FR_API int fr_gauc_user_terms(const int64_t* meanrank, int64_t n_users, double* out, void* stream);
+
 /* ---- built-in profiler -------------------------------------------------------------------------------
  * When enabled every kernel launch of this library is bracketed by a hipEvent pair recorded on the
  * launch stream; fr_prof_read synchronises the outstanding events and returns the accumulated device

@@ -12,7 +12,7 @@ enum KernelKind {
     K_BUCKET_ROWS, K_FOCF_SHARD_SCORE, K_FOCF_SHARD_GRADS, K_LINEAR_FWD,
     K_LINEAR_BWD_INPUT, K_LINEAR_BWD_WEIGHT, K_NFCF_LOSS, K_BN_FWD, K_BN_BWD, K_ROWDOT, K_BPR, K_SPMM, K_ROW_GATHER, K_SAMPLE_NEG, K_FOCF_STEP, K_FOCF_LPT, K_FOCF_STAGE, K_DYN_NEG_SELECT, K_DYN_NEG_DOT_SELECT,
     K_RECOMMEND, K_TOPK_ROWS, K_MLP_INFER, K_PAIR_MLP, K_DYN_NEG_MLP, K_REC_CELLS,
-    K_REC_MEANRANK, K_ROWS_NORMALIZE, K_DF_CELLS, K_COUNT
+    K_REC_MEANRANK, K_ROWS_NORMALIZE, K_DF_CELLS, K_BOOTSTRAP, K_COUNT
 };
 bool prof_on();
 // algorithmic work of a launch of `kind` (FLOP of a dense product, bytes of an SpMM), summed while the profiler is on
@@ -103,6 +103,14 @@ int launch_sort_many(const SortJobList& jobs, int64_t n_rows_max, uint32_t* err,
 // history CSR (indptr may be null), become -inf.  Accounted under K_TOPK_ROWS.
 int launch_score_mask(float* scores, long long U, long long N, long long ld, const long long* indptr, const long long* hist,
                       long long hist_len, int mask_pad, hipStream_t stream);
+
+// Groups as segments cut into chunks of `chunk_len` consecutive positions (metrics.hip): chunk_start[0 .. G] = the exclusive scan
+// of ceil(n_g / chunk_len), clamped to max_chunks; and out[g][j] = the sum over group g's chunks, in ascending chunk order from 0.0,
+// of part[chunk][j], j < n (mean: times 1 / n_g, NaN for an empty group).
+int launch_group_chunk_scan(const int64_t* group_start, long long G, long long U, long long chunk_len, long long max_chunks,
+                            long long* chunk_start, hipStream_t stream);
+int launch_group_fold(const double* part, const long long* chunk_start, const int64_t* group_start, long long U, long long G, int n,
+                      bool mean, double* out, hipStream_t stream);
 
 // a history CSR as fr_rec_args and fr_pair_mlp_args carry it: optional; with it, items (unless empty) and the ascending order
 inline int check_hist_csr(const int64_t* indptr, const int64_t* items, int64_t len, int32_t sorted, const char* who) {

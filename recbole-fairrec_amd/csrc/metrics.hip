@@ -4,6 +4,8 @@
 //   topk_metrics_kernel      Hit / MRR / NDCG / Recall / Precision / MAP @ 1..K from the `rec.topk` matrix (:40-232)
 //   topk_grouped_kernel      the same six metrics per group of users (groups as segments of a permutation), and
 //   gauc_grouped_kernel      GAUC's two sums per group from `rec.meanrank`: a wave per chunk of 64 members, any number of groups
+//   topk_user_terms_kernel   every row's own terms of chosen (metric, cut-off) pairs, and
+//   gauc_user_terms_kernel   every user's GAUC term and weight: the columns fr_bootstrap_group_sums (bootstrap.hip) resamples
 //   group_sums_kernel        per (item segment, group): sum of scores, count, count of positives -- the tables every
 //                            fairness metric starts from (:948-970, :1322-1335); same segment machinery as the FOCF
 //                            fairness term (16 lanes per segment, fixed order)
@@ -41,38 +43,62 @@ __device__ __forceinline__ T block_sum4(const T* __restrict__ red4) {
     return ((red4[0] + red4[1]) + red4[2]) + red4[3];
 }
 
-// The per-user terms of the six top-k metrics of one wave of 64 rows and their butterfly sums: lane = one row of `rec_topk`
-// (row u; !ok: a lane without a row, every term 0), out[m][k] = wave sum, m = hit, mrr, ndcg, recall, precision, map.
-// A row with zero positives: NDCG 0 (divided by the ideal DCG of all K ranks, the reference's wrapped index), MAP 0,
-// Recall NaN (0 / 0, as the reference).  Shared by topk_metrics_kernel (lane = user of the block) and
-// topk_grouped_kernel (lane = member of a group's chunk): the same terms, the same bits.
+// The per-row arithmetic of the six top-k metrics: topk_row_begin reads the row's head, topk_row_step(k) advances to rank k
+// (k = 0, 1, .. in order) and leaves the row's terms at cut-off k + 1 in v[m], m = hit, mrr, ndcg, recall, precision, map.
+// !ok: a lane without a row, every term 0.  A row with zero positives: NDCG 0 (divided by the ideal DCG of all K ranks, the
+// reference's wrapped index), MAP 0, Recall NaN (0 / 0, as the reference).  The one place these terms are computed: the wave
+// sums below (fr_topk_metrics, fr_topk_metrics_grouped) and fr_topk_user_terms read them from here, the same bits.
+struct TopkRow {
+    const int32_t* row;
+    bool ok;
+    int pos_len, ilen, csum;
+    double first_rr, dcg, idcg, sum_pre;
+    double idcg_all;             // ilen <= 0 only: the ideal DCG of all K ranks
+};
+
+__device__ __forceinline__ TopkRow topk_row_begin(const int32_t* __restrict__ rec_topk, long long u, bool ok, int K) {
+    TopkRow s;
+    s.row = rec_topk + (ok ? u : 0) * (long long)(K + 1);
+    s.ok = ok;
+    s.pos_len = ok ? s.row[K] : 1;
+    s.ilen = s.pos_len < K ? s.pos_len : K;
+    s.csum = 0;
+    s.first_rr = 0.0, s.dcg = 0.0, s.idcg = 0.0, s.sum_pre = 0.0;
+    s.idcg_all = 0.0;
+    if (ok && s.ilen <= 0)
+        for (int k = 0; k < K; ++k) s.idcg_all += 1.0 / log2((double)(k + 2));
+    return s;
+}
+
+__device__ __forceinline__ void topk_row_step(TopkRow& s, int k, double (&v)[6]) {
+    const bool ok = s.ok;
+    const bool hit = ok && s.row[k] != 0;
+    const double disc = 1.0 / log2((double)(k + 2));
+    if (hit && s.csum == 0) s.first_rr = 1.0 / (double)(k + 1);
+    s.csum += hit ? 1 : 0;
+    if (hit) s.dcg += disc;
+    if (k < s.ilen) s.idcg += disc;
+    v[0] = ok && s.csum > 0 ? 1.0 : 0.0;
+    v[1] = ok ? s.first_rr : 0.0;
+    v[2] = ok ? s.dcg / (s.ilen > 0 ? s.idcg : s.idcg_all) : 0.0;
+    v[3] = ok ? (double)s.csum / (double)s.pos_len : 0.0;
+    v[4] = ok ? (double)s.csum / (double)(k + 1) : 0.0;
+    // MAP (metrics.py:100-139): sum over the hits so far of Precision@j, over min(k + 1, min(positives, K))
+    if (hit) s.sum_pre += (double)s.csum / (double)(k + 1);
+    v[5] = ok && s.ilen > 0 ? s.sum_pre / (double)(k + 1 < s.ilen ? k + 1 : s.ilen) : 0.0;
+}
+
+// The terms of one wave of 64 rows and their butterfly sums: lane = one row of `rec_topk` (row u; !ok: a lane without a row),
+// out[m][k] = wave sum.  Shared by topk_metrics_kernel (lane = user of the block) and topk_grouped_kernel (lane = member of a
+// group's chunk): the same terms, the same bits.
 __device__ __forceinline__ void topk_wave_terms(const int32_t* __restrict__ rec_topk, long long u, bool ok, int K, int lane,
                                                 double* __restrict__ out) {
-    const int32_t* row = rec_topk + (ok ? u : 0) * (long long)(K + 1);
-    const int pos_len = ok ? row[K] : 1;
-    const int ilen = pos_len < K ? pos_len : K;
-    int csum = 0;
-    double first_rr = 0.0, dcg = 0.0, idcg = 0.0, sum_pre = 0.0;
-    double idcg_all = 0.0;       // ilen <= 0 only: the ideal DCG of all K ranks
-    if (ok && ilen <= 0)
-        for (int k = 0; k < K; ++k) idcg_all += 1.0 / log2((double)(k + 2));
+    TopkRow s = topk_row_begin(rec_topk, u, ok, K);
     for (int k = 0; k < K; ++k) {
-        const bool hit = ok && row[k] != 0;
-        const double disc = 1.0 / log2((double)(k + 2));
-        if (hit && csum == 0) first_rr = 1.0 / (double)(k + 1);
-        csum += hit ? 1 : 0;
-        if (hit) dcg += disc;
-        if (k < ilen) idcg += disc;
-        const double v0 = ok && csum > 0 ? 1.0 : 0.0;
-        const double v1 = ok ? first_rr : 0.0;
-        const double v2 = ok ? dcg / (ilen > 0 ? idcg : idcg_all) : 0.0;
-        const double v3 = ok ? (double)csum / (double)pos_len : 0.0;
-        const double v4 = ok ? (double)csum / (double)(k + 1) : 0.0;
-        // MAP (metrics.py:100-139): sum over the hits so far of Precision@j, over min(k + 1, min(positives, K))
-        if (hit) sum_pre += (double)csum / (double)(k + 1);
-        const double v5 = ok && ilen > 0 ? sum_pre / (double)(k + 1 < ilen ? k + 1 : ilen) : 0.0;
-        const double s0 = wave_sum(v0), s1 = wave_sum(v1), s2 = wave_sum(v2), s3 = wave_sum(v3),
-                     s4 = wave_sum(v4), s5 = wave_sum(v5);
+        double v[6];
+        topk_row_step(s, k, v);
+        const double s0 = wave_sum(v[0]), s1 = wave_sum(v[1]), s2 = wave_sum(v[2]), s3 = wave_sum(v[3]),
+                     s4 = wave_sum(v[4]), s5 = wave_sum(v[5]);
         if (lane == 0) {
             out[0 * K + k] = s0;
             out[1 * K + k] = s1;
@@ -80,6 +106,29 @@ __device__ __forceinline__ void topk_wave_terms(const int32_t* __restrict__ rec_
             out[3 * K + k] = s3;
             out[4 * K + k] = s4;
             out[5 * K + k] = s5;
+        }
+    }
+}
+
+// out[u][j] = row u's term of metric cols.metric[j] at cut-off cols.cut[j]: one thread per row, the steps of topk_row_step
+// up to the largest cut-off
+struct TopkCols {
+    int n, kmax;
+    int metric[FR_USER_TERMS_MAX_COLS], cut[FR_USER_TERMS_MAX_COLS];
+};
+
+__global__ __launch_bounds__(256) void topk_user_terms_kernel(const int32_t* __restrict__ rec_topk, long long U, int K,
+                                                              TopkCols cols, double* __restrict__ out) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (u >= U) return;
+    TopkRow s = topk_row_begin(rec_topk, u, true, K);
+    for (int k = 0; k < cols.kmax; ++k) {
+        double v[6];
+        topk_row_step(s, k, v);
+        for (int j = 0; j < cols.n; ++j) {
+            if (cols.cut[j] != k + 1) continue;
+            const int m = cols.metric[j];
+            out[u * cols.n + j] = m == 0 ? v[0] : m == 1 ? v[1] : m == 2 ? v[2] : m == 3 ? v[3] : m == 4 ? v[4] : v[5];
         }
     }
 }
@@ -101,9 +150,10 @@ __global__ __launch_bounds__(64) void topk_metrics_kernel(const int32_t* __restr
 // to the grid as well).
 static constexpr int CS_THREADS = 256;
 
-// chunk_start[0 .. G]: the exclusive scan of ceil(n_g / 64), by ONE block (a thread scans a contiguous run of groups)
+// chunk_start[0 .. G]: the exclusive scan of ceil(n_g / chunk_len), by ONE block (a thread scans a contiguous run of groups);
+// chunk_len = 64 for the wave-per-chunk kernels here, fr_bootstrap_group_sums passes its own
 __global__ __launch_bounds__(CS_THREADS) void group_chunk_scan_kernel(const int64_t* __restrict__ group_start, long long G,
-                                                                      long long U, long long max_chunks,
+                                                                      long long U, long long chunk_len, long long max_chunks,
                                                                       long long* __restrict__ chunk_start) {
     __shared__ long long tot[CS_THREADS];
     const int t = threadIdx.x;
@@ -113,7 +163,7 @@ __global__ __launch_bounds__(CS_THREADS) void group_chunk_scan_kernel(const int6
     for (long long g = g0; g < g1; ++g) {
         long long lo, hi;
         group_range(group_start, g, U, lo, hi);
-        mine += (hi - lo + 63) / 64;
+        mine += (hi - lo + chunk_len - 1) / chunk_len;
     }
     tot[t] = mine;
     __syncthreads();
@@ -123,25 +173,9 @@ __global__ __launch_bounds__(CS_THREADS) void group_chunk_scan_kernel(const int6
         long long lo, hi;
         group_range(group_start, g, U, lo, hi);
         chunk_start[g] = run < max_chunks ? run : max_chunks;
-        run += (hi - lo + 63) / 64;
+        run += (hi - lo + chunk_len - 1) / chunk_len;
     }
     if (t == CS_THREADS - 1) chunk_start[G] = run < max_chunks ? run : max_chunks;
-}
-
-// the (group, chunk) of block b, or false: the last g with chunk_start[g] <= b (groups without a chunk share their
-// successor's entry and are passed over)
-__device__ __forceinline__ bool block_chunk(const long long* __restrict__ chunk_start, long long G, long long b, long long& g,
-                                            long long& c) {
-    if (b >= chunk_start[G]) return false;
-    long long lo = 0, hi = G;            // invariant: chunk_start[lo] <= b < chunk_start[hi]
-    while (hi - lo > 1) {
-        const long long mid = (lo + hi) >> 1;
-        if (chunk_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    g = lo;
-    c = b - chunk_start[lo];
-    return true;
 }
 
 // the row of lane `lane` of block b, or ok = false
@@ -185,6 +219,36 @@ __global__ __launch_bounds__(256) void group_fold_kernel(const double* __restric
     out[t] = a;
 }
 
+// One user's GAUC term from its `rec.meanrank` triple: kept (a positive and a negative) -> term = auc_u * pos_len, weight =
+// pos_len; dropped (no_pos / no_neg) or !ok -> 0, 0.  Shared by gauc_grouped_kernel and fr_gauc_user_terms: the same bits.
+__device__ __forceinline__ bool gauc_user_term(const int64_t* __restrict__ meanrank, long long u, bool ok, double& term,
+                                               double& weight, bool& no_pos, bool& no_neg) {
+    const long long two_rank = ok ? meanrank[u * 3] : 0, user_len = ok ? meanrank[u * 3 + 1] : 0,
+                    pos_len = ok ? meanrank[u * 3 + 2] : 0;
+    no_pos = ok && pos_len == 0;
+    no_neg = ok && pos_len != 0 && user_len == pos_len;
+    const bool keep = ok && !no_pos && !no_neg;
+    term = 0.0, weight = 0.0;
+    if (keep) {
+        const long long pair2 = 2 * (user_len + 1) * pos_len - pos_len * (pos_len + 1) - two_rank;
+        const double auc_u = (double)pair2 / (double)(2 * (user_len - pos_len) * pos_len);
+        weight = (double)pos_len;
+        term = auc_u * weight;
+    }
+    return keep;
+}
+
+__global__ __launch_bounds__(256) void gauc_user_terms_kernel(const int64_t* __restrict__ meanrank, long long U,
+                                                              double* __restrict__ out) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (u >= U) return;
+    bool no_pos, no_neg;
+    double term, weight;
+    gauc_user_term(meanrank, u, true, term, weight, no_pos, no_neg);
+    out[u * 2] = term;
+    out[u * 2 + 1] = weight;
+}
+
 // GAUC's sums per chunk from the `rec.meanrank` triples { 2 * pos_rank_sum, user_len, pos_len }: a user with a positive and a
 // negative adds auc_u * pos_len and pos_len, auc_u = pair / ((user_len - pos_len) * pos_len) with pair = (user_len + 1) *
 // pos_len - pos_len * (pos_len + 1) / 2 - pos_rank_sum (evaluator.gauc); numerator and denominator are integers (both doubled),
@@ -199,17 +263,9 @@ __global__ __launch_bounds__(64) void gauc_grouped_kernel(const int64_t* __restr
     const int lane = threadIdx.x;
     bool ok;
     const long long u = chunk_member(perm, group_start, U, g, c, lane, ok);
-    const long long two_rank = ok ? meanrank[u * 3] : 0, user_len = ok ? meanrank[u * 3 + 1] : 0,
-                    pos_len = ok ? meanrank[u * 3 + 2] : 0;
-    const bool no_pos = ok && pos_len == 0, no_neg = ok && pos_len != 0 && user_len == pos_len;
-    const bool keep = ok && !no_pos && !no_neg;
-    double term = 0.0, weight = 0.0;
-    if (keep) {
-        const long long pair2 = 2 * (user_len + 1) * pos_len - pos_len * (pos_len + 1) - two_rank;
-        const double auc_u = (double)pair2 / (double)(2 * (user_len - pos_len) * pos_len);
-        weight = (double)pos_len;
-        term = auc_u * weight;
-    }
+    bool no_pos, no_neg;
+    double term, weight;
+    const bool keep = gauc_user_term(meanrank, u, ok, term, weight, no_pos, no_neg);
     const double s0 = wave_sum(term), s1 = wave_sum(weight);
     const int n0 = wave_sum(keep ? 1 : 0), n1 = wave_sum(no_pos ? 1 : 0), n2 = wave_sum(no_neg ? 1 : 0);
     if (lane == 0) {
@@ -848,6 +904,57 @@ extern "C" int fr_topk_metrics(const int32_t* rec_topk, int64_t n_users, int32_t
     return FR_OK;
 }
 
+// The chunk scan and the fold of per-chunk partials, for the grouped entries here and for fr_bootstrap_group_sums
+// (bootstrap.hip); declared in kernels.hpp.
+int fr::launch_group_chunk_scan(const int64_t* group_start, long long G, long long U, long long chunk_len, long long max_chunks,
+                                long long* chunk_start, hipStream_t stream) {
+    hipLaunchKernelGGL(group_chunk_scan_kernel, dim3(1), dim3(CS_THREADS), 0, stream, group_start, G, U, chunk_len, max_chunks,
+                       chunk_start);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+int fr::launch_group_fold(const double* part, const long long* chunk_start, const int64_t* group_start, long long U, long long G,
+                          int n, bool mean, double* out, hipStream_t stream) {
+    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((G * n + 255) / 256)), dim3(256), 0, stream, part, chunk_start,
+                       group_start, U, G, n, mean, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+extern "C" int fr_topk_user_terms(const int32_t* rec_topk, int64_t n_users, int32_t k, const int32_t* metric, const int32_t* cut,
+                                  int32_t n_cols, double* out, void* stream_) {
+    FR_CHECK_ARG(rec_topk && metric && cut && out, "fr_topk_user_terms: null pointer");
+    FR_CHECK_ARG(n_users >= 1 && n_users < (1ll << 31) && k >= 1 && n_cols >= 1 && n_cols <= FR_USER_TERMS_MAX_COLS,
+                 "fr_topk_user_terms: 1 <= n_users < 2^31, k >= 1, 1 <= n_cols <= %d (got %lld, %d, %d)", FR_USER_TERMS_MAX_COLS,
+                 (long long)n_users, (int)k, (int)n_cols);
+    TopkCols cols;
+    cols.n = n_cols;
+    cols.kmax = 0;
+    for (int j = 0; j < FR_USER_TERMS_MAX_COLS; ++j) {
+        cols.metric[j] = j < n_cols ? metric[j] : 0;
+        cols.cut[j] = j < n_cols ? cut[j] : 0;
+        if (j >= n_cols) continue;
+        FR_CHECK_ARG(metric[j] >= 0 && metric[j] <= 5 && cut[j] >= 1 && cut[j] <= k,
+                     "fr_topk_user_terms: column %d: metric %d not in 0..5 or cut-off %d not in 1..%d", j, (int)metric[j],
+                     (int)cut[j], (int)k);
+        cols.kmax = cut[j] > cols.kmax ? cut[j] : cols.kmax;
+    }
+    hipLaunchKernelGGL(topk_user_terms_kernel, dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
+                       rec_topk, (long long)n_users, (int)k, cols, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
+extern "C" int fr_gauc_user_terms(const int64_t* meanrank, int64_t n_users, double* out, void* stream_) {
+    FR_CHECK_ARG(meanrank && out, "fr_gauc_user_terms: null pointer");
+    FR_CHECK_ARG(n_users >= 1 && n_users < (1ll << 31), "fr_gauc_user_terms: 1 <= n_users < 2^31 (got %lld)", (long long)n_users);
+    hipLaunchKernelGGL(gauc_user_terms_kernel, dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
+                       meanrank, (long long)n_users, out);
+    FR_CHECK_LAUNCH();
+    return FR_OK;
+}
+
 // the main grid of the grouped entries: ceil(n_users / 64) + n_groups blocks, an upper bound on the chunks; 0 = out of range
 static long long grouped_blocks(int64_t n_users, int64_t n_groups) {
     if (n_users < 1 || n_groups < 1 || n_groups > 0x7fffffffLL) return 0;
@@ -877,17 +984,11 @@ extern "C" int fr_topk_metrics_grouped(const int32_t* rec_topk, const int64_t* p
                  "fr_topk_metrics_grouped: workspace too small");
     double* part = (double*)ws;
     long long* chunk_start = (long long*)(part + (size_t)blocks * 6 * k);
-    hipLaunchKernelGGL(group_chunk_scan_kernel, dim3(1), dim3(CS_THREADS), 0, stream, group_start, (long long)n_groups,
-                       (long long)n_users, blocks, chunk_start);
-    FR_CHECK_LAUNCH();
+    if (int rc = launch_group_chunk_scan(group_start, n_groups, n_users, 64, blocks, chunk_start, stream)) return rc;
     hipLaunchKernelGGL(topk_grouped_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, rec_topk, perm, group_start,
                        (long long)n_users, (int)k, (long long)n_groups, (const long long*)chunk_start, part);
     FR_CHECK_LAUNCH();
-    const long long cells = (long long)n_groups * 6 * k;
-    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, (const double*)part,
-                       (const long long*)chunk_start, group_start, (long long)n_users, (long long)n_groups, 6 * (int)k, true, out);
-    FR_CHECK_LAUNCH();
-    return FR_OK;
+    return launch_group_fold(part, chunk_start, group_start, n_users, n_groups, 6 * (int)k, true, out, stream);
 }
 
 // workspace: part_d[blocks][2] doubles, part_i[blocks][3] int64, then chunk_start[n_groups + 1]
@@ -909,16 +1010,11 @@ extern "C" int fr_gauc_grouped(const int64_t* meanrank, const int64_t* perm, con
     double* part_d = (double*)ws;
     long long* part_i = (long long*)(part_d + (size_t)blocks * 2);
     long long* chunk_start = part_i + (size_t)blocks * 3;
-    hipLaunchKernelGGL(group_chunk_scan_kernel, dim3(1), dim3(CS_THREADS), 0, stream, group_start, (long long)n_groups,
-                       (long long)n_users, blocks, chunk_start);
-    FR_CHECK_LAUNCH();
+    if (int rc = launch_group_chunk_scan(group_start, n_groups, n_users, 64, blocks, chunk_start, stream)) return rc;
     hipLaunchKernelGGL(gauc_grouped_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, meanrank, perm, group_start,
                        (long long)n_users, (long long)n_groups, (const long long*)chunk_start, part_d, part_i);
     FR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((n_groups * 2 + 255) / 256)), dim3(256), 0, stream,
-                       (const double*)part_d, (const long long*)chunk_start, group_start, (long long)n_users, (long long)n_groups,
-                       2, false, out);
-    FR_CHECK_LAUNCH();
+    if (int rc = launch_group_fold(part_d, chunk_start, group_start, n_users, n_groups, 2, false, out, stream)) return rc;
     hipLaunchKernelGGL(group_fold_counts_kernel, dim3((unsigned)((n_groups * 3 + 255) / 256)), dim3(256), 0, stream,
                        (const long long*)part_i, (const long long*)chunk_start, (long long)n_groups, kept);
     FR_CHECK_LAUNCH();

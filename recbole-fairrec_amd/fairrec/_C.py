@@ -27,6 +27,8 @@ MLP_INFER_MAX_WIDTH = 512  # FR_MLP_INFER_MAX_WIDTH
 MLP_INFER_MAX_NETS = 8     # FR_MLP_INFER_MAX_NETS
 PAIR_MLP_MAX_LINEARS = 6   # FR_PAIR_MLP_MAX_LINEARS
 PAIR_MLP_MAX_WIDTH = 256   # FR_PAIR_MLP_MAX_WIDTH
+BOOTSTRAP_MAX_COLS = 64    # FR_BOOTSTRAP_MAX_COLS, FR_USER_TERMS_MAX_COLS
+BOOTSTRAP_MAX_REP = 65536  # FR_BOOTSTRAP_MAX_REP
 
 FOCF_OBJECTIVES = {"none": 0, "value": 1, "absolute": 2, "under": 3, "over": 4, "nonparity": 5}
 
@@ -201,6 +203,11 @@ _PROTOS = {
     "fr_fair_metrics_from_stats": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_df_cells_workspace_bytes": (c_size_t, [c_int64]),
     "fr_df_cells": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_bootstrap_group_sums_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64, c_int32]),
+    "fr_bootstrap_group_sums": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_uint64, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_topk_user_terms": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    "fr_gauc_user_terms": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "fr_value_metrics_workspace_bytes": (c_size_t, [c_int64]),
     "fr_value_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_auc_sorted_workspace_bytes": (c_size_t, [c_int64]),

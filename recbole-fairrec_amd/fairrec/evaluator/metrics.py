@@ -20,6 +20,11 @@ group_gauc (fr_gauc_grouped), group_value_metrics (the value kernels on each gro
 attribute <A>' as well: group_exposure_metrics (csrc/exposure.hip: fr_exposure_grouped, every group and every k in one chain after
 ONE torch.sort of the keys (group, item, rank); no [groups, items] table).
 
+`group_bootstrap: B` (off by default; with `utility_by_group`) adds percentile intervals from B replicates of a Poisson bootstrap over
+users, '<m> ci_low | ci_high of <A>=<value>' and '<m> gap ci_low | ci_high of sensitive attribute <A>', for the top-k metrics and
+gauc: topk_user_terms / gauc_user_terms once per evaluation, bootstrap_group_sums per attribute (csrc/bootstrap.hip:
+fr_bootstrap_group_sums, the U x B weights made in registers and never stored), bootstrap_intervals on the host.
+
 `eval_args.mode: labeled` is evaluation by value: 'auc', 'logloss', 'mae', 'rmse' of `rec.score` (what `predict` returned)
 against `data.label` (LABEL_FIELD), every row of the evaluation set (fr_value_metrics, fr_auc_sorted).  'gauc' is a ranking
 metric: it reads `rec.meanrank` (fr_eval_meanrank_segments) in the full / uniN / popN modes.
@@ -389,6 +394,100 @@ def group_exposure_metrics(rec_items: torch.Tensor, group_index: torch.Tensor, n
     return res
 
 
+def topk_user_terms(rec_topk: torch.Tensor, columns) -> torch.Tensor:
+    """double [U, C] on the device: column j = every row's own term of top-k metric columns[j][0] (a name out of TOPK_NAMES) at
+    cut-off columns[j][1] -- what `topk_metrics` averages over the rows, the same bits (fr_topk_user_terms)."""
+    rec = rec_topk.to(torch.int32).contiguous()
+    U, K = rec.shape[0], rec.shape[1] - 1
+    columns = [(str(m).lower(), int(k)) for m, k in columns]
+    bad = [c for c in columns if c[0] not in TOPK_NAMES or not 1 <= c[1] <= K]
+    if bad or not columns:
+        raise ValueError(f'topk_user_terms: columns {bad} are not (name out of {TOPK_NAMES}, cut-off in 1..{K}) pairs')
+    parts = []
+    for lo in range(0, len(columns), _C.BOOTSTRAP_MAX_COLS):
+        part = columns[lo:lo + _C.BOOTSTRAP_MAX_COLS]
+        n = len(part)
+        out = torch.empty((U, n), dtype=torch.float64, device=rec.device)
+        _C.call('topk_user_terms', rec.data_ptr(), U, K, (_C.c_int32 * n)(*[TOPK_NAMES.index(m) for m, _ in part]),
+                (_C.c_int32 * n)(*[k for _, k in part]), n, out.data_ptr())
+        parts.append(out)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+def gauc_user_terms(meanrank: torch.Tensor) -> torch.Tensor:
+    """double [U, 2] on the device: (auc_u * pos_len, pos_len) of every user `gauc` keeps, (0, 0) of a dropped one
+    (fr_gauc_user_terms); GAUC of a set of users = the quotient of the two column sums."""
+    mr = meanrank.to(torch.int64).contiguous()
+    out = torch.empty((mr.shape[0], 2), dtype=torch.float64, device=mr.device)
+    _C.call('gauc_user_terms', mr.data_ptr(), mr.shape[0], out.data_ptr())
+    return out
+
+
+def bootstrap_group_sums(values: torch.Tensor, group_index: torch.Tensor, n_groups: int, n_rep: int, seed: int):
+    """Poisson bootstrap over the rows of `values` (double [U, C] on the device): (sums double [G, B, C], weight int64 [G, B]),
+    sums[g, b, c] = sum over group g's rows r of w(r, b) * values[r, c], weight[g, b] = their sum of w(r, b); w(r, b) ~ Poisson(1)
+    from Philox by the contract of fairrec_hip.h, a function of (row index, replicate, seed) alone: the same replicates under
+    every grouping.  fr_bootstrap_group_sums makes the weights in registers, never in memory; more than 64 columns go through
+    several calls."""
+    if values.dim() != 2 or values.dtype != torch.float64:
+        raise ValueError(f'bootstrap_group_sums: values must be a float64 [rows, columns] tensor, not {values.dtype} {tuple(values.shape)}')
+    values = values.contiguous()
+    U, C = values.shape
+    G, B = int(n_groups), int(n_rep)
+    if group_index.numel() != U:
+        raise ValueError(f'bootstrap_group_sums: {group_index.numel()} group indices for {U} rows')
+    if not 1 <= B <= _C.BOOTSTRAP_MAX_REP or C < 1:
+        raise ValueError(f'bootstrap_group_sums: {B} replicates of {C} columns; 1..{_C.BOOTSTRAP_MAX_REP} replicates, at least one column')
+    perm, start = group_segments(group_index, G)
+    dev = values.device
+    weight = torch.empty((G, B), dtype=torch.int64, device=dev)
+    parts = []
+    for lo in range(0, C, _C.BOOTSTRAP_MAX_COLS):
+        n = min(C - lo, _C.BOOTSTRAP_MAX_COLS)
+        sums = torch.empty((G, B, n), dtype=torch.float64, device=dev)
+        _C.call('bootstrap_group_sums', values.data_ptr() + lo * 8, U, n, C, perm.data_ptr(), start.data_ptr(), G, B,
+                int(seed) & (2 ** 64 - 1), sums.data_ptr(), weight.data_ptr(), ws=(U, n, G, B), device=dev)
+        parts.append(sums)
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=2)), weight
+
+
+def bootstrap_intervals(stat, level: float, what: str = ''):
+    """Percentile intervals of bootstrap replicates.  stat: float64 [G, B] on the host, the statistic of group g in replicate b,
+    NaN (or infinite) = unusable.  -> (low [G], high [G], gap_low, gap_high, usable [G], gap_usable): per group
+    np.quantile(its usable values, [(1 - level) / 2, (1 + level) / 2]); the gap of a replicate is max_g - min_g, usable when every
+    group's value is; `usable` counts them.  Fewer usable replicates than B / 2: a NaN interval and one warning (`what` names
+    the attribute and the metric in it)."""
+    stat = np.asarray(stat, dtype=np.float64)
+    G, B = stat.shape
+    q = [(1.0 - level) / 2.0, (1.0 + level) / 2.0]
+    ok = np.isfinite(stat)
+    usable = ok.sum(axis=1)
+    low, high = np.full(G, np.nan), np.full(G, np.nan)
+    for g in range(G):
+        if 2 * usable[g] >= B:
+            low[g], high[g] = np.quantile(stat[g][ok[g]], q)
+    every = ok.all(axis=0)
+    gap_usable = int(every.sum())
+    gap_low = gap_high = float('nan')
+    if 2 * gap_usable >= B:
+        cols = stat[:, every]
+        gap_low, gap_high = (float(x) for x in np.quantile(cols.max(axis=0) - cols.min(axis=0), q))
+    starved = [f'group {g} ({int(usable[g])})' for g in range(G) if 2 * usable[g] < B]
+    if 2 * gap_usable < B:
+        starved.append(f'the gap ({gap_usable})')
+    if starved:
+        getLogger().warning('bootstrap intervals of %s: fewer than half of the %d replicates are usable for %s; these intervals '
+                            'are nan', what or 'a statistic', B, ', '.join(starved))
+    return low, high, gap_low, gap_high, usable, gap_usable
+
+
+def _ratio(num, den):
+    """num / den on the host, NaN where the denominator is zero"""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(den != 0, num / np.where(den != 0, den, 1.0), np.nan)
+
+
 class Evaluator:
     """recbole/evaluator/evaluator.py: metric names from `config['metrics']` -> one result dict."""
 
@@ -437,6 +536,25 @@ class Evaluator:
         if self.exposure and self.mode == 'labeled':
             raise ValueError("exposure_by_group needs eval_args.mode full / uniN / popN, not 'labeled': the exposure metrics "
                              "read the ranked lists")
+        self.bootstrap, self.bootstrap_level = self._bootstrap_keys(config['group_bootstrap'], config['group_bootstrap_level'])
+        if self.bootstrap and not self.utility:
+            raise ValueError('group_bootstrap needs utility_by_group: the intervals belong to its per-group metrics')
+        if self.bootstrap and self.mode == 'labeled':
+            raise ValueError("group_bootstrap needs eval_args.mode full / uniN / popN, not 'labeled': the bootstrap resamples "
+                             "users, and the rows of the labeled mode are interactions")
+        self.seed = int(config['seed']) if config['seed'] is not None else 0
+
+    @staticmethod
+    def _bootstrap_keys(n_rep, level):
+        """`group_bootstrap` (None / 0: off, else an integer B in 2..65536) and `group_bootstrap_level` (strictly inside 0..1)"""
+        if n_rep is None or (not isinstance(n_rep, bool) and n_rep == 0):
+            return 0, None
+        if isinstance(n_rep, bool) or not isinstance(n_rep, int) or not 2 <= n_rep <= _C.BOOTSTRAP_MAX_REP:
+            raise ValueError(f'group_bootstrap must be None, 0 or an integer in 2..{_C.BOOTSTRAP_MAX_REP}, not {n_rep!r}')
+        level = 0.95 if level is None else level
+        if isinstance(level, bool) or not isinstance(level, (int, float)) or not 0.0 < level < 1.0:
+            raise ValueError(f'group_bootstrap_level must lie strictly between 0 and 1, not {level!r}')
+        return int(n_rep), float(level)
 
     @staticmethod
     def _intersections(entries, attrs):
@@ -492,6 +610,7 @@ class Evaluator:
         sensitive attribute <A>' (max - min, population std, worst group; float64 on the host, NaN if a group is NaN)."""
         labeled = self.mode == 'labeled'
         res = {}
+        boot = self._bootstrap_columns(collected) if self.bootstrap else None
         for name, gidx, G, labels in self._groups(collected, self.utility, 'data.' if labeled else 'data.user.'):
             by_group = {}
             if labeled:
@@ -503,7 +622,40 @@ class Evaluator:
                 allk = group_topk_metrics(collected['rec.topk'], gidx, G, self.topk)
                 by_group.update({k: v for k, v in allk.items() if k.split('@')[0] in self.metrics})
             self._report_groups(res, name, labels, by_group, ('gap', 'std', 'min'))
+            if boot is not None:
+                self._report_intervals(res, name, labels, gidx, G, *boot)
         return res
+
+    def _bootstrap_columns(self, collected):
+        """`group_bootstrap`: the per-user terms every attribute's bootstrap sums up, made once per evaluation -> (values double
+        [U, C] on the device, {result metric: (its column, None) for a top-k metric -- the statistic is sum / weight --, or
+        (numerator column, denominator column) for gauc})"""
+        parts, stats, C = [], {}, 0
+        columns = [(m, int(k)) for m in TOPK_NAMES if m in self.metrics for k in self.topk]
+        if "gauc" in self.metrics:
+            parts.append(gauc_user_terms(collected['rec.meanrank']))
+            stats['gauc'] = (0, 1)
+            C = 2
+        if columns:
+            parts.append(topk_user_terms(collected['rec.topk'], columns))
+            stats.update({f'{m}@{k}': (C + j, None) for j, (m, k) in enumerate(columns)})
+        if not parts:
+            return None
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)).contiguous(), stats
+
+    def _report_intervals(self, res, name, labels, gidx, G, values, stats):
+        """'<m> ci_low | ci_high of <A>=<value>' and '<m> gap ci_low | ci_high of sensitive attribute <A>': the percentile
+        intervals of `group_bootstrap` replicates of every group's metric and of max - min over the groups"""
+        sums, weight = bootstrap_group_sums(values, gidx, G, self.bootstrap, self.seed)
+        sums, weight = sums.cpu().numpy(), weight.cpu().numpy()
+        for m, (num, den) in stats.items():
+            stat = _ratio(sums[:, :, num], weight if den is None else sums[:, :, den])
+            low, high, gap_low, gap_high, _, _ = bootstrap_intervals(stat, self.bootstrap_level, f'{m} of sensitive attribute {name}')
+            for g, label in enumerate(labels):
+                res[f'{m} ci_low of {name}={label}'] = float(low[g])
+                res[f'{m} ci_high of {name}={label}'] = float(high[g])
+            res[f'{m} gap ci_low of sensitive attribute {name}'] = gap_low
+            res[f'{m} gap ci_high of sensitive attribute {name}'] = gap_high
 
     def _exposure_by_group(self, collected) -> Dict[str, float]:
         """`exposure_by_group`: every requested exposure metric and k per group of each selected attribute, and of each
