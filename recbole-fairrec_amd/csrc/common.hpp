@@ -361,13 +361,14 @@ __device__ __forceinline__ void replay2(RowFrag<E>& p0, RowFrag<E>& m0, RowFrag<
 // Each policy names the state arrays its learner keeps (the kernels never touch the others: a table may have them NULL),
 // one step on one element with a data gradient (`elem`, scalars s0 / s1 = entries 4j / 4j+1 of the step table), the
 // wave-uniform test for "a zero-data-gradient step is the identity on (p, state)" (then nothing is replayed or swept) and
-// the one for "... leaves p as it is" (`p_invariant`: a read-only gather then needs the parameters alone).
+// the one for "... leaves p as it is" (`p_invariant`: a read-only gather then needs the parameters alone).  The host asks
+// the same structs (`learner_facts` below): nothing about a learner is written down a second time.
 // AdamC carries the constants of every learner: wd, eps, and for RMSprop alpha in b2 / 1-alpha in omb2.
 struct LearnerAdam {
     static constexpr int ID = FR_LEARNER_ADAM;
     static constexpr bool HAS_M = true, HAS_V = true;
-    __device__ static __forceinline__ bool identity(const AdamC&) { return false; }
-    __device__ static __forceinline__ bool p_invariant(const AdamC&) { return false; }
+    __host__ __device__ static __forceinline__ bool identity(const AdamC&) { return false; }
+    __host__ __device__ static __forceinline__ bool p_invariant(const AdamC&) { return false; }
     __device__ static __forceinline__ void elem(float& p, float& m, float& v, float gd, float s0, float s1, const AdamC& c) {
         adam_elem(p, m, v, gd, s0, s1, c);
     }
@@ -395,8 +396,8 @@ __device__ __forceinline__ float step_sqrt(float x) {
 struct LearnerSgd {
     static constexpr int ID = FR_LEARNER_SGD;
     static constexpr bool HAS_M = false, HAS_V = false;
-    __device__ static __forceinline__ bool identity(const AdamC& c) { return c.wd == 0.f; }
-    __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }
+    __host__ __device__ static __forceinline__ bool identity(const AdamC& c) { return c.wd == 0.f; }
+    __host__ __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }
     __device__ static __forceinline__ void elem(float& p, float&, float&, float gd, float s0, float, const AdamC& c) {
         const float g = fmaf(c.wd, p, gd);
         p = fmaf(-s0, g, p);
@@ -412,8 +413,8 @@ struct LearnerSgd {
 struct LearnerAdagrad {
     static constexpr int ID = FR_LEARNER_ADAGRAD;
     static constexpr bool HAS_M = true, HAS_V = false;
-    __device__ static __forceinline__ bool identity(const AdamC& c) { return c.wd == 0.f; }
-    __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }
+    __host__ __device__ static __forceinline__ bool identity(const AdamC& c) { return c.wd == 0.f; }
+    __host__ __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }
     __device__ static __forceinline__ void elem(float& p, float& m, float&, float gd, float s0, float, const AdamC& c) {
         const float g = fmaf(c.wd, p, gd);
         m = fmaf(g, g, m);
@@ -432,8 +433,8 @@ struct LearnerAdagrad {
 struct LearnerRmsprop {
     static constexpr int ID = FR_LEARNER_RMSPROP;
     static constexpr bool HAS_M = true, HAS_V = false;
-    __device__ static __forceinline__ bool identity(const AdamC&) { return false; }
-    __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }   // (only square_avg decays)
+    __host__ __device__ static __forceinline__ bool identity(const AdamC&) { return false; }
+    __host__ __device__ static __forceinline__ bool p_invariant(const AdamC& c) { return c.wd == 0.f; }   // (only square_avg decays)
     __device__ static __forceinline__ void elem(float& p, float& m, float&, float gd, float s0, float, const AdamC& c) {
         const float g = fmaf(c.wd, p, gd);
         m = fmaf(c.omb2 * g, g, m * c.b2);
@@ -507,5 +508,16 @@ __device__ __forceinline__ void replay2l(RowFrag<E>& p0, RowFrag<E>& m0, RowFrag
         case FR_LEARNER_RMSPROP: { using L = ::fr::LearnerRmsprop; __VA_ARGS__; } break; \
         default: { using L = ::fr::LearnerAdam; __VA_ARGS__; } break;                   \
     }
+
+// host: the same facts read off the policy of `a->learner` -- the state arrays a table or dense tensor must bring, and
+// whether with these hyper-parameters no row can ever be behind (nothing to flush, nothing to sweep)
+struct LearnerFacts {
+    bool has_m, has_v, identity;
+};
+inline LearnerFacts learner_facts(const fr_adam* a) {
+    LearnerFacts f{};
+    FR_DISPATCH_L(a->learner, (f = LearnerFacts{L::HAS_M, L::HAS_V, L::identity(make_adamc(a))}));
+    return f;
+}
 
 }  // namespace fr

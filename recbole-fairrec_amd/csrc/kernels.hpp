@@ -143,8 +143,9 @@ __device__ __forceinline__ TableV resolved(TableV T) {
     return T;
 }
 
-inline int check_table(const fr_table* t, const char* who) {
-    if (!t || !t->p || !t->m || !t->v || !t->last || !t->stamp) {
+// a table whose state arrays m / v must be there where asked for
+inline int check_table_with(const fr_table* t, bool with_m, bool with_v, const char* who) {
+    if (!t || !t->p || (with_m && !t->m) || (with_v && !t->v) || !t->last || !t->stamp) {
         set_error("%s: table has null pointers", who);
         return FR_EINVAL;
     }
@@ -158,6 +159,8 @@ inline int check_table(const fr_table* t, const char* who) {
     }
     return FR_OK;
 }
+
+inline int check_table(const fr_table* t, const char* who) { return check_table_with(t, true, true, who); }
 
 inline int check_adam(const fr_adam* a, const char* who) {
     if (!a || !a->scalars || a->cap < 1) {
@@ -187,20 +190,8 @@ inline int check_focf_adam(const fr_adam* a, const char* who) {
 inline int check_table_for(const fr_table* t, const fr_adam* a, const char* who) {
     int rc = check_adam(a, who);
     if (rc) return rc;
-    const bool need_m = a->learner != FR_LEARNER_SGD, need_v = a->learner == FR_LEARNER_ADAM;
-    if (!t || !t->p || (need_m && !t->m) || (need_v && !t->v) || !t->last || !t->stamp) {
-        set_error("%s: table has null pointers", who);
-        return FR_EINVAL;
-    }
-    if (t->dim < 1 || t->dim > 256) {
-        set_error("%s: embedding dim %d not in 1..256", who, t->dim);
-        return FR_EUNSUPPORTED;
-    }
-    if (t->n_rows < 1 || t->n_rows > 0x7fffffffLL) {
-        set_error("%s: n_rows %lld not in 1..2^31-1", who, (long long)t->n_rows);
-        return FR_EUNSUPPORTED;
-    }
-    return FR_OK;
+    const LearnerFacts lf = learner_facts(a);
+    return check_table_with(t, lf.has_m, lf.has_v, who);
 }
 
 // Sweep slice of a table for optimizer step `step` with period S: rows [lo, hi).

@@ -117,8 +117,7 @@ __device__ __forceinline__ void gather_train_row(const GatherJob& J, const AdamC
     if (L::HAS_M) load_row<E>(m, T.m + (size_t)row * D, D, lane);
     if (L::HAS_V) load_row<E>(v, T.v + (size_t)row * D, D, lane);
     const int t0 = uniform(lt);
-    if constexpr (L::ID == FR_LEARNER_ADAM) replay<E>(p, m, v, t0, T.step - 1, c, lane);
-    else replay1<L, E>(p, m, v, t0, T.step - 1, c);      // (nothing at all where a missed step is the identity)
+    replay1<L, E>(p, m, v, t0, T.step - 1, c);      // (nothing at all where a missed step is the identity)
     store_row<E>(p, J.rows_out + (size_t)jp * D, D, lane);
     if (L::HAS_M) store_row<E>(m, J.w.m_side + (size_t)j * D, D, lane);
     if (L::HAS_V) store_row<E>(v, J.w.v_side + (size_t)j * D, D, lane);
@@ -203,18 +202,11 @@ __global__ __launch_bounds__(256) void table_apply_grad_kernel(ApplyJob ja, Appl
 
 using namespace fr;
 
-// a zero-data-gradient step leaves (p, state) as they are: SGD and Adagrad without weight decay
-static inline bool replay_is_identity(const fr_adam* a) {
-    return (a->learner == FR_LEARNER_SGD || a->learner == FR_LEARNER_ADAGRAD) && (float)a->weight_decay == 0.f;
-}
-static inline bool learner_has_m(const fr_adam* a) { return a->learner != FR_LEARNER_SGD; }
-static inline bool learner_has_v(const fr_adam* a) { return a->learner == FR_LEARNER_ADAM; }
-
 extern "C" int fr_table_flush(const fr_table* t, const fr_adam* adam, void* stream_) {
     int rc;
     if ((rc = check_table_for(t, adam, "fr_table_flush"))) return rc;
     if (t->step < 1 && !t->step_dev) return FR_OK;
-    if (replay_is_identity(adam)) return FR_OK;       // no row can be behind: nothing to move
+    if (learner_facts(adam).identity) return FR_OK;       // no row can be behind: nothing to move
     const AdamC c = make_adamc(adam);
     const TableV Tv = view(t);
     long long blocks = (t->n_rows + 3) / 4;
@@ -247,8 +239,8 @@ extern "C" int fr_adam_dense(float* p, const float* g, float* m, float* v, int64
                              int32_t step, void* stream_) {
     int rc;
     if ((rc = check_adam(adam, "fr_adam_dense"))) return rc;
-    FR_CHECK_ARG(p && g && (m || !learner_has_m(adam)) && (v || !learner_has_v(adam)) && n >= 0 && step >= 1,
-                 "fr_adam_dense: bad argument");
+    const LearnerFacts lf = learner_facts(adam);
+    FR_CHECK_ARG(p && g && (m || !lf.has_m) && (v || !lf.has_v) && n >= 0 && step >= 1, "fr_adam_dense: bad argument");
     if (n == 0) return FR_OK;
     long long blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
@@ -266,14 +258,15 @@ extern "C" int fr_adam_dense_multi(const fr_dense_desc* descs, int32_t n_tensors
     if ((rc = check_adam(adam, "fr_adam_dense_multi"))) return rc;
     FR_CHECK_ARG(descs && n_tensors >= 0, "fr_adam_dense_multi: bad argument");
     const AdamC c = make_adamc(adam);
+    const LearnerFacts lf = learner_facts(adam);
     for (int32_t base = 0; base < n_tensors; base += FR_ADAM_DENSE_MAX) {
         const int cnt = std::min<int>(FR_ADAM_DENSE_MAX, n_tensors - base);
         DenseBatch b;
         long long nmax = 1;
         for (int k = 0; k < cnt; ++k) {
             const fr_dense_desc& d = descs[base + k];
-            FR_CHECK_ARG(d.p && d.g && (d.m || !learner_has_m(adam)) && (d.v || !learner_has_v(adam)) && d.n >= 0 &&
-                             (d.step >= 1 || d.step_dev), "fr_adam_dense_multi: bad descriptor %d", base + k);
+            FR_CHECK_ARG(d.p && d.g && (d.m || !lf.has_m) && (d.v || !lf.has_v) && d.n >= 0 && (d.step >= 1 || d.step_dev),
+                         "fr_adam_dense_multi: bad descriptor %d", base + k);
             b.t[k] = d;
             nmax = std::max<long long>(nmax, d.n);
         }
@@ -294,28 +287,65 @@ extern "C" size_t fr_table_train_workspace_bytes(int64_t M, int32_t dim) {
 
 static inline bool lay_ok(int32_t chunk, int32_t stride) { return chunk == 0 || (chunk > 0 && stride >= chunk); }
 
-// one (tb == nullptr) or two tables of the same dim and M per call: one sort launch (a workgroup per table) on the
+// the sort of one id list into the segments part of a table workspace
+static SortJob make_sort_job(const int64_t* idx, int64_t n_rows, const TableWs& w, Lay lay) {
+    SortJob s{idx, n_rows, w.perm, w.seg_start, w.seg_row, nullptr, w.nseg, nullptr, nullptr, lay};
+    s.seg_first = w.seg_first;
+    return s;
+}
+
+// What the fr_table_gather_train* entry points hand to gather_train_impl.
+struct TrainSide {           // one table's share of a training lookup
+    const fr_table* t;
+    const int64_t* idx;
+    float* rows;
+    void* ws;
+};
+struct RoLookup {            // a read-only lookup riding along (fr_table_lookup_pair): its own table, hyper-parameters, ids
+    const fr_table* t;
+    const fr_adam* adam;
+    const int64_t* idx;
+    int64_t M;
+    float* out;
+};
+struct GatherTrainArgs {
+    const char* who;
+    const fr_adam* adam;
+    TrainSide a, b;          // b.t == nullptr: one table
+    int64_t M;               // ids per table
+    int32_t chunk, stride;
+    size_t ws_bytes;
+    uint32_t* err_flag;
+    hipStream_t stream;
+    bool prepared = false;   // fr_table_sort2 already left the segments of these id lists in the workspaces
+    const RoLookup* ro = nullptr;
+};
+
+// one (b.t == nullptr) or two tables of the same dim and M per call: one sort launch (a workgroup per table) on the
 // side stream, one gather launch
-static int gather_train_impl(const char* who, const fr_table* ta, const fr_table* tb, const fr_adam* adam,
-                             const int64_t* idx_a, const int64_t* idx_b, int64_t M, int32_t chunk, int32_t stride,
-                             float* rows_a, float* rows_b, void* ws_a, void* ws_b, size_t ws_bytes, uint32_t* err_flag,
-                             hipStream_t stream, bool prepared = false, const fr_table* ro = nullptr,
-                             const fr_adam* ro_adam = nullptr, const int64_t* ro_idx = nullptr, int64_t ro_M = 0,
-                             float* ro_out = nullptr) {
+static int gather_train_impl(const GatherTrainArgs& g) {
+    const fr_table *const ta = g.a.t, *const tb = g.b.t;
+    const fr_adam* const adam = g.adam;
+    const RoLookup* const ro = g.ro;
+    const char* const who = g.who;
+    const int64_t M = g.M;
+    uint32_t* const err_flag = g.err_flag;
+    const hipStream_t stream = g.stream;
     int rc;
     if ((rc = check_table_for(ta, adam, who)) || (tb && (rc = check_table_for(tb, adam, who)))) return rc;
-    FR_CHECK_ARG(idx_a && rows_a && ws_a && M >= 1 && M <= FR_SORT_MAX && ta->step >= 1 && lay_ok(chunk, stride),
+    FR_CHECK_ARG(g.a.idx && g.a.rows && g.a.ws && M >= 1 && M <= FR_SORT_MAX && ta->step >= 1 && lay_ok(g.chunk, g.stride),
                  "%s: bad argument (M=%lld, step=%d)", who, (long long)M, ta->step);
-    FR_CHECK_ARG(!tb || (idx_b && rows_b && ws_b && ws_b != ws_a && tb->dim == ta->dim && tb->step >= 1),
+    FR_CHECK_ARG(!tb || (g.b.idx && g.b.rows && g.b.ws && g.b.ws != g.a.ws && tb->dim == ta->dim && tb->step >= 1),
                  "%s: bad second table", who);
-    const Lay lay{chunk, stride};
-    TableWs wa = table_layout(ws_a, M, ta->dim);
-    TableWs wb = tb ? table_layout(ws_b, M, tb->dim) : wa;
-    FR_CHECK_ARG(ws_bytes >= wa.bytes, "%s: workspace %zu < %zu bytes", who, ws_bytes, wa.bytes);
-    SortJob sa{idx_a, ta->n_rows, wa.perm, wa.seg_start, wa.seg_row, nullptr, wa.nseg, nullptr, nullptr, lay};
-    SortJob sb{idx_b, tb ? tb->n_rows : 0, wb.perm, wb.seg_start, wb.seg_row, nullptr, wb.nseg, nullptr, nullptr, lay};
-    sa.seg_first = wa.seg_first;
-    sb.seg_first = wb.seg_first;
+    const Lay lay{g.chunk, g.stride};
+    const TableWs wa = table_layout(g.a.ws, M, ta->dim);
+    const TableWs wb = tb ? table_layout(g.b.ws, M, tb->dim) : wa;
+    FR_CHECK_ARG(g.ws_bytes >= wa.bytes, "%s: workspace %zu < %zu bytes", who, g.ws_bytes, wa.bytes);
+    const SortJob sa = make_sort_job(g.a.idx, ta->n_rows, wa, lay);
+    const SortJob sb = make_sort_job(g.b.idx, tb ? tb->n_rows : 0, wb, lay);
+    const AdamC c = make_adamc(adam);
+    const GatherJob ja{view(ta), g.a.idx, g.a.rows, wa};
+    const GatherJob jb = tb ? GatherJob{view(tb), g.b.idx, g.b.rows, wb} : ja;
     SideStream* ss = side_stream();
     // The sort (one latency-bound workgroup per list) runs beside the gather on the side stream -- except inside a stream
     // capture: a hipGraph replays both branches on one hardware queue, every kernel dispatched after the sort retires behind it
@@ -331,10 +361,10 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
     static const bool no_merge = getenv("FAIRREC_LOOKUP_SEPARATE") != nullptr;
     const int kpt = M <= 2 * SORT_THREADS ? 2 : (M <= 4 * SORT_THREADS ? 4 : (M <= 8 * SORT_THREADS ? 8 : 16));
     // (the read-only table rides along only under the same learner: one policy per launch)
-    if (!prepared && !no_merge && kpt != 0 && (!overlap || ro) && (!ro || (ro->dim + 63) / 64 == (ta->dim + 63) / 64) &&
-        (!ro || (ro_adam && ro_adam->learner == adam->learner))) {
-        if (ro && (rc = check_table_for(ro, ro_adam, who))) return rc;
-        FR_CHECK_ARG(!ro || (ro_idx && ro_out && ro_M >= 0), "%s: bad read-only lookup", who);
+    if (!g.prepared && !no_merge && kpt != 0 && (!overlap || ro) && (!ro || (ro->t->dim + 63) / 64 == (ta->dim + 63) / 64) &&
+        (!ro || (ro->adam && ro->adam->learner == adam->learner))) {
+        if (ro && (rc = check_table_for(ro->t, ro->adam, who))) return rc;
+        FR_CHECK_ARG(!ro || (ro->idx && ro->out && ro->M >= 0), "%s: bad read-only lookup", who);
         SortJobList jobs{};
         jobs.j[0] = sa;
         jobs.M[0] = (int)M;
@@ -348,13 +378,10 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
         }
         int bits = 1;
         while (bits < 32 && (1ll << bits) < nmax) ++bits;
-        const AdamC c = make_adamc(adam);
-        const AdamC cp = ro ? make_adamc(ro_adam) : c;
-        GatherJob ja{view(ta), idx_a, rows_a, wa};
-        GatherJob jb = tb ? GatherJob{view(tb), idx_b, rows_b, wb} : ja;
-        PlainJob pj{ro ? view(ro) : view(ta), ro_idx, ro_out, ro ? (long long)ro_M : 0};
+        const AdamC cp = ro ? make_adamc(ro->adam) : c;
+        const PlainJob pj = ro ? PlainJob{view(ro->t), ro->idx, ro->out, (long long)ro->M} : PlainJob{view(ta), nullptr, nullptr, 0};
         constexpr int WPB = SORT_THREADS / 64;
-        const long long blocks = jobs.n + (M + WPB - 1) / WPB * (tb ? 2 : 1) + (ro ? (ro_M + WPB - 1) / WPB : 0);
+        const long long blocks = jobs.n + (M + WPB - 1) / WPB * (tb ? 2 : 1) + (ro ? (ro->M + WPB - 1) / WPB : 0);
         ProfScope prof(K_TABLE_GATHER_TRAIN, stream);
 #define FR_LOOKUP_LAUNCH(KPT)                                                                                              \
     {                                                                                                                      \
@@ -369,36 +396,30 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
         FR_LAUNCH(prof, (table_lookup_kernel<L, E, KPT>), dim3((unsigned)blocks), dim3(SORT_THREADS), sort_lds_bytes<KPT>(),  \
                   stream, jobs, npass, ja, jb, tb ? 2 : 1, pj, c, cp, (long long)M, lay, err_flag);                        \
     }
-        if (kpt == 2) {
-            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(2)));
-        } else if (kpt == 4) {
-            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(4)));
-        } else if (kpt == 8) {
-            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(8)));
-        } else {
-            FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(16)));
+        switch (kpt) {
+            case 2: FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(2))); break;
+            case 4: FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(4))); break;
+            case 8: FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(8))); break;
+            default: FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LOOKUP_LAUNCH(16))); break;
         }
 #undef FR_LOOKUP_LAUNCH
         FR_CHECK_LAUNCH();
         return FR_OK;
     }
     if (ro) {      // not mergeable: the read-only gather as its own launch
-        if ((rc = fr_table_gather(ro, ro_adam, ro_idx, ro_M, ro_out, err_flag, stream))) return rc;
+        if ((rc = fr_table_gather(ro->t, ro->adam, ro->idx, ro->M, ro->out, err_flag, stream))) return rc;
     }
-    if (prepared) {
+    if (g.prepared) {
         // fr_table_sort2 already left the segments of these id lists in the workspaces (one step ahead)
     } else if (overlap) {
         FR_CHECK_HIP(hipEventRecord(ss->fork, stream));
         FR_CHECK_HIP(hipStreamWaitEvent(ss->stream, ss->fork, 0));
         if ((rc = launch_sort(sa, tb ? &sb : nullptr, M, err_flag, ss->stream))) return rc;
         // joined by the first consumer of the segments (apply_grad / shard_fair)
-        if ((rc = side_mark(ws_a)) || (tb && (rc = side_mark(ws_b)))) return rc;
+        if ((rc = side_mark(g.a.ws)) || (tb && (rc = side_mark(g.b.ws)))) return rc;
     } else if ((rc = launch_sort(sa, tb ? &sb : nullptr, M, err_flag, stream))) {
         return rc;
     }
-    const AdamC c = make_adamc(adam);
-    GatherJob ja{view(ta), idx_a, rows_a, wa};
-    GatherJob jb = tb ? GatherJob{view(tb), idx_b, rows_b, wb} : ja;
     {
         ProfScope prof(K_TABLE_GATHER_TRAIN, stream);
         FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_gather_train_kernel<L, E>), dim3((unsigned)((M + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)M, lay, err_flag)));
@@ -410,8 +431,8 @@ static int gather_train_impl(const char* who, const fr_table* ta, const fr_table
 extern "C" int fr_table_gather_train(const fr_table* t, const fr_adam* adam, const int64_t* idx, int64_t M,
                                      int32_t chunk, int32_t stride, float* rows_out, void* ws, size_t ws_bytes,
                                      uint32_t* err_flag, void* stream_) {
-    return gather_train_impl("fr_table_gather_train", t, nullptr, adam, idx, nullptr, M, chunk, stride, rows_out, nullptr,
-                             ws, nullptr, ws_bytes, err_flag, (hipStream_t)stream_);
+    return gather_train_impl({"fr_table_gather_train", adam, {t, idx, rows_out, ws}, {}, M, chunk, stride, ws_bytes, err_flag,
+                              (hipStream_t)stream_});
 }
 
 // fr_table_gather_train on `t` and fr_table_gather on a second, read-only table `ro` (its own id list and hyper-parameters)
@@ -420,8 +441,9 @@ extern "C" int fr_table_lookup_pair(const fr_table* t, const fr_adam* adam, cons
                                     void* ws, size_t ws_bytes, const fr_table* ro, const fr_adam* ro_adam,
                                     const int64_t* ro_idx, int64_t ro_M, float* ro_out, uint32_t* err_flag, void* stream_) {
     FR_CHECK_ARG(ro && ro_adam && ro_idx && ro_out && ro_M >= 1, "fr_table_lookup_pair: bad read-only lookup");
-    return gather_train_impl("fr_table_lookup_pair", t, nullptr, adam, idx, nullptr, M, 0, 0, rows_out, nullptr, ws, nullptr,
-                             ws_bytes, err_flag, (hipStream_t)stream_, false, ro, ro_adam, ro_idx, ro_M, ro_out);
+    const RoLookup rl{ro, ro_adam, ro_idx, ro_M, ro_out};
+    return gather_train_impl({"fr_table_lookup_pair", adam, {t, idx, rows_out, ws}, {}, M, 0, 0, ws_bytes, err_flag,
+                              (hipStream_t)stream_, false, &rl});
 }
 
 // The same with the segments of `idx` already in ws (FR_TABLE_PREPARED), e.g. copied from the workspace of another table
@@ -444,8 +466,8 @@ extern "C" int fr_table_join(const void* ws, void* stream_) {
 extern "C" int fr_table_gather_train_prepared(const fr_table* t, const fr_adam* adam, const int64_t* idx, int64_t M,
                                               int32_t chunk, int32_t stride, float* rows_out, void* ws, size_t ws_bytes,
                                               uint32_t* err_flag, void* stream_) {
-    return gather_train_impl("fr_table_gather_train_prepared", t, nullptr, adam, idx, nullptr, M, chunk, stride, rows_out,
-                             nullptr, ws, nullptr, ws_bytes, err_flag, (hipStream_t)stream_, true);
+    return gather_train_impl({"fr_table_gather_train_prepared", adam, {t, idx, rows_out, ws}, {}, M, chunk, stride, ws_bytes,
+                              err_flag, (hipStream_t)stream_, true});
 }
 
 extern "C" int fr_table_gather_train2(const fr_table* ta, const fr_table* tb, const fr_adam* adam, const int64_t* idx_a,
@@ -453,8 +475,8 @@ extern "C" int fr_table_gather_train2(const fr_table* ta, const fr_table* tb, co
                                       float* rows_b, int32_t flags, void* ws_a, void* ws_b, size_t ws_bytes,
                                       uint32_t* err_flag, void* stream_) {
     FR_CHECK_ARG(tb, "fr_table_gather_train2: second table is null");
-    return gather_train_impl("fr_table_gather_train2", ta, tb, adam, idx_a, idx_b, M, chunk, stride, rows_a, rows_b, ws_a,
-                             ws_b, ws_bytes, err_flag, (hipStream_t)stream_, (flags & FR_TABLE_PREPARED) != 0);
+    return gather_train_impl({"fr_table_gather_train2", adam, {ta, idx_a, rows_a, ws_a}, {tb, idx_b, rows_b, ws_b}, M, chunk,
+                              stride, ws_bytes, err_flag, (hipStream_t)stream_, (flags & FR_TABLE_PREPARED) != 0});
 }
 
 // The index-only part of fr_table_gather_train2, callable one batch AHEAD on another stream (it depends on nothing
@@ -465,46 +487,57 @@ extern "C" int fr_table_sort2(const int64_t* idx_a, const int64_t* idx_b, int64_
                               uint32_t* err_flag, void* stream_) {
     FR_CHECK_ARG(idx_a && idx_b && ws_a && ws_b && ws_a != ws_b && M >= 1 && M <= FR_SORT_MAX && dim >= 1 && n_rows_a >= 1 &&
                      n_rows_b >= 1 && lay_ok(chunk, stride), "fr_table_sort2: bad argument");
-    TableWs wa = table_layout(ws_a, M, dim), wb = table_layout(ws_b, M, dim);
+    const TableWs wa = table_layout(ws_a, M, dim), wb = table_layout(ws_b, M, dim);
     FR_CHECK_ARG(ws_bytes >= wa.bytes, "fr_table_sort2: workspace %zu < %zu bytes", ws_bytes, wa.bytes);
     const Lay lay{chunk, stride};
-    SortJob sa{idx_a, n_rows_a, wa.perm, wa.seg_start, wa.seg_row, nullptr, wa.nseg, nullptr, nullptr, lay};
-    SortJob sb{idx_b, n_rows_b, wb.perm, wb.seg_start, wb.seg_row, nullptr, wb.nseg, nullptr, nullptr, lay};
-    sa.seg_first = wa.seg_first;
-    sb.seg_first = wb.seg_first;
+    const SortJob sa = make_sort_job(idx_a, n_rows_a, wa, lay), sb = make_sort_job(idx_b, n_rows_b, wb, lay);
     return launch_sort(sa, &sb, M, err_flag, (hipStream_t)stream_);
 }
 
-static int apply_grad_impl(const char* who, const fr_table* ta, const fr_table* tb, const fr_adam* adam, int64_t M,
-                           int32_t chunk, int32_t stride, const float* rows_a, const float* grad_a, const float* rows_b,
-                           const float* grad_b, int32_t sweep_a, int32_t sweep_b, void* ws_a, void* ws_b, size_t ws_bytes,
-                           hipStream_t stream, int64_t Mb = -1, size_t ws_b_bytes = 0) {
+// One table's share of an update: its batch of M ids (sorted into `ws` by the lookup), the rows gathered for them, the gradient
+// rows that came back, and its sweep period.
+struct ApplySide {
+    const fr_table* t;
+    int64_t M;
+    const float* rows;
+    const float* grad;
+    int32_t sweep;
+    void* ws;
+    size_t ws_bytes;
+};
+
+// one (b.t == nullptr) or two tables of the same dim per launch
+static int apply_grad_impl(const char* who, const fr_adam* adam, const ApplySide& a, const ApplySide& b, int32_t chunk,
+                           int32_t stride, hipStream_t stream) {
+    const fr_table *const ta = a.t, *const tb = b.t;
     int rc;
-    if (Mb < 0) Mb = M, ws_b_bytes = ws_bytes;
     if ((rc = check_table_for(ta, adam, who)) || (tb && (rc = check_table_for(tb, adam, who)))) return rc;
-    FR_CHECK_ARG(rows_a && grad_a && ws_a && M >= 1 && M <= FR_SORT_MAX && ta->step >= 1 && lay_ok(chunk, stride),
+    FR_CHECK_ARG(a.rows && a.grad && a.ws && a.M >= 1 && a.M <= FR_SORT_MAX && ta->step >= 1 && lay_ok(chunk, stride),
                  "%s: bad argument", who);
-    FR_CHECK_ARG(!tb || (rows_b && grad_b && ws_b && ws_b != ws_a && tb->dim == ta->dim && tb->step >= 1 && Mb >= 1 &&
-                         Mb <= FR_SORT_MAX && (Mb == M || chunk == 0)),
+    FR_CHECK_ARG(!tb || (b.rows && b.grad && b.ws && b.ws != a.ws && tb->dim == ta->dim && tb->step >= 1 && b.M >= 1 &&
+                         b.M <= FR_SORT_MAX && (b.M == a.M || chunk == 0)),
                  "%s: bad second table", who);
     const Lay lay{chunk, stride};
-    TableWs wa = table_layout(ws_a, M, ta->dim);
-    TableWs wb = tb ? table_layout(ws_b, Mb, tb->dim) : wa;
-    FR_CHECK_ARG(ws_bytes >= wa.bytes && (!tb || ws_b_bytes >= wb.bytes), "%s: workspace %zu < %zu bytes", who, ws_bytes, wa.bytes);
-    if ((rc = side_join(ws_a, stream)) || (tb && (rc = side_join(ws_b, stream)))) return rc;
+    const TableWs wa = table_layout(a.ws, a.M, ta->dim);
+    const TableWs wb = tb ? table_layout(b.ws, b.M, tb->dim) : wa;
+    FR_CHECK_ARG(a.ws_bytes >= wa.bytes && (!tb || b.ws_bytes >= wb.bytes), "%s: workspace %zu < %zu bytes", who, a.ws_bytes,
+                 wa.bytes);
+    if ((rc = side_join(a.ws, stream)) || (tb && (rc = side_join(b.ws, stream)))) return rc;
     // waves reserved for the sweeper = rows of a full slice (the slice itself depends on the effective step, which may
-    // live on the device)
+    // live on the device); none where rows outside the batch do not change
     const int per_wave = sweep_rows_per_wave(ta->dim);
-    if (replay_is_identity(adam)) sweep_a = sweep_b = 0;     // rows outside the batch do not change: no sweeper waves
-    const long long sw_a = sweep_a > 0 ? ((ta->n_rows + sweep_a - 1) / sweep_a + per_wave - 1) / per_wave : 0;
-    const long long sw_b = tb && sweep_b > 0 ? ((tb->n_rows + sweep_b - 1) / sweep_b + per_wave - 1) / per_wave : 0;
-    const long long waves = std::max(M + sw_a, tb ? Mb + sw_b : 0);
+    const bool sweeps = !learner_facts(adam).identity;
+    auto job = [&](const ApplySide& s, const TableWs& w) {
+        const int period = sweeps ? s.sweep : 0;
+        const long long sw = period > 0 ? ((s.t->n_rows + period - 1) / period + per_wave - 1) / per_wave : 0;
+        return ApplyJob{view(s.t), w, s.rows, s.grad, period, (int)sw, (long long)s.M};
+    };
+    const ApplyJob ja = job(a, wa), jb = tb ? job(b, wb) : ja;
+    const long long waves = std::max(ja.M + ja.sw_n, tb ? jb.M + jb.sw_n : 0);
     const AdamC c = make_adamc(adam);
-    ApplyJob ja{view(ta), wa, rows_a, grad_a, (int)sweep_a, (int)sw_a, (long long)M};
-    ApplyJob jb = tb ? ApplyJob{view(tb), wb, rows_b, grad_b, (int)sweep_b, (int)sw_b, (long long)Mb} : ja;
     {
         ProfScope prof(K_TABLE_APPLY_GRAD, stream);
-        FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_apply_grad_kernel<L, E>), dim3((unsigned)((waves + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)M, lay)));
+        FR_DISPATCH_L(adam->learner, FR_DISPATCH_E(ta->dim, FR_LAUNCH(prof, (table_apply_grad_kernel<L, E>), dim3((unsigned)((waves + 3) / 4), tb ? 2 : 1), dim3(256), 0, stream, ja, jb, c, (long long)a.M, lay)));
     }
     FR_CHECK_LAUNCH();
     return FR_OK;
@@ -513,8 +546,8 @@ static int apply_grad_impl(const char* who, const fr_table* ta, const fr_table* 
 extern "C" int fr_table_apply_grad(const fr_table* t, const fr_adam* adam, int64_t M, int32_t chunk, int32_t stride,
                                    const float* rows, const float* grad_rows, int32_t sweep_period, void* ws,
                                    size_t ws_bytes, void* stream_) {
-    return apply_grad_impl("fr_table_apply_grad", t, nullptr, adam, M, chunk, stride, rows, grad_rows, nullptr, nullptr,
-                           sweep_period, 0, ws, nullptr, ws_bytes, (hipStream_t)stream_);
+    return apply_grad_impl("fr_table_apply_grad", adam, {t, M, rows, grad_rows, sweep_period, ws, ws_bytes}, {}, chunk, stride,
+                           (hipStream_t)stream_);
 }
 
 extern "C" int fr_table_apply_grad2(const fr_table* ta, const fr_table* tb, const fr_adam* adam, int64_t M,
@@ -522,8 +555,8 @@ extern "C" int fr_table_apply_grad2(const fr_table* ta, const fr_table* tb, cons
                                     const float* rows_b, const float* grad_b, int32_t sweep_a, int32_t sweep_b,
                                     void* ws_a, void* ws_b, size_t ws_bytes, void* stream_) {
     FR_CHECK_ARG(tb, "fr_table_apply_grad2: second table is null");
-    return apply_grad_impl("fr_table_apply_grad2", ta, tb, adam, M, chunk, stride, rows_a, grad_a, rows_b, grad_b, sweep_a,
-                           sweep_b, ws_a, ws_b, ws_bytes, (hipStream_t)stream_);
+    return apply_grad_impl("fr_table_apply_grad2", adam, {ta, M, rows_a, grad_a, sweep_a, ws_a, ws_bytes},
+                           {tb, M, rows_b, grad_b, sweep_b, ws_b, ws_bytes}, chunk, stride, (hipStream_t)stream_);
 }
 
 // fr_table_apply_grad on TWO tables of one width in one launch, each with its own id count (a user table next to the item table
@@ -534,6 +567,6 @@ extern "C" int fr_table_apply_grad_two(const fr_table* ta, const fr_table* tb, c
                                        int32_t sweep_a, int32_t sweep_b, void* ws_a, size_t ws_a_bytes, void* ws_b,
                                        size_t ws_b_bytes, void* stream_) {
     FR_CHECK_ARG(tb && Mb >= 1, "fr_table_apply_grad_two: second table is null");
-    return apply_grad_impl("fr_table_apply_grad_two", ta, tb, adam, Ma, 0, 0, rows_a, grad_a, rows_b, grad_b, sweep_a, sweep_b,
-                           ws_a, ws_b, ws_a_bytes, (hipStream_t)stream_, Mb, ws_b_bytes);
+    return apply_grad_impl("fr_table_apply_grad_two", adam, {ta, Ma, rows_a, grad_a, sweep_a, ws_a, ws_a_bytes},
+                           {tb, Mb, rows_b, grad_b, sweep_b, ws_b, ws_b_bytes}, 0, 0, (hipStream_t)stream_);
 }

@@ -8,6 +8,8 @@ namespace fr {
 // Row `r` of a resolved table as of its step T.step, in registers (d = lane + 64*e): the parameters, caught up through
 // the zero-gradient steps it has not seen (replay of the lazy Adam update).  An id outside [0, n_rows) sets
 // FR_DEV_ERR_INDEX_RANGE and reads row 0.  fr_table_gather and fr_dyn_neg_dot_select read rows through this.
+// Two bodies on purpose: they differ in the ORDER of the loads (Adam asks for `last` first, the others for the row, which may
+// be all they need); one body with the row first for all compiled table.hip and dyn_neg.hip to other device code.
 template <int E, class L = LearnerAdam>
 __device__ __forceinline__ void row_at_step(const TableV& T, const AdamC& c, long long r, RowFrag<E>& p, uint32_t* err,
                                             const int lane) {
@@ -34,7 +36,7 @@ __device__ __forceinline__ void row_at_step(const TableV& T, const AdamC& c, lon
     if (t0 < T.step) {
         load_row<E>(m, T.m + (size_t)row * D, D, lane);
         load_row<E>(v, T.v + (size_t)row * D, D, lane);
-        replay<E>(p, m, v, t0, T.step, c, lane);
+        replay1<L, E>(p, m, v, t0, T.step, c);
     }
 }
 
@@ -163,8 +165,7 @@ __device__ __forceinline__ void sweep_row(const TableV& T, const AdamC& c, long 
     if (uniform(st) >= skip_from) return;
     const int t0 = uniform(lt);
     if (t0 >= upto) return;
-    if constexpr (L::ID == FR_LEARNER_ADAM) replay<E>(p, m, v, t0, upto, c, lane);
-    else replay1<L, E>(p, m, v, t0, upto, c);
+    replay1<L, E>(p, m, v, t0, upto, c);
     store_row<E>(p, T.p + (size_t)row * D, D, lane);
     if (L::HAS_M) store_row<E>(m, T.m + (size_t)row * D, D, lane);
     if (L::HAS_V) store_row<E>(v, T.v + (size_t)row * D, D, lane);
@@ -294,13 +295,13 @@ __device__ __forceinline__ void sweep_row_pair(const TableV& T, const AdamC& c, 
     const bool doA = uniform(sa) < skip_from && ta < upto;
     const bool doB = uniform(sb) < skip_from && tb < upto;
     if (doA && doB) {
-        if (ta < tb) replay<E>(pa, ma, va, ta, tb, c, lane);
-        else if (tb < ta) replay<E>(pb, mb, vb, tb, ta, c, lane);
-        replay2<E>(pa, ma, va, pb, mb, vb, ta > tb ? ta : tb, upto, c, lane);
+        if (ta < tb) replay1<L, E>(pa, ma, va, ta, tb, c);
+        else if (tb < ta) replay1<L, E>(pb, mb, vb, tb, ta, c);
+        replay2l<L, E>(pa, ma, va, pb, mb, vb, ta > tb ? ta : tb, upto, c);
     } else if (doA) {
-        replay<E>(pa, ma, va, ta, upto, c, lane);
+        replay1<L, E>(pa, ma, va, ta, upto, c);
     } else if (doB) {
-        replay<E>(pb, mb, vb, tb, upto, c, lane);
+        replay1<L, E>(pb, mb, vb, tb, upto, c);
     }
     if (doA) {
         store_row<E>(pa, T.p + (size_t)rowA * D, D, lane);

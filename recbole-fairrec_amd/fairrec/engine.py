@@ -15,7 +15,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _C
-from .optim import LEARNER_ADAM, LEARNER_RMSPROP, LEARNER_STATE, AdamHyper, LazyLookup, LazyTable
+from .optim import LEARNER_ADAM, LEARNERS, AdamHyper, LazyLookup, LazyTable
 
 
 class DenseState:
@@ -28,9 +28,7 @@ class DenseState:
 
     def _alloc(self):
         # only the state the learner keeps (include/fairrec_hip.h): Adam m and v, Adagrad / RMSprop m, SGD none
-        has_m, has_v = (k is not None for k in LEARNER_STATE[self.learner])
-        self.m = torch.zeros_like(self.p.data) if has_m else None
-        self.v = torch.zeros_like(self.p.data) if has_v else None
+        self.m, self.v = LEARNERS[self.learner].alloc(self.p.data)
 
     def set_learner(self, learner: int):
         if learner != self.learner:
@@ -41,13 +39,24 @@ class DenseState:
 
     def state(self):
         """torch.optim.<Learner>'s per-parameter state (None where torch keeps none)."""
-        m_name, v_name = LEARNER_STATE[self.learner]
-        if m_name is None or (self.learner == LEARNER_RMSPROP and self.step == 0):
-            return None
-        st = {"step": torch.tensor(float(self.step)), m_name: self.m}
-        if v_name is not None:
-            st[v_name] = self.v
-        return st
+        return LEARNERS[self.learner].entry(self.step, self.m, self.v)
+
+    def load_state(self, st):
+        """Inverse of `state`.  `st` None = the loaded dict has no entry for this tensor: see fairrec.optim.Learner."""
+        rec = LEARNERS[self.learner]
+        if st is None and rec.entry_always:
+            return
+        if st is not None and rec.m_name is not None:
+            self.step = int(st["step"])
+            self.m.copy_(st[rec.m_name])
+            if rec.v_name is not None:
+                self.v.copy_(st[rec.v_name])
+        else:
+            self.step = 0
+            if self.m is not None:
+                self.m.zero_()
+        if self.step_dev is not None:
+            self.step_dev.fill_(self.step)
 
 
 class GenericEngine:
@@ -324,24 +333,8 @@ class GenericEngine:
         return {k: d.state() for k, d in self._dense.items() if self._owned(k, group)}
 
     def load_dense_state(self, sd, group=None):
-        """Adam: the entries of `sd`.  Other learners: every dense tensor of `group` (one without an entry -- SGD, an
-        RMSprop tensor never stepped -- is reset to no state); names that are no dense tensor here are ignored."""
-        if group is not None or any(d.learner != LEARNER_ADAM for d in self._dense.values()):
-            for k, d in self._dense.items():
-                if d.learner == LEARNER_ADAM or not self._owned(k, group):
-                    continue
-                st = sd.get(k)
-                m_name = LEARNER_STATE[d.learner][0]
-                d.step = int(st["step"]) if st is not None and m_name is not None else 0
-                if d.m is not None:
-                    d.m.copy_(st[m_name]) if st is not None else d.m.zero_()
-                if d.step_dev is not None:
-                    d.step_dev.fill_(d.step)
-            sd = {k: st for k, st in sd.items() if k in self._dense and self._dense[k].learner == LEARNER_ADAM}
-        for k, st in sd.items():
-            d = self._dense[k]
-            d.step = int(st["step"])
-            if d.step_dev is not None:
-                d.step_dev.fill_(d.step)
-            d.m.copy_(st["exp_avg"])
-            d.v.copy_(st["exp_avg_sq"])
+        """Every dense tensor of `group`, with its entry of `sd` or None (`DenseState.load_state`); names that are no dense
+        tensor here are ignored."""
+        for k, d in self._dense.items():
+            if self._owned(k, group):
+                d.load_state(sd.get(k))

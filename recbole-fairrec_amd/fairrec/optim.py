@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import numpy as np
@@ -57,10 +58,43 @@ def _used_on_side_stream(t: torch.Tensor):
 
 
 LEARNER_ADAM, LEARNER_SGD, LEARNER_ADAGRAD, LEARNER_RMSPROP = 0, 1, 2, 3     # fr_adam.learner (include/fairrec_hip.h)
-LEARNER_NAMES = {LEARNER_ADAM: "adam", LEARNER_SGD: "sgd", LEARNER_ADAGRAD: "adagrad", LEARNER_RMSPROP: "rmsprop"}
-# the state arrays each learner keeps: (fr_table.m, fr_table.v) and their names in torch's state_dict
-LEARNER_STATE = {LEARNER_ADAM: ("exp_avg", "exp_avg_sq"), LEARNER_SGD: (None, None), LEARNER_ADAGRAD: ("sum", None),
-                 LEARNER_RMSPROP: ("square_avg", None)}
+
+
+@dataclass(frozen=True)
+class Learner:
+    """Everything the host side knows about one learner; `LEARNERS` (end of this file) holds one per id.  The device side's
+    counterpart is the `Learner*` policy struct of csrc/common.hpp.
+
+    An entry ABSENT from a loaded state_dict (`LazyTable.load_optim_state(None)`, `DenseState.load_state(None)`):
+    where `entry_always` holds the dict does not speak about that tensor, which is left as it is.  Otherwise a table keeps
+    its step unless `state_at_first_step` (an absent entry then means "never stepped": step 0, state zeroed) and is marked
+    current, while a dense tensor goes to step 0 with its state zeroed whatever the learner.  That the two differ for SGD
+    and Adagrad is how the learners were added, not a design; it is kept as it is and stated here only."""
+    id: int                           # fr_adam.learner
+    name: str                         # the `learner` config value
+    torch_cls: type                   # the torch.optim class whose state_dict layout is written and read
+    fused_cls: type                   # its FusedLazyOptimizer
+    m_name: Optional[str]             # torch's names of the state arrays kept in fr_table.m / .v (None: not kept)
+    v_name: Optional[str] = None
+    state_at_first_step: bool = False      # torch creates a parameter's state at its first step: none is written before
+    state_from_construction: bool = False  # torch creates the state of EVERY parameter it was built on, stepped or not
+    entry_always: bool = False        # every table and dense tensor has an entry in the state_dict written here
+    # param_groups[0] in torch's layout: the constructor's arguments plus these keys; None = the arguments were completed
+    # by the installed torch itself (`_torch_group_keys`), nothing to add
+    group_extra: Optional[dict] = None
+
+    def entry(self, step: int, m, v) -> Optional[Dict[str, torch.Tensor]]:
+        """torch's per-parameter state of a tensor at `step` with state arrays m / v (None where torch has none)."""
+        if self.m_name is None or (self.state_at_first_step and step == 0):
+            return None
+        st = {"step": torch.tensor(float(step)), self.m_name: m}
+        if self.v_name is not None:
+            st[self.v_name] = v
+        return st
+
+    def alloc(self, like: torch.Tensor):
+        """Zeroed (m, v) for a parameter tensor: only the arrays the learner keeps."""
+        return tuple(torch.zeros_like(like) if n is not None else None for n in (self.m_name, self.v_name))
 
 
 def sgd_step_scalars(lr: float, weight_decay: float, cap: int) -> np.ndarray:
@@ -87,41 +121,21 @@ def rmsprop_step_scalars(lr: float, cap: int) -> np.ndarray:
     return out
 
 
-class AdamHyper:
-    """lr / weight_decay / betas / eps + the device table of per-step scalars (fr_adam in the C ABI)."""
-    learner = LEARNER_ADAM
-
-    def __init__(self, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, device="cuda", cap=32768):
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
-        self.device = torch.device(device)
-        while True:
-            tab = adam_step_scalars(self.lr, self.betas[0], self.betas[1], cap, self.weight_decay, self.eps)
-            # steps beyond `cap` reuse entry `cap`: only valid once both scalars stopped changing in fp32
-            if (tab[4 * cap] == np.float32(self.lr) and tab[4 * cap + 1] == np.float32(1.0)) or cap >= (1 << 22):
-                break
-            cap *= 2
-        self.cap = cap
-        self.saturated = bool(tab[4 * cap] == np.float32(self.lr) and tab[4 * cap + 1] == np.float32(1.0))
-        self.host_scalars = tab
-        self.scalars = torch.from_numpy(tab).to(self.device) if self.device.type == "cuda" else None
-        self._c = _C.FrAdam(_C.ptr(self.scalars), cap, 0, self.weight_decay, self.betas[0], self.betas[1], self.eps)
-
-    def c(self) -> "_C.FrAdam":
-        return self._c
-
-    def check_step(self, step: int):
-        if step > self.cap and not self.saturated:
-            raise _C.FairrecError(f"Adam step {step} exceeds the scalar table ({self.cap}) and the bias "
-                                  "corrections have not saturated; raise `cap`")
-
-
-class _PlainHyper:
-    """The fr_adam struct of a learner whose per-step scalars are constant from step 1 on (lr_decay = 0): a one-entry
-    table.  Same `c()` / `check_step` contract as AdamHyper."""
+class _Hyper:
+    """The hyper-parameters of one optimizer + the device table of its per-step scalars (fr_adam in the C ABI).  A subclass
+    sets `learner`, its own attributes (`weight_decay` and `device` among them) and calls `_finish`."""
     learner = None
 
-    def _finish(self, tab: np.ndarray, cap: int, beta1: float, beta2: float, eps: float, saturated: bool = True):
-        self.cap, self.saturated, self.host_scalars = cap, saturated, tab
+    def _finish(self, scalars, cap: int, saturated, beta1: float, beta2: float, eps: float):
+        """`scalars(cap)` builds the host table.  Steps beyond `cap` reuse entry `cap`, which is only valid once that entry
+        has stopped changing in fp32 (`saturated(tab, cap)`): `cap` doubles until then, or up to 2^22."""
+        while True:
+            tab = scalars(cap)
+            self.saturated = bool(saturated(tab, cap))
+            if self.saturated or cap >= (1 << 22):
+                break
+            cap *= 2
+        self.cap, self.host_scalars = cap, tab
         self.scalars = torch.from_numpy(tab).to(self.device) if self.device.type == "cuda" else None
         self._c = _C.FrAdam(_C.ptr(self.scalars), cap, self.learner, self.weight_decay, beta1, beta2, eps)
 
@@ -130,21 +144,34 @@ class _PlainHyper:
 
     def check_step(self, step: int):
         if step > self.cap and not self.saturated:
-            raise _C.FairrecError(f"{LEARNER_NAMES[self.learner]} step {step} exceeds the scalar table ({self.cap}); "
-                                  "raise `cap`")
+            raise _C.FairrecError(f"{LEARNERS[self.learner].name} step {step} exceeds the scalar table ({self.cap}) and "
+                                  "its scalars have not saturated; raise `cap`")
 
 
-class SGDHyper(_PlainHyper):
-    """torch.optim.SGD(params, lr, weight_decay=wd): momentum 0, no state."""
+class AdamHyper(_Hyper):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay): state `exp_avg`, `exp_avg_sq`.  The table holds the bias
+    corrections of the steps up to `cap` (grown until both stopped changing in fp32)."""
+    learner = LEARNER_ADAM
+
+    def __init__(self, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, device="cuda", cap=32768):
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
+        self.device = torch.device(device)
+        self._finish(lambda cap: adam_step_scalars(self.lr, self.betas[0], self.betas[1], cap, self.weight_decay, self.eps),
+                     cap, lambda tab, cap: tab[4 * cap] == np.float32(self.lr) and tab[4 * cap + 1] == np.float32(1.0),
+                     self.betas[0], self.betas[1], self.eps)
+
+
+class SGDHyper(_Hyper):
+    """torch.optim.SGD(params, lr, weight_decay=wd): momentum 0, no state.  Constant scalars: a one-entry table."""
     learner = LEARNER_SGD
 
     def __init__(self, lr=1e-3, weight_decay=0.0, device="cuda"):
         self.lr, self.weight_decay, self.eps = float(lr), float(weight_decay), 0.0
         self.device = torch.device(device)
-        self._finish(sgd_step_scalars(self.lr, self.weight_decay, 1), 1, 0.0, 0.0, 0.0)
+        self._finish(lambda cap: sgd_step_scalars(self.lr, self.weight_decay, cap), 1, lambda tab, cap: True, 0.0, 0.0, 0.0)
 
 
-class AdagradHyper(_PlainHyper):
+class AdagradHyper(_Hyper):
     """torch.optim.Adagrad(params, lr, weight_decay=wd): eps 1e-10, initial_accumulator_value 0; state `sum`.  With
     lr_decay > 0 the table holds clr_j for j <= cap (grown until clr stops changing in fp32, or 2^22 steps)."""
     learner = LEARNER_ADAGRAD
@@ -152,27 +179,20 @@ class AdagradHyper(_PlainHyper):
     def __init__(self, lr=1e-2, lr_decay=0.0, weight_decay=0.0, eps=1e-10, device="cuda", cap=1):
         self.lr, self.lr_decay, self.weight_decay, self.eps = float(lr), float(lr_decay), float(weight_decay), float(eps)
         self.device = torch.device(device)
-        if self.lr_decay == 0.0:
-            cap = 1
-        while True:
-            tab = adagrad_step_scalars(self.lr, self.lr_decay, cap)
-            if self.lr_decay == 0.0 or cap >= (1 << 22) or tab[4 * cap] == np.float32(
-                    self.lr / (1 + cap * self.lr_decay)):
-                break
-            cap *= 2
-        saturated = self.lr_decay == 0.0 or bool(tab[4 * cap] == np.float32(self.lr / (1 + cap * self.lr_decay)))
-        self._finish(tab, cap, 0.0, 0.0, self.eps, saturated)
+        self._finish(lambda cap: adagrad_step_scalars(self.lr, self.lr_decay, cap), cap if self.lr_decay != 0.0 else 1,
+                     lambda tab, cap: self.lr_decay == 0.0 or tab[4 * cap] == np.float32(self.lr / (1 + cap * self.lr_decay)),
+                     0.0, 0.0, self.eps)
 
 
-class RMSpropHyper(_PlainHyper):
+class RMSpropHyper(_Hyper):
     """torch.optim.RMSprop(params, lr, weight_decay=wd): alpha 0.99 (fr_adam.beta2), eps 1e-8, momentum 0, not
-    centered; state `square_avg`."""
+    centered; state `square_avg`.  Constant scalars: a one-entry table."""
     learner = LEARNER_RMSPROP
 
     def __init__(self, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, device="cuda"):
         self.lr, self.alpha, self.eps, self.weight_decay = float(lr), float(alpha), float(eps), float(weight_decay)
         self.device = torch.device(device)
-        self._finish(rmsprop_step_scalars(self.lr, 1), 1, 0.0, self.alpha, self.eps)
+        self._finish(lambda cap: rmsprop_step_scalars(self.lr, cap), 1, lambda tab, cap: True, 0.0, self.alpha, self.eps)
 
 
 class LazyTable:
@@ -209,9 +229,7 @@ class LazyTable:
         if self.m is None and self.v is None:
             if self.trainable:
                 # only the state its learner keeps (SGD: none, Adagrad / RMSprop: m; include/fairrec_hip.h)
-                has_m, has_v = (k is not None for k in LEARNER_STATE[self.learner])
-                self.m = torch.zeros_like(self.weight) if has_m else None
-                self.v = torch.zeros_like(self.weight) if has_v else None
+                self.m, self.v = LEARNERS[self.learner].alloc(self.weight)
             else:  # frozen table: never replayed (last == step == 0), m/v never touched
                 self.m = self.v = self.weight
 
@@ -273,6 +291,32 @@ class LazyTable:
                                           out.data_ptr(), _C.ptr(err_flag), _C.current_stream()), "fr_table_gather")
         return out
 
+    # --- step bookkeeping shared by the training entry points below ---------------------------------------
+    def _ensure_ws(self, M: int) -> bool:
+        """Make `_ws` large enough for a training lookup of M ids; True when it had to be (re)allocated."""
+        need = _C.lib().fr_table_train_workspace_bytes(M, self.dim)
+        if self._ws is not None and self._ws.numel() >= need:
+            return False
+        self._ws = torch.empty(need, dtype=torch.uint8, device=self.weight.device)
+        return True
+
+    def _take_pending(self, M: Optional[int] = None, need_rows: bool = False):
+        """(M, rows) that the preceding gather_train* parked; `M`: the id count it must have had, `need_rows`: it must have
+        kept the rows tensor (the lookups on raw pointers do not)."""
+        if self._pending is None or (need_rows and self._pending[1] is None):
+            raise _C.FairrecError("apply_grad without a preceding gather_train")
+        if M is not None and self._pending[0] != M:
+            raise _C.FairrecError("apply_grad without a matching gather_train")
+        return self._pending
+
+    def _finish_step(self):
+        """The optimizer step of the pending batch has been issued."""
+        self.step += 1
+        self._dirty = True
+        self._pending = None
+        self._grad_rows = None
+        self._keep = None
+
     # --- generic training pair (models with an MLP between the embeddings and the loss) -----------------
     def gather_train(self, hyper: AdamHyper, idx: torch.Tensor, err_flag: Optional[torch.Tensor] = None,
                      segments_of: Optional["LazyTable"] = None) -> torch.Tensor:
@@ -298,9 +342,7 @@ class LazyTable:
         dev = self.weight.device
         rows = torch.empty((M, self.dim), dtype=torch.float32, device=dev)
         ro_rows = torch.empty((ro_idx.numel(), ro.dim), dtype=torch.float32, device=dev)
-        need = _C.lib().fr_table_train_workspace_bytes(M, self.dim)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._ensure_ws(M)
         t, r = self.c(self.step + 1), ro.c()
         hyper.check_step(self.step + 1)
         _C.check(_C.lib().fr_table_lookup_pair(ctypes.byref(t), ctypes.byref(hyper.c()), idx.data_ptr(), M, rows.data_ptr(),
@@ -318,9 +360,7 @@ class LazyTable:
                           err_flag: Optional[torch.Tensor] = None, segments_of: Optional["LazyTable"] = None):
         """The same on raw device pointers with a slot layout (fairrec_hip.h): M ids read from / M rows written into
         exchange buffers in place.  The caller keeps the buffers alive until `apply_grad_from`."""
-        need = _C.lib().fr_table_train_workspace_bytes(M, self.dim)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.weight.device)
+        self._ensure_ws(M)
         t = self.c(self.step + 1)
         hyper.check_step(self.step + 1)
         if segments_of is not None and segments_of._ws is not None and segments_of.n_rows == self.n_rows:
@@ -342,9 +382,7 @@ class LazyTable:
 
     def apply_grad(self, hyper: AdamHyper, grad_rows: Optional[torch.Tensor] = None, sweep_period: int = 0):
         """fr_table_apply_grad: duplicate-summed gradient + Adam step `self.step + 1` + sweeper slice."""
-        if self._pending is None:
-            raise _C.FairrecError("apply_grad without a preceding gather_train")
-        M, rows = self._pending
+        M, rows = self._take_pending(need_rows=True)
         g = grad_rows if grad_rows is not None else self._grad_rows
         if g is None:
             raise _C.FairrecError("no gradient reached the gathered rows (loss.backward() not called?)")
@@ -356,17 +394,12 @@ class LazyTable:
                         chunk: int = 0, stride: int = 0):
         """fr_table_apply_grad on raw device pointers with a slot layout (the rows of the preceding
         `gather_train_into` and the gradient rows that came back for them)."""
-        if self._pending is None or self._pending[0] != M:
-            raise _C.FairrecError("apply_grad without a matching gather_train")
+        self._take_pending(M)
         t = self.c(self.step + 1)
         _C.check(_C.lib().fr_table_apply_grad(ctypes.byref(t), ctypes.byref(hyper.c()), M, chunk, stride, rows_ptr,
                                               grad_ptr, int(sweep_period), self._ws.data_ptr(), self._ws.numel(),
                                               _C.current_stream()), "fr_table_apply_grad")
-        self.step += 1
-        self._dirty = True
-        self._pending = None
-        self._grad_rows = None
-        self._keep = None
+        self._finish_step()
 
     # --- two tables of a step in one launch each (the user and item table of the row-sharded step) ------
     @staticmethod
@@ -382,11 +415,9 @@ class LazyTable:
                           rows_b: int, chunk: int = 0, stride: int = 0, err_flag: Optional[torch.Tensor] = None,
                           prepared: bool = False):
         assert ta.dim == tb.dim and ta.step == tb.step
-        need = _C.lib().fr_table_train_workspace_bytes(M, ta.dim)
         for t in (ta, tb):
-            if t._ws is None or t._ws.numel() < need:
-                assert not prepared, "prepared workspaces must be installed as table._ws by the caller"
-                t._ws = torch.empty(need, dtype=torch.uint8, device=t.weight.device)
+            grown = t._ensure_ws(M)
+            assert not (grown and prepared), "prepared workspaces must be installed as table._ws by the caller"
         hyper.check_step(ta.step + 1)
         ca, cb = ta.c(ta.step + 1), tb.c(tb.step + 1)
         if not prepared:
@@ -405,8 +436,7 @@ class LazyTable:
     def apply_grad_pair(ta: "LazyTable", tb: "LazyTable", hyper: AdamHyper, M: int, rows_a: int, grad_a: int, rows_b: int,
                         grad_b: int, sweep_a: int, sweep_b: int, chunk: int = 0, stride: int = 0):
         for t in (ta, tb):
-            if t._pending is None or t._pending[0] != M:
-                raise _C.FairrecError("apply_grad without a matching gather_train")
+            t._take_pending(M)
         ca, cb = ta.c(ta.step + 1), tb.c(tb.step + 1)
         _C.check(_C.lib().fr_table_apply_grad2(ctypes.byref(ca), ctypes.byref(cb), ctypes.byref(hyper.c()), M, chunk,
                                                stride, rows_a, grad_a, rows_b, grad_b, int(sweep_a), int(sweep_b),
@@ -414,11 +444,7 @@ class LazyTable:
                                                min(ta._ws.numel(), tb._ws.numel()), _C.current_stream()),
                  "fr_table_apply_grad2")
         for t in (ta, tb):
-            t.step += 1
-            t._dirty = True
-            t._pending = None
-            t._grad_rows = None
-            t._keep = None
+            t._finish_step()
 
     NARROW_SWEEP = int(os.environ.get("FAIRREC_NARROW_SWEEP", 64))
 
@@ -428,11 +454,9 @@ class LazyTable:
         parked and the gradient rows autograd left -- in ONE launch (fr_table_apply_grad_two)."""
         args = []
         for t in (ta, tb):
-            if t._pending is None or t._pending[1] is None:
-                raise _C.FairrecError("apply_grad without a preceding gather_train")
+            M, rows = t._take_pending(need_rows=True)
             if t._grad_rows is None:
                 raise _C.FairrecError("no gradient reached the gathered rows (loss.backward() not called?)")
-            M, rows = t._pending
             g = t._grad_rows.contiguous()
             assert g.shape == rows.shape and g.dtype == torch.float32
             args.append((M, rows, g))
@@ -443,11 +467,7 @@ class LazyTable:
                                                   ta._ws.data_ptr(), ta._ws.numel(), tb._ws.data_ptr(), tb._ws.numel(),
                                                   _C.current_stream()), "fr_table_apply_grad_two")
         for t in (ta, tb):
-            t.step += 1
-            t._dirty = True
-            t._pending = None
-            t._grad_rows = None
-            t._keep = None
+            t._finish_step()
 
     def default_sweep(self, M: int) -> int:
         """Sweep about M rows per step, so that no row is more than n_rows / M steps stale.  A one-column table (a bias) is
@@ -457,44 +477,28 @@ class LazyTable:
         s = max(8, math.ceil(self.n_rows / max(M, 1)))
         return min(s, max(8, self.NARROW_SWEEP)) if self.dim == 1 else s
 
-    # --- interchange with torch.optim.Adam.state_dict() (trainer.py:221-240 checkpoints) ---------------
-    def adam_state(self, hyper: AdamHyper) -> Dict[str, torch.Tensor]:
-        self.sync_step()
-        self.flush(hyper)
-        return {"step": torch.tensor(float(self.step)), "exp_avg": self.m, "exp_avg_sq": self.v}
-
+    # --- interchange with torch.optim.<Learner>.state_dict() (trainer.py:221-240 checkpoints) ------------
     def optim_state(self, hyper) -> Optional[Dict[str, torch.Tensor]]:
-        """This table's entry of its learner's torch state_dict, flushed to `step`: Adam's as `adam_state`; Adagrad
-        {step, sum}; RMSprop {step, square_avg} once stepped (torch creates it at the first step), else None; SGD None."""
-        if self.learner == LEARNER_ADAM:
-            return self.adam_state(hyper)
+        """This table's entry of its learner's torch state_dict, flushed to `step` (`Learner.entry`: Adam {step, exp_avg,
+        exp_avg_sq}; Adagrad {step, sum}; RMSprop {step, square_avg} once stepped, else None; SGD None)."""
         self.sync_step()
         self.flush(hyper)
-        name = LEARNER_STATE[self.learner][0]
-        if name is None or (self.learner == LEARNER_RMSPROP and self.step == 0):
-            return None
-        return {"step": torch.tensor(float(self.step)), name: self.m}
+        return LEARNERS[self.learner].entry(self.step, self.m, self.v)
 
     def load_optim_state(self, state: Optional[Dict[str, torch.Tensor]]):
-        """Inverse of `optim_state`; `state` None (SGD, or an RMSprop parameter never stepped) leaves the table current as
-        it stands."""
-        if self.learner == LEARNER_ADAM:
-            return self.load_adam_state(state)
+        """Inverse of `optim_state`.  `state` None = the loaded dict has no entry for this table: see `Learner`."""
+        rec = LEARNERS[self.learner]
+        if state is None and rec.entry_always:
+            return
         self.ensure_state()
-        name = LEARNER_STATE[self.learner][0]
-        if state is not None and name is not None:
+        if state is not None and rec.m_name is not None:
             self.step = int(state["step"])
-            self.m.copy_(state[name])
-        elif self.learner == LEARNER_RMSPROP:
+            self.m.copy_(state[rec.m_name])
+            if rec.v_name is not None:
+                self.v.copy_(state[rec.v_name])
+        elif rec.state_at_first_step:
             self.step = 0
             self.m.zero_()
-        self._mark_current()
-
-    def load_adam_state(self, state: Dict[str, torch.Tensor]):
-        self.ensure_state()
-        self.step = int(state["step"])
-        self.m.copy_(state["exp_avg"])
-        self.v.copy_(state["exp_avg_sq"])
         self._mark_current()
 
     def _mark_current(self):
@@ -547,11 +551,14 @@ class FusedLazyOptimizer:
     `hyper` (AdamHyper, SGDHyper, AdagradHyper, RMSpropHyper); the subclasses below build it from torch's arguments.
     """
 
-    def __init__(self, engine, hyper, defaults: dict, sweep_period=None, group=None, clip_grad_norm=None):
+    def __init__(self, engine, hyper, args: dict, sweep_period=None, group=None, clip_grad_norm=None):
+        """`args`: the arguments of torch's constructor that the subclass was given."""
         self.engine = engine
         self.group = group
-        if hyper.learner != LEARNER_ADAM and not getattr(engine, "lazy_learners", False):
-            raise NotImplementedError(f"learner '{LEARNER_NAMES[hyper.learner]}' runs on the single-device generic engine "
+        self._group_arg = () if group is None else (group,)      # (an engine without groups takes no such argument)
+        rec = LEARNERS[hyper.learner]
+        if rec.id != LEARNER_ADAM and not getattr(engine, "lazy_learners", False):
+            raise NotImplementedError(f"learner '{rec.name}' runs on the single-device generic engine "
                                       f"only, not on {type(engine).__name__} (its step is Adam's)")
         # config `clip_grad_norm` = kwargs of torch.nn.utils.clip_grad_norm_, which the reference's loop calls between
         # backward() and step() (trainer.py:194-195); the gradient only exists inside step() here, so it is clipped there
@@ -563,32 +570,24 @@ class FusedLazyOptimizer:
                 raise NotImplementedError("clip_grad_norm: only norm_type 2 is on the device path")
         self.hyper = hyper
         self.learner = hyper.learner
-        self.defaults = defaults
-        if group is None:
-            engine.bind_optimizer(self, sweep_period)
-        else:
-            engine.bind_optimizer(self, sweep_period, group)
+        # what the name-keyed state_dict writes as param_groups[0]: Adam's own arguments, the other learners' completed
+        # with the defaults of the installed torch
+        self.defaults = dict(args) if rec.group_extra is not None else _torch_group_keys(rec.torch_cls, **args)
+        engine.bind_optimizer(self, sweep_period, *self._group_arg)
 
     def zero_grad(self, set_to_none: bool = True):
         if hasattr(self.engine, "zero_grad"):
-            self.engine.zero_grad(self.group) if self.group is not None else self.engine.zero_grad()
+            self.engine.zero_grad(*self._group_arg)
 
     def step(self, closure=None):
         if closure is not None:
             raise NotImplementedError("closure-based step is not supported by the fused path")
         if self.clip:
             self.last_grad_norm = self.engine.clip_grad_norm(float(self.clip["max_norm"]), self.group)
-        if self.group is not None:
-            self.engine.backward_adam(self.group)
-        else:
-            self.engine.backward_adam()
+        self.engine.backward_adam(*self._group_arg)
 
     def _tables(self):
-        return self.engine.tables(self.group) if self.group is not None else self.engine.tables()
-
-    def _torch_groups(self) -> dict:
-        return dict(self.defaults, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False,
-                    fused=None)
+        return self.engine.tables(*self._group_arg)
 
     def state_dict(self, param_names=None):
         """torch.optim.<Learner>'s state_dict content, flushed to the current step (Adam: `exp_avg`, `exp_avg_sq`, `step`;
@@ -597,17 +596,17 @@ class FusedLazyOptimizer:
         optimizer, i.e. `[n for n, _ in model.named_parameters()]`) torch's own layout -- integer indices and
         `param_groups[0]['params'] = [0, 1, ...]` -- which the reference's `optimizer.load_state_dict` accepts as it is
         (trainer.py:221-240, :258-284)."""
+        rec = LEARNERS[self.learner]
         state = {name: t.optim_state(self.hyper) for name, t in self._tables().items()}
         if hasattr(self.engine, "dense_state"):
-            state.update(self.engine.dense_state(self.group) if self.group is not None else self.engine.dense_state())
+            state.update(self.engine.dense_state(*self._group_arg))
         state = {n: st for n, st in state.items() if st is not None}
         if param_names is not None:
-            if self.learner == LEARNER_ADAGRAD:
-                # torch.optim.Adagrad creates the state of EVERY parameter at construction (step 0, sum 0)
+            if rec.state_from_construction:     # (Adagrad: step 0, sum 0 for the parameters not stepped here)
                 for n in param_names:
                     like = self._param_like(n)
                     if n not in state and like is not None:
-                        state[n] = {"step": torch.tensor(0.0), "sum": torch.zeros_like(like)}
+                        state[n] = rec.entry(0, *rec.alloc(like))
             idx = {n: k for k, n in enumerate(param_names)}
             missing = [n for n in state if n not in idx]
             if missing:
@@ -616,7 +615,7 @@ class FusedLazyOptimizer:
             # torch lists EVERY parameter the optimizer was built on, in order, and keeps state only for those that were
             # stepped (a frozen table -- NFCF's user table after reset_params, FairGo's tables in the finetune stage -- has
             # an index and no state); load_state_dict maps saved ids to parameters by POSITION and checks the group length
-            groups = dict(self._torch_groups(), params=list(range(len(param_names))))
+            groups = dict(self.defaults, **(rec.group_extra or {}), params=list(range(len(param_names))))
             return {"state": state, "param_groups": [groups]}
         return {"state": state, "param_groups": [dict(self.defaults, params=list(state.keys()))]}
 
@@ -631,28 +630,17 @@ class FusedLazyOptimizer:
         """Accepts this class's name-keyed layout and torch.optim.<Learner>'s integer-keyed one (a checkpoint written by the
         reference); the latter needs `param_names`, the parameter names in the reference optimizer's order."""
         tables = self._tables()
-        dense = {}
         state = sd["state"]
         if state and all(isinstance(k, int) for k in state):
             if param_names is None:
                 raise KeyError("optimizer state with torch's integer parameter indices: pass param_names "
                                "([n for n, _ in model.named_parameters()]) to name them")
             state = {param_names[k]: st for k, st in state.items()}
-        if self.learner != LEARNER_ADAM:
-            # a table with no entry (SGD; RMSprop never stepped) is current as loaded
-            for name, t in tables.items():
-                t.load_optim_state(state.get(name))
-            dense = {k: st for k, st in state.items() if k not in tables}
-            if hasattr(self.engine, "load_dense_state"):
-                self.engine.load_dense_state(dense, self.group)
-            return
-        for name, st in state.items():
-            if name in tables:
-                tables[name].load_adam_state(st)
-            else:
-                dense[name] = st
-        if dense:
-            self.engine.load_dense_state(dense)
+        # every tensor this optimizer owns, with its entry or None (what an absent entry means: `Learner`)
+        for name, t in tables.items():
+            t.load_optim_state(state.get(name))
+        if hasattr(self.engine, "load_dense_state"):
+            self.engine.load_dense_state({k: st for k, st in state.items() if k not in tables}, self.group)
 
 
 class FusedLazyAdam(FusedLazyOptimizer):
@@ -669,12 +657,8 @@ class FusedLazySGD(FusedLazyOptimizer):
     outside the batch never changes, so nothing is replayed or swept."""
 
     def __init__(self, engine, lr=1e-3, weight_decay=0.0, sweep_period=None, group=None, clip_grad_norm=None):
-        super().__init__(engine, SGDHyper(lr, weight_decay, device=engine.device),
-                         _torch_group_keys(torch.optim.SGD, lr=lr, weight_decay=weight_decay), sweep_period, group,
-                         clip_grad_norm)
-
-    def _torch_groups(self):
-        return dict(self.defaults)
+        super().__init__(engine, SGDHyper(lr, weight_decay, device=engine.device), dict(lr=lr, weight_decay=weight_decay),
+                         sweep_period, group, clip_grad_norm)
 
 
 class FusedLazyAdagrad(FusedLazyOptimizer):
@@ -684,11 +668,8 @@ class FusedLazyAdagrad(FusedLazyOptimizer):
     def __init__(self, engine, lr=1e-2, lr_decay=0.0, weight_decay=0.0, eps=1e-10, sweep_period=None, group=None,
                  clip_grad_norm=None):
         super().__init__(engine, AdagradHyper(lr, lr_decay, weight_decay, eps, device=engine.device),
-                         _torch_group_keys(torch.optim.Adagrad, lr=lr, lr_decay=lr_decay, weight_decay=weight_decay, eps=eps),
-                         sweep_period, group, clip_grad_norm)
-
-    def _torch_groups(self):
-        return dict(self.defaults)
+                         dict(lr=lr, lr_decay=lr_decay, weight_decay=weight_decay, eps=eps), sweep_period, group,
+                         clip_grad_norm)
 
 
 class FusedLazyRMSprop(FusedLazyOptimizer):
@@ -698,11 +679,16 @@ class FusedLazyRMSprop(FusedLazyOptimizer):
     def __init__(self, engine, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, sweep_period=None, group=None,
                  clip_grad_norm=None):
         super().__init__(engine, RMSpropHyper(lr, alpha, eps, weight_decay, device=engine.device),
-                         _torch_group_keys(torch.optim.RMSprop, lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay),
-                         sweep_period, group, clip_grad_norm)
-
-    def _torch_groups(self):
-        return dict(self.defaults)
+                         dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay), sweep_period, group, clip_grad_norm)
 
 
-FUSED_LAZY = {"adam": FusedLazyAdam, "sgd": FusedLazySGD, "adagrad": FusedLazyAdagrad, "rmsprop": FusedLazyRMSprop}
+# The one description of each learner on the host side, indexed by fr_adam.learner.
+LEARNERS = {rec.id: rec for rec in (
+    Learner(LEARNER_ADAM, "adam", torch.optim.Adam, FusedLazyAdam, "exp_avg", "exp_avg_sq", entry_always=True,
+            group_extra=dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False,
+                             fused=None)),
+    Learner(LEARNER_SGD, "sgd", torch.optim.SGD, FusedLazySGD, None),
+    Learner(LEARNER_ADAGRAD, "adagrad", torch.optim.Adagrad, FusedLazyAdagrad, "sum", state_from_construction=True),
+    Learner(LEARNER_RMSPROP, "rmsprop", torch.optim.RMSprop, FusedLazyRMSprop, "square_avg", state_at_first_step=True),
+)}
+FUSED_LAZY = {rec.name: rec.fused_cls for rec in LEARNERS.values()}      # by `learner` config value (trainer.py)
