@@ -21,37 +21,26 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mt19937.hpp"
 
 namespace {
+
+using fr::MT_H;
+using fr::MT_M;
+using fr::MT_N;
 
 struct Mt {
     uint32_t* key;
     int pos;
-    uint32_t tw[624];                        // the tempered outputs of the current 624 words (temper(key[k]) for all k)
+    uint32_t tw[MT_N];                       // the tempered outputs of the current 624 words (temper(key[k]) for all k)
     inline void temper_block() {
-        for (int k = 0; k < 624; ++k) {      // independent per word: the compiler vectorises it
-            uint32_t y = key[k];
-            y ^= y >> 11;
-            y ^= (y << 7) & 0x9d2c5680u;
-            y ^= (y << 15) & 0xefc60000u;
-            y ^= y >> 18;
-            tw[k] = y;
-        }
+        for (int k = 0; k < MT_N; ++k) tw[k] = fr::mt_temper(key[k]);      // independent per word: the compiler vectorises it
     }
-    inline void gen() {
-        constexpr uint32_t UPPER = 0x80000000u, LOWER = 0x7fffffffu, A = 0x9908b0dfu;
+    inline void gen() {                      // mt19937_gen in place: word k is overwritten once nothing behind it reads it
         int kk;
-        uint32_t y;
-        for (kk = 0; kk < 624 - 397; ++kk) {
-            y = (key[kk] & UPPER) | (key[kk + 1] & LOWER);
-            key[kk] = key[kk + 397] ^ (y >> 1) ^ ((0u - (y & 1u)) & A);
-        }
-        for (; kk < 623; ++kk) {
-            y = (key[kk] & UPPER) | (key[kk + 1] & LOWER);
-            key[kk] = key[kk + (397 - 624)] ^ (y >> 1) ^ ((0u - (y & 1u)) & A);
-        }
-        y = (key[623] & UPPER) | (key[0] & LOWER);
-        key[623] = key[396] ^ (y >> 1) ^ ((0u - (y & 1u)) & A);
+        for (kk = 0; kk < MT_H; ++kk) key[kk] = key[kk + MT_M] ^ fr::mt_mix(key[kk], key[kk + 1]);
+        for (; kk < MT_N - 1; ++kk) key[kk] = key[kk - MT_H] ^ fr::mt_mix(key[kk], key[kk + 1]);
+        key[MT_N - 1] = key[MT_M - 1] ^ fr::mt_mix(key[MT_N - 1], key[0]);
         pos = 0;
         temper_block();
     }
@@ -67,13 +56,12 @@ inline int64_t perm_first(Mt& mt, int64_t n, std::vector<uint32_t>& jv) {
     uint32_t* __restrict__ j = jv.data();
     uint32_t i = (uint32_t)(n - 1);
     while (i >= 1) {
-        uint32_t mask = i;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+        const uint32_t mask = fr::bounded_mask(i);
         const uint32_t lo = (mask >> 1) + 1;                       // i in [lo, mask]: this mask
         while (i >= lo) {
-            if (mt.pos == 624) mt.gen();
+            if (mt.pos == MT_N) mt.gen();
             const uint32_t* w = mt.tw + mt.pos;
-            const int avail = 624 - mt.pos;
+            const int avail = MT_N - mt.pos;
             int t = 0;
             for (; t < avail && i >= lo; ++t) {
                 const uint32_t v = w[t] & mask;
@@ -112,12 +100,12 @@ extern "C" int fr_focf_compose_epoch(uint32_t* state, const int64_t* item_unique
                                      int64_t* batch_end_out, int64_t max_batches, int64_t* n_batches_out) {
     FR_CHECK_ARG(state && item_uniques && indptr && picks_out && batch_end_out && n_batches_out && step >= 1 && n_uniq >= 1,
                  "fr_focf_compose_epoch: bad argument");
-    FR_CHECK_ARG(state[624] <= 624, "fr_focf_compose_epoch: generator position %u", state[624]);
-    uint32_t key[624];
+    FR_CHECK_ARG(state[MT_N] <= MT_N, "fr_focf_compose_epoch: generator position %u", state[MT_N]);
+    uint32_t key[MT_N];
     memcpy(key, state, sizeof(key));
     Mt mt;
     mt.key = key;
-    mt.pos = (int)state[624];
+    mt.pos = (int)state[MT_N];
     mt.temper_block();
     std::vector<int64_t> cands;
     std::vector<uint32_t> j;
@@ -138,7 +126,7 @@ extern "C" int fr_focf_compose_epoch(uint32_t* state, const int64_t* item_unique
         pr += step;
     }
     memcpy(state, key, sizeof(key));
-    state[624] = (uint32_t)mt.pos;
+    state[MT_N] = (uint32_t)mt.pos;
     *n_batches_out = n_batches;
     return FR_OK;
 }

@@ -26,23 +26,11 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mt19937.hpp"
 
 namespace fr {
 
-static constexpr int RP_MT_N = 624, RP_MT_M = 397, RP_MT_THREADS = 256;
-
-__device__ __forceinline__ uint32_t rp_mix(uint32_t a, uint32_t b) {
-    const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
-    return (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-}
-
-__device__ __forceinline__ uint32_t rp_temper(uint32_t y) {
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-}
+static constexpr int RP_MT_THREADS = 256;
 
 // kernel 1: the generator's next n_draws words, UNTEMPERED, in draw order; the state (key[624], pos) is left where the draws
 // put it.  One workgroup of four waves (one per SIMD of a CU): a block of 624 words is three barrier-separated phases --
@@ -51,15 +39,14 @@ __device__ __forceinline__ uint32_t rp_temper(uint32_t y) {
 // (tempering, the modulo, the atomics) is left to the wide kernels behind it.
 __global__ __launch_bounds__(RP_MT_THREADS) void randperm_words_kernel(uint32_t* __restrict__ state, uint32_t* __restrict__ raw,
                                                                        long long n_draws) {
-    __shared__ uint32_t buf[2][RP_MT_N];
+    __shared__ uint32_t buf[2][MT_N];
     const int tid = threadIdx.x;
     int cur = 0;
-    for (int k = tid; k < RP_MT_N; k += RP_MT_THREADS) buf[0][k] = state[k];
-    const int pos0 = (int)state[RP_MT_N];
+    for (int k = tid; k < MT_N; k += RP_MT_THREADS) buf[0][k] = state[k];
+    const int pos0 = (int)state[MT_N];
     __syncthreads();
-    constexpr int D = RP_MT_N - RP_MT_M;     // 227
     // what is left of the block the state holds
-    const int first = n_draws < (long long)(RP_MT_N - pos0) ? (int)n_draws : RP_MT_N - pos0;
+    const int first = n_draws < (long long)(MT_N - pos0) ? (int)n_draws : MT_N - pos0;
     for (int k = tid; k < first; k += RP_MT_THREADS) raw[k] = buf[0][pos0 + k];
     long long done = first;
     int pos = pos0 + first;
@@ -69,35 +56,35 @@ __global__ __launch_bounds__(RP_MT_THREADS) void randperm_words_kernel(uint32_t*
         uint32_t* nw = buf[cur ^ 1];
         const long long room = n_draws - done;        // words of this block that are draws: min(room, 624)
         uint32_t* dst = raw + done;
-        if (tid < D) {
-            const uint32_t v = o[tid + RP_MT_M] ^ rp_mix(o[tid], o[tid + 1]);
+        if (tid < MT_H) {
+            const uint32_t v = mt_next_word(o, nw, tid);
             nw[tid] = v;
             if (tid < room) dst[tid] = v;
         }
         __syncthreads();
-        if (tid < D) {
-            const uint32_t v = nw[tid] ^ rp_mix(o[tid + D], o[tid + D + 1]);
-            nw[tid + D] = v;
-            if (tid + D < room) dst[tid + D] = v;
+        if (tid < MT_H) {
+            const uint32_t v = mt_next_word(o, nw, tid + MT_H);
+            nw[tid + MT_H] = v;
+            if (tid + MT_H < room) dst[tid + MT_H] = v;
         }
         __syncthreads();
-        if (tid < RP_MT_N - 1 - 2 * D) {
-            const uint32_t v = nw[tid + D] ^ rp_mix(o[tid + 2 * D], o[tid + 2 * D + 1]);
-            nw[tid + 2 * D] = v;
-            if (tid + 2 * D < room) dst[tid + 2 * D] = v;
-        } else if (tid == RP_MT_N - 1 - 2 * D) {
-            const uint32_t v = nw[RP_MT_M - 1] ^ rp_mix(o[RP_MT_N - 1], nw[0]);
-            nw[RP_MT_N - 1] = v;
-            if (RP_MT_N - 1 < room) dst[RP_MT_N - 1] = v;
+        if (tid < MT_N - 1 - 2 * MT_H) {
+            const uint32_t v = mt_next_word(o, nw, tid + 2 * MT_H);
+            nw[tid + 2 * MT_H] = v;
+            if (tid + 2 * MT_H < room) dst[tid + 2 * MT_H] = v;
+        } else if (tid == MT_N - 1 - 2 * MT_H) {      // (one branch for all of [454, 624) compiles to other device code)
+            const uint32_t v = mt_next_word(o, nw, MT_N - 1);
+            nw[MT_N - 1] = v;
+            if (MT_N - 1 < room) dst[MT_N - 1] = v;
         }
         __syncthreads();
         cur ^= 1;
-        const int take = room < (long long)RP_MT_N ? (int)room : RP_MT_N;
+        const int take = room < (long long)MT_N ? (int)room : MT_N;
         done += take;
         pos = take;
     }
-    for (int k = tid; k < RP_MT_N; k += RP_MT_THREADS) state[k] = buf[cur][k];
-    if (tid == 0) state[RP_MT_N] = (uint32_t)pos;
+    for (int k = tid; k < MT_N; k += RP_MT_THREADS) state[k] = buf[cur][k];
+    if (tid == 0) state[MT_N] = (uint32_t)pos;
 }
 
 __global__ __launch_bounds__(256) void randperm_init_kernel(int32_t* __restrict__ parent, int32_t* __restrict__ head, long long n) {
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256) void randperm_link_kernel(int32_t* __restrict_
                                                             int32_t* __restrict__ head, int32_t* __restrict__ next, long long n) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n - 1) return;
-    const uint32_t x = rp_temper((uint32_t)t[i]);
+    const uint32_t x = mt_temper((uint32_t)t[i]);
     const int32_t p = (int32_t)(i + (long long)(x % (uint32_t)(n - i)));      // n - i <= n < 2^31
     t[i] = p;
     if (p == (int32_t)i) return;                       // a self swap moves nothing

@@ -51,11 +51,25 @@ class DeviceRandomState:
         w = np.concatenate([key, np.array([int(state[2])], dtype=np.uint32)]).view(np.int32)
         self.state.copy_(torch.from_numpy(w.copy()))
 
-    def _workspace(self, total: int) -> torch.Tensor:
-        need = _C.lib().fr_sample_negatives_workspace_bytes(total)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+    def _workspace(self, nbytes: int) -> torch.Tensor:
+        """The scratch buffer, grown to at least `nbytes` (the only place it grows)."""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _lists_workspace(self, positions: int) -> torch.Tensor:
+        """Room for the two collision lists of a call of `positions` values."""
+        return self._workspace(_C.lib().fr_sample_negatives_workspace_bytes(positions))
+
+    def _call_sequence(self, call_keys: torch.Tensor, call_counts: torch.Tensor):
+        """(keys, offsets, total, max_call, out) of a sequence of single-key calls: call c fills
+        out[offsets[c]:offsets[c + 1]] for key keys[c] (one host sync for the two sizes)."""
+        keys = call_keys.to(self.device, torch.int64).contiguous()
+        counts = call_counts.to(self.device, torch.int64)
+        offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        total, max_call = int(offsets[-1].item()), int(counts.max().item()) if counts.numel() else 0
+        return keys, offsets, total, max_call, torch.empty(total, dtype=torch.int64, device=self.device)
 
     def randint(self, low: int, high: int, n: int) -> torch.Tensor:
         """np.random.randint(low, high, n) as an int64 device tensor (range below 2**32 - 1)."""
@@ -72,7 +86,7 @@ class DeviceRandomState:
         n = key_ids.numel()
         out = torch.empty(n * num, dtype=torch.int64, device=self.device)
         if n:
-            ws = self._workspace(n * num)
+            ws = self._lists_workspace(n * num)
             _C.check(_C.lib().fr_sample_negatives(self.state.data_ptr(), low, high, key_ids.data_ptr(), n, num,
                                                   used_indptr.data_ptr(), used_items.data_ptr(), used_indptr.numel() - 1,
                                                   out.data_ptr(), _C.ptr(rounds_out), ws.data_ptr(), ws.numel(),
@@ -83,19 +97,11 @@ class DeviceRandomState:
                      used_indptr: torch.Tensor, used_items: torch.Tensor) -> torch.Tensor:
         """Consecutive single-key calls on this stream in one launch: call c draws call_counts[c] values for key
         call_keys[c] (each call finishes its re-draw rounds before the next one draws).  Returns the concatenation."""
-        call_keys = call_keys.to(self.device, torch.int64).contiguous()
-        counts = call_counts.to(self.device, torch.int64)
-        offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=self.device)
-        torch.cumsum(counts, 0, out=offsets[1:])
-        total, max_call = int(offsets[-1].item()), int(counts.max().item()) if counts.numel() else 0
-        out = torch.empty(total, dtype=torch.int64, device=self.device)
+        call_keys, offsets, total, max_call, out = self._call_sequence(call_keys, call_counts)
         if total:
             # (room for the speculative form of a long call sequence: csrc/sampler.hip, sample_calls_fast_kernel)
-            need = max(_C.lib().fr_sample_negatives_calls_workspace_bytes(total, max_call),
-                       _C.lib().fr_sample_negatives_workspace_bytes(max_call))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            ws = self._ws
+            ws = self._workspace(max(_C.lib().fr_sample_negatives_calls_workspace_bytes(total, max_call),
+                                     _C.lib().fr_sample_negatives_workspace_bytes(max_call)))
             _C.check(_C.lib().fr_sample_negatives_calls(self.state.data_ptr(), low, high, call_keys.data_ptr(),
                                                         offsets.data_ptr(), call_keys.numel(), max_call,
                                                         used_indptr.data_ptr(), used_items.data_ptr(),
@@ -112,7 +118,7 @@ class DeviceRandomState:
         n = key_ids.numel()
         out = torch.empty(n * num, dtype=torch.int64, device=self.device)
         if n:
-            ws = self._workspace(n * num) if used_indptr is not None else None
+            ws = self._lists_workspace(n * num) if used_indptr is not None else None
             _C.check(_C.lib().fr_sample_negatives_pop(self.state.data_ptr(), table, key_ids.data_ptr(), n, num,
                                                       _C.ptr(used_indptr), _C.ptr(used_items),
                                                       used_indptr.numel() - 1 if used_indptr is not None else 0,
@@ -125,14 +131,9 @@ class DeviceRandomState:
                          used_items: torch.Tensor) -> torch.Tensor:
         """`sample_calls` with popularity-biased draws (fr_sample_negatives_pop_calls): the calls one after the other in
         one launch, each finishing its re-draw rounds before the next one draws."""
-        call_keys = call_keys.to(self.device, torch.int64).contiguous()
-        counts = call_counts.to(self.device, torch.int64)
-        offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=self.device)
-        torch.cumsum(counts, 0, out=offsets[1:])
-        total, max_call = int(offsets[-1].item()), int(counts.max().item()) if counts.numel() else 0
-        out = torch.empty(total, dtype=torch.int64, device=self.device)
+        call_keys, offsets, total, max_call, out = self._call_sequence(call_keys, call_counts)
         if total:
-            ws = self._workspace(max_call)
+            ws = self._lists_workspace(max_call)
             _C.check(_C.lib().fr_sample_negatives_pop_calls(self.state.data_ptr(), table, call_keys.data_ptr(),
                                                             offsets.data_ptr(), call_keys.numel(), max_call,
                                                             used_indptr.data_ptr(), used_items.data_ptr(),
