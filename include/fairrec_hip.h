@@ -1476,6 +1476,79 @@ typedef struct fr_dyn_neg_mlp_args {
 FR_API int fr_dyn_neg_mlp_select(const fr_dyn_neg_mlp_args* a, int64_t* out, uint32_t* err_flag, void* stream);
 FR_API int fr_dyn_neg_mlp_scores(const fr_dyn_neg_mlp_args* a, float* scores, uint32_t* err_flag, void* stream);
 
+/* ---- sensitive-attribute leakage probe (csrc/probe.hip; fairrec/evaluator/leakage.py) -------------------------------------
+ * Up to FR_PROBE_MAX_HEADS attackers ("heads", one per sensitive attribute, no shared parameters) read the same rows of a
+ * user-embedding matrix X [U, D] (row stride ldx).  Head a has C_a = classes[a] classes and, with the shared hidden width H,
+ *     H > 0 :  z1 = W1 x + b1, h = relu(z1) (x < 0 ? 0 : x), z2 = W2 h + b2        W1 [H, D], W2 [C_a, H]
+ *     H == 0:  z2 = W x + b                                                         W  [C_a, D]
+ * its loss is the mean softmax cross-entropy over the batch by fr_softmax_ce's formulas (the maximum taken off first,
+ * p = __expf(z - mx) / se, term = __logf(se) - (z[y] - mx), dz2 = (p - onehot) / (float)B), relu' = (z1 > 0).
+ *
+ * Flat layout, shared by params, m, v and grad_out: [head 0][head 1]..., a head = [W1 | b1 | W2 | b2] row-major (H == 0:
+ * [W | b]); fr_probe_param_count floats in all.
+ *
+ * Rows: batch position b reads X row r = rows ? rows[b] : b and head a's label labels[a * ldl + r] (int64): a label table
+ * [n_heads, ldl] indexed like X, so a permutation slice needs no gathered copy.  A row index outside 0..U-1 sets
+ * FR_DEV_ERR_INDEX_RANGE in *err_flag and the row contributes nothing to any head; a label outside 0..C_a-1 sets it and the row
+ * contributes nothing to head a.  The divisor stays B.  No read goes out of bounds.
+ *
+ * Limits: 1 <= D <= 256; H == 0 or 1 <= H <= 256; 2 <= C_a <= 64; 1 <= n_heads <= 8 (FR_EUNSUPPORTED otherwise, as
+ * fr_probe_supported answers); 1 <= B <= 65536 (FR_EUNSUPPORTED); 1 <= U < 2^31, ldx >= D, ldl >= U (rows given) or >= B,
+ * B <= U when rows is NULL, step >= 1, Adam as the learner with weight_decay 0, a workspace of
+ * fr_probe_step_workspace_bytes, no null pointer but rows and grad_out (FR_EINVAL).  Every refusal comes before anything is
+ * launched or written, and fr_last_error names the argument.
+ *
+ * fr_probe_step: ONE optimiser step of all heads on one batch, in two launches whatever n_heads is.
+ *   launch 1  fr_probe_grid(B) workgroups: tiles = ceil(B / 32), tiles per workgroup tpw = ceil(tiles / 256), workgroups =
+ *             ceil(tiles / tpw); workgroup w walks tiles w tpw .. -- a function of B alone.  A tile of X is read once and
+ *             serves every head: forward, softmax, loss terms, dz2, dW2 = dz2^T h, db2, dh = dz2 W2, dz1 = dh (z1 > 0),
+ *             dW1 = dz1^T X, db1.  Every product is a chain of v_mfma_f32_32x32x2_f32, ascending from 0, two inner indices per
+ *             step (exact fp32 fma, the first index of a pair first): over the input columns in the forward, over the classes
+ *             in dh, over the 32 rows of the tile in the weight gradients (bias gradients: the 32 rows added ascending from 0).
+ *             Rows beyond B contribute exact zeros.  A tile's gradient is added to the workgroup's own slot of the workspace
+ *             (first tile: stored), each cell by the one lane that owns it: no float atomic.
+ *   launch 2  gradient = the slots added in workgroup order; grad_out (optional) receives it; Adam by fr_adam_dense's formulas
+ *             with the scalars of `step` on params / m / v: bit for bit fr_adam_dense on grad_out.  loss [1 + n_heads]:
+ *             loss[1 + a] = (head a's terms: per tile row slot over the workgroup's tiles, the 32 slots ascending, the
+ *             workgroups ascending) * (1 / (float)B); loss[0] = the heads' losses added in head order.
+ *   The bits of every output depend on the inputs alone, not on the device: two calls on equal inputs give equal bits.
+ * fr_probe_forward: launch 1's forward alone, logits [B, sum C_a] (head a's columns from sum_{a' < a} C_a'), the same bits the
+ *   step computes; nothing else is written.  The probe's own kernel, not fr_mlp_infer: one launch for all heads, one read of X.
+ * fr_probe_eval: the metric reduction over n held-out rows.  logits [n, sum C_a] (position b), labels / rows / U as above.
+ *   Per head: correct [n_heads] int64 = rows whose argmax (the lowest class among equal maxima) is the label; logloss
+ *   [n_heads] double = sum of log(se) - (z[y] - mx) in double; class_count [sum C_a] int64 = rows per label; probs
+ *   [n, sum C_a] float = the double softmax rounded once (a row with a bad index or label sets the flag and is counted
+ *   nowhere; its probabilities are still written).  Partials per 256 rows, added in block order: deterministic.
+ *   AUC: torch.sort of a class's probs column, then fr_auc_sorted. */
+#define FR_PROBE_MAX_HEADS   8
+#define FR_PROBE_MAX_WIDTH   256
+#define FR_PROBE_MAX_CLASSES 64
+#define FR_PROBE_MAX_BATCH   65536
+typedef struct fr_probe_args {
+    const float* X;
+    const int64_t* rows;      /* [B] or NULL */
+    const int64_t* labels;    /* [n_heads, ldl]; unused by fr_probe_forward */
+    int64_t U;
+    int64_t ldx;
+    int64_t ldl;
+    int64_t B;
+    int32_t D;
+    int32_t H;
+    int32_t n_heads;
+    int32_t classes[FR_PROBE_MAX_HEADS];
+} fr_probe_args;
+FR_API int fr_probe_supported(int32_t D, int32_t H, int32_t n_heads, const int32_t* classes);
+FR_API int64_t fr_probe_param_count(int32_t D, int32_t H, int32_t n_heads, const int32_t* classes);   /* 0: unsupported */
+FR_API int32_t fr_probe_grid(int64_t B);                                                            /* 0: unsupported */
+FR_API size_t fr_probe_step_workspace_bytes(int32_t D, int32_t H, int32_t n_heads, const int32_t* classes, int64_t B);
+FR_API int fr_probe_step(const fr_probe_args* a, float* params, float* m, float* v, const fr_adam* adam, int32_t step,
+                         float* loss, float* grad_out, void* ws, size_t ws_bytes, uint32_t* err_flag, void* stream);
+FR_API int fr_probe_forward(const fr_probe_args* a, const float* params, float* logits, uint32_t* err_flag, void* stream);
+FR_API size_t fr_probe_eval_workspace_bytes(int64_t n, int32_t n_heads, const int32_t* classes);
+FR_API int fr_probe_eval(const float* logits, const int64_t* labels, int64_t ldl, const int64_t* rows, int64_t U, int64_t n,
+                         int32_t n_heads, const int32_t* classes, int64_t* correct, double* logloss, int64_t* class_count,
+                         float* probs, void* ws, size_t ws_bytes, uint32_t* err_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

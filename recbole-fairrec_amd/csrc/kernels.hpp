@@ -12,7 +12,8 @@ enum KernelKind {
     K_BUCKET_ROWS, K_FOCF_SHARD_SCORE, K_FOCF_SHARD_GRADS, K_LINEAR_FWD,
     K_LINEAR_BWD_INPUT, K_LINEAR_BWD_WEIGHT, K_NFCF_LOSS, K_BN_FWD, K_BN_BWD, K_ROWDOT, K_BPR, K_SPMM, K_ROW_GATHER, K_SAMPLE_NEG, K_FOCF_STEP, K_FOCF_LPT, K_FOCF_STAGE, K_DYN_NEG_SELECT, K_DYN_NEG_DOT_SELECT,
     K_RECOMMEND, K_TOPK_ROWS, K_MLP_INFER, K_PAIR_MLP, K_DYN_NEG_MLP, K_REC_CELLS,
-    K_REC_MEANRANK, K_ROWS_NORMALIZE, K_DF_CELLS, K_BOOTSTRAP, K_COUNT
+    K_REC_MEANRANK, K_ROWS_NORMALIZE, K_DF_CELLS, K_BOOTSTRAP,
+    K_PROBE_STEP, K_PROBE_APPLY, K_PROBE_EVAL, K_COUNT
 };
 bool prof_on();
 // algorithmic work of a launch of `kind` (FLOP of a dense product, bytes of an SpMM), summed while the profiler is on

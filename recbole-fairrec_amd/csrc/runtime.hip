@@ -34,7 +34,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "sample_negatives_kernel", "focf_step_kernel", "focf_lpt_kernel", "focf_stage_kernel", "dyn_neg_select_kernel", "dyn_neg_dot_select_kernel",
     "recommend_kernel", "topk_rows_kernel", "mlp_infer_kernel", "pair_mlp_kernel", "dyn_neg_mlp_kernel",
     "recommend_cells_kernel", "recommend_meanrank_kernel", "rows_l2_normalize_kernel", "df_cells_kernel",
-    "bootstrap_chunk_kernel"};
+    "bootstrap_chunk_kernel", "probe_step_kernel", "probe_apply_kernel", "probe_eval_kernel"};
 
 struct ProfState {
     bool on = false;

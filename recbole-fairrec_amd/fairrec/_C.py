@@ -29,6 +29,8 @@ PAIR_MLP_MAX_LINEARS = 6   # FR_PAIR_MLP_MAX_LINEARS
 PAIR_MLP_MAX_WIDTH = 256   # FR_PAIR_MLP_MAX_WIDTH
 BOOTSTRAP_MAX_COLS = 64    # FR_BOOTSTRAP_MAX_COLS, FR_USER_TERMS_MAX_COLS
 BOOTSTRAP_MAX_REP = 65536  # FR_BOOTSTRAP_MAX_REP
+PROBE_MAX_HEADS = 8        # FR_PROBE_MAX_HEADS
+PROBE_MAX_BATCH = 65536    # FR_PROBE_MAX_BATCH
 
 FOCF_OBJECTIVES = {"none": 0, "value": 1, "absolute": 2, "under": 3, "over": 4, "nonparity": 5}
 
@@ -98,6 +100,11 @@ class FrDynNegMlpArgs(Structure):   # include/fairrec_hip.h: fr_dyn_neg_mlp_args
                 ("cand", c_void_p), ("ldp", c_int64), ("ldw1", c_int64), ("n", c_int64),
                 ("n_out", c_int32 * (PAIR_MLP_MAX_LINEARS - 1)), ("n1", c_int32), ("n_linears", c_int32), ("act", c_int32),
                 ("num", c_int32), ("M", c_int32)]
+
+
+class FrProbeArgs(Structure):       # include/fairrec_hip.h: fr_probe_args
+    _fields_ = [("X", c_void_p), ("rows", c_void_p), ("labels", c_void_p), ("U", c_int64), ("ldx", c_int64), ("ldl", c_int64),
+                ("B", c_int64), ("D", c_int32), ("H", c_int32), ("n_heads", c_int32), ("classes", c_int32 * PROBE_MAX_HEADS)]
 
 
 class FairrecError(RuntimeError):
@@ -369,6 +376,16 @@ _PROTOS = {
     "fr_prof_read_work": (c_int, [c_int, POINTER(c_double)]),
     "fr_adam_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(FrAdam), c_int32,
                               c_void_p]),
+    "fr_probe_supported": (c_int, [c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "fr_probe_param_count": (c_int64, [c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "fr_probe_grid": (c_int32, [c_int64]),
+    "fr_probe_step_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, POINTER(c_int32), c_int64]),
+    "fr_probe_step": (c_int, [POINTER(FrProbeArgs), c_void_p, c_void_p, c_void_p, POINTER(FrAdam), c_int32, c_void_p, c_void_p,
+                              c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fr_probe_forward": (c_int, [POINTER(FrProbeArgs), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fr_probe_eval_workspace_bytes": (c_size_t, [c_int64, c_int32, POINTER(c_int32)]),
+    "fr_probe_eval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, POINTER(c_int32), c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -487,6 +487,8 @@ class Trainer(AbstractTrainer):
         (user, item, rating) batches the RMSE / MAE of `model.predict * max_rating` against RATING_FIELD."""
         if not eval_data:
             return None
+        if not hasattr(self.model, 'get_sst_embed'):
+            leakage_results(self.config, self.model, eval_data, None)      # leakage_probe unset: nothing; True: the ValueError
         from ..data.dataloader import FullSortEvalDataLoader, LabeledEvalDataLoader, NegSampleEvalDataLoader
         if isinstance(eval_data, (FullSortEvalDataLoader, NegSampleEvalDataLoader)):
             self._load_for_eval(load_best_model, model_file)
@@ -512,6 +514,28 @@ class Trainer(AbstractTrainer):
             ae += err.abs().sum()
             n += err.numel()
         return OrderedDict(rmse=float((se / max(n, 1)).sqrt().item()), mae=float((ae / max(n, 1)).item()))
+
+
+def leakage_results(config, model, eval_data, sst_list):
+    """`leakage_probe: True`: the leakage keys (fairrec/evaluator/leakage.py) of a freshly trained attacker on
+    `model.get_sst_embed(user_features, sst_list)`, for the attributes that call stores; {} with the key unset.  The model's
+    buffers are put back afterwards (the dict-held filter MLPs take a BatchNorm batch from every forward pass, SURVEY.md
+    App. B-3), so that an evaluation after the probe reads what it would have read without it."""
+    from ..evaluator.leakage import probe_enabled, probe_leakage, probe_settings
+    if not probe_enabled(config):
+        return {}
+    probe_settings(config)                 # a bad key is refused before any device work
+    if not hasattr(model, 'get_sst_embed'):
+        raise ValueError(f"leakage_probe: {type(model).__name__} has no get_sst_embed; probe its user matrix with "
+                         "fairrec.evaluator.leakage.probe_leakage(embedding, labels, config)")
+    modules = [model] + [m for m in (getattr(model, 'filter_layer', None) or {}).values() if isinstance(m, torch.nn.Module)]
+    kept = [(b, b.clone()) for mod in modules for b in mod.buffers()]
+    try:
+        stored = model.get_sst_embed(eval_data.dataset.get_user_feature()[1:], sst_list)
+    finally:
+        for b, old in kept:
+            b.copy_(old)
+    return probe_leakage(stored.pop('embedding'), stored, config)
 
 
 class PFCNTrainer(Trainer):
@@ -626,6 +650,9 @@ class PFCNTrainer(Trainer):
             name = '{}_embed-{}.pth'.format(self.config['model'], self.config['filter_mode'])
             torch.save(self.model.get_sst_embed(user_features), os.path.join(self.checkpoint_dir, name))
 
+    def _add_leakage(self, result, eval_data, sst_list):
+        result.update(leakage_results(self.config, self.model, eval_data, sst_list))
+
     def _subsets(self):
         import itertools
         attrs = self.config['sst_attr_list']
@@ -661,9 +688,12 @@ class PFCNTrainer(Trainer):
             final = {}
             if self.filter_mode != 'none':
                 for sub in self._subsets():
-                    final['{}-{}'.format(self.config['filter_mode'] or self.filter_mode, sub)] = run(eval_data, (sub,))
+                    key = '{}-{}'.format(self.config['filter_mode'] or self.filter_mode, sub)
+                    final[key] = run(eval_data, (sub,))
+                    self._add_leakage(final[key], eval_data, sub)      # after the subset's own evaluation
             else:
                 final[self.config['filter_mode']] = run(eval_data)
+                self._add_leakage(final[self.config['filter_mode']], eval_data, None)
             return final
         raise NotImplementedError("evaluation of the filtered models needs an evaluation loader "
                                   "(FullSortEvalDataLoader / NegSampleEvalDataLoader / LabeledEvalDataLoader)")
@@ -814,6 +844,8 @@ class FairGoTrainer(PFCNTrainer):
         for stage, path in stages:
             self.model.train_stage = stage
             for key, value in Trainer.evaluate(self, eval_data, True, path, show_progress).items():
+                result[f'{stage}-{key}'] = value
+            for key, value in leakage_results(self.config, self.model, eval_data, list(self.mask_label.values())).items():
                 result[f'{stage}-{key}'] = value
         return result
 
