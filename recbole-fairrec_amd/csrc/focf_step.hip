@@ -1011,9 +1011,9 @@ __device__ __forceinline__ void focf_fair_single(int objective, float fair_weigh
     } else if (objective == FR_FOCF_ABSOLUTE) {
         d = fabsf(P - T); q = (P > T) ? 1.f : (P < T ? -1.f : 0.f);
     } else if (objective == FR_FOCF_UNDER) {
-        d = (T - P > 0.f) ? T - P : 0.f; q = (T - P > 0.f) ? -1.f : 0.f;
+        d = (T - P > 0.f) ? T - P : 0.f; q = (T - P >= 0.f) ? -1.f : 0.f;
     } else {
-        d = (P - T > 0.f) ? P - T : 0.f; q = (P - T > 0.f) ? 1.f : 0.f;
+        d = (P - T > 0.f) ? P - T : 0.f; q = (P - T >= 0.f) ? 1.f : 0.f;
     }
     const float delta = in0 ? d - 0.f : 0.f - d;
     const float x = fabsf(delta);

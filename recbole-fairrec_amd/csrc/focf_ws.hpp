@@ -169,10 +169,10 @@ __device__ __forceinline__ void focf_objective(int objective, float P0, float T0
         q1 = (P1 > T1) ? 1.f : (P1 < T1 ? -1.f : 0.f);
     } else if (objective == FR_FOCF_UNDER) {
         d0 = (T0 - P0 > 0.f) ? T0 - P0 : 0.f; d1 = (T1 - P1 > 0.f) ? T1 - P1 : 0.f;
-        q0 = (T0 - P0 > 0.f) ? -1.f : 0.f;    q1 = (T1 - P1 > 0.f) ? -1.f : 0.f;
+        q0 = (T0 - P0 >= 0.f) ? -1.f : 0.f;   q1 = (T1 - P1 >= 0.f) ? -1.f : 0.f;   // torch.clamp passes the gradient at x == min
     } else {  // over
         d0 = (P0 - T0 > 0.f) ? P0 - T0 : 0.f; d1 = (P1 - T1 > 0.f) ? P1 - T1 : 0.f;
-        q0 = (P0 - T0 > 0.f) ? 1.f : 0.f;     q1 = (P1 - T1 > 0.f) ? 1.f : 0.f;
+        q0 = (P0 - T0 >= 0.f) ? 1.f : 0.f;    q1 = (P1 - T1 >= 0.f) ? 1.f : 0.f;
     }
 }
 
