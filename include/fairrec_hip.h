@@ -1161,7 +1161,47 @@ FR_API int fr_df_cells(const int64_t* perm, const int64_t* item_start, int64_t n
  *   (FR_USER_TERMS_MAX_COLS).  rec_topk int32 [n_users][k + 1] as fr_topk_metrics.  A zero-positive row: Recall NaN, NDCG and MAP 0.
  * fr_gauc_user_terms: out double [n_users][2] = (auc_u * pos_len, pos_len) of a kept user, (0, 0) of a dropped one, from the
  *   `rec.meanrank` triples of fr_gauc_grouped and the device function it uses.
- *   Both: 1 <= n_users < 2^31; FR_EINVAL (null pointer, size or column out of range) before anything is launched or written. */
+ *   Both: 1 <= n_users < 2^31; FR_EINVAL (null pointer, size or column out of range) before anything is launched or written.
+ *
+ * fr_bootstrap_fair_metrics: the fairness metrics (fr_group_sums + fr_fair_metrics_from_stats, and NonParity's group means) in
+ *   every replicate of the same bootstrap, resampling USERS: replicate b is the metric of the multiset in which member j occurs
+ *   w(unit[j], b) times, w as above with r = unit[j].  The unit is the user's row in the evaluation, so a user weighs the same
+ *   here, in fr_bootstrap_group_sums over the users, and under every attribute.  unit int64 per member, in [0, 2^31) (the Philox
+ *   counter takes its low 32 bits).
+ *   Members and items as in fr_group_sums: positions j in [item_start[k], item_start[k+1]) are the members of item k, member
+ *   perm[j] (perm int64 [n_members], NULL = identity; item_start int64 [n_items + 1] on the device); group int32, value float,
+ *   wtrue float (NULL: every wtrue is 0) and unit are indexed by member.  A member whose group index is outside [0, n_groups)
+ *   is counted in no cell and no total.  perm is clamped into [0, n_members), item_start into [0, n_members]: a malformed table
+ *   gives unspecified values and no access outside the arrays.
+ *   Per replicate b, item k and group g the cell is S = sum w * value, C = sum w, T = sum w * wtrue.  Item k is PRESENT in b when
+ *   its sum over g of C is > 0; K_b = the number of present items.  `want` selects what is computed beyond K_b and the totals:
+ *     FR_FAIR_WANT_VALUE (n_groups must be 2): out_terms[0..3][b] = the sums over the present items of the Value, Absolute, Under
+ *       and Over terms of fr_fair_metrics_from_stats (n = C + 1e-5, p = S / n, r = T / n);
+ *     FR_FAIR_WANT_DF: out_terms[4][b] = the sum over the present items of the DifferentialFairness epsilon of that entry with
+ *       the table entries (float)((S + 1.0 / K_b) / (C + 1.0)): alpha = 1 / K_b, the replicate's own number of items, not
+ *       1 / n_items; float32 logf, a NaN pair left out.
+ *   A term not selected is written as 0.
+ *     out_terms        double [5][n_rep]         sums, NOT divided: the caller divides by K_b (K_b = 0: 0 / 0 = NaN)
+ *     out_items        int64  [n_rep]            K_b
+ *     out_group_sum    double [n_groups][n_rep]  sum over ALL members of group g of w * value   (NonParity: the group mean is
+ *     out_group_weight int64  [n_groups][n_rep]  sum over them of w, exact                       their quotient)
+ *   SUMMATION ORDER (a contract): the items are cut into `chunks` runs of consecutive whole items, item k in chunk
+ *   floor(item_start[k] / L), L = ceil(n_members / chunks), chunks = min(1024, n_items, max(1, 2^20 / n_rep),
+ *   ceil(n_members / 64)).  One wave takes one chunk and 256 replicates; a lane owns four replicates, one Philox call per (member,
+ *   lane) gives its four weights, nothing is stored per member or per item.  The lane walks the chunk's members in ascending
+ *   position, adds w * value (exact in double) into the member's cell and group total, closes an item after its last member
+ *   and adds the item's terms to its running sums in ascending item order.  K_b comes from a first walk, which also gives the
+ *   value-type sums and the totals; the DifferentialFairness sums come from a second walk that starts from 1 / K_b.  The
+ *   per-chunk partials are added in ascending chunk order from 0.  An item is never split: the longest item bounds the chain.
+ *   No floating-point atomics: the same input gives the same bytes on every call.
+ *   Workspace: fr_bootstrap_fair_metrics_workspace_bytes = chunks * n_rep * (2 * n_groups + 6) * 8: bounded by the chunks, never
+ *   by members * n_rep or items * n_rep.
+ *   Limits: 1 <= n_members <= 2^28, 1 <= n_items < 2^31, 1 <= n_groups <= 8, 1 <= n_rep <= 65536 (FR_BOOTSTRAP_MAX_REP), want a
+ *   combination of the two bits (0: K_b and the totals only).  FR_EINVAL before anything is launched or written: a null pointer
+ *   other than perm / wtrue, a size out of range, FR_FAIR_WANT_VALUE with n_groups != 2, ws below the _workspace_bytes value,
+ *   which is 0 for arguments out of range. */
+#define FR_FAIR_WANT_VALUE 1
+#define FR_FAIR_WANT_DF 2
 #define FR_BOOTSTRAP_MAX_COLS 64
 #define FR_BOOTSTRAP_MAX_REP 65536
 #define FR_USER_TERMS_MAX_COLS 64
@@ -1172,6 +1212,12 @@ FR_API int fr_bootstrap_group_sums(const double* values, int64_t n_rows, int32_t
 FR_API int fr_topk_user_terms(const int32_t* rec_topk, int64_t n_users, int32_t k, const int32_t* metric, const int32_t* cut,
                               int32_t n_cols, double* out, void* stream);
 FR_API int fr_gauc_user_terms(const int64_t* meanrank, int64_t n_users, double* out, void* stream);
+FR_API size_t fr_bootstrap_fair_metrics_workspace_bytes(int64_t n_members, int64_t n_items, int32_t n_groups, int32_t n_rep);
+FR_API int fr_bootstrap_fair_metrics(const int64_t* perm, const int64_t* item_start, int64_t n_items, int64_t n_members,
+                                     const int32_t* group, const float* value, const float* wtrue, const int64_t* unit,
+                                     int32_t n_groups, int32_t n_rep, uint64_t seed, int32_t want, double* out_terms,
+                                     int64_t* out_items, double* out_group_sum, int64_t* out_group_weight, void* ws,
+                                     size_t ws_bytes, void* stream);
 
 /* ---- built-in profiler -------------------------------------------------------------------------------
  * When enabled every kernel launch of this library is bracketed by a hipEvent pair recorded on the

@@ -29,6 +29,7 @@ PAIR_MLP_MAX_LINEARS = 6   # FR_PAIR_MLP_MAX_LINEARS
 PAIR_MLP_MAX_WIDTH = 256   # FR_PAIR_MLP_MAX_WIDTH
 BOOTSTRAP_MAX_COLS = 64    # FR_BOOTSTRAP_MAX_COLS, FR_USER_TERMS_MAX_COLS
 BOOTSTRAP_MAX_REP = 65536  # FR_BOOTSTRAP_MAX_REP
+FAIR_WANT_VALUE, FAIR_WANT_DF = 1, 2   # FR_FAIR_WANT_VALUE, FR_FAIR_WANT_DF
 PROBE_MAX_HEADS = 8        # FR_PROBE_MAX_HEADS
 PROBE_MAX_BATCH = 65536    # FR_PROBE_MAX_BATCH
 
@@ -215,6 +216,10 @@ _PROTOS = {
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_topk_user_terms": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p, c_void_p]),
     "fr_gauc_user_terms": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "fr_bootstrap_fair_metrics_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "fr_bootstrap_fair_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                          c_int32, c_uint64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
     "fr_value_metrics_workspace_bytes": (c_size_t, [c_int64]),
     "fr_value_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_auc_sorted_workspace_bytes": (c_size_t, [c_int64]),

@@ -15,6 +15,10 @@ With `utility_by_group` or `exposure_by_group` set, every ranking branch also ke
 key selects, one value per row of `rec.topk` -- and (`utility_by_group`) the labeled branch `data.<attr>` per row; without the
 keys the collected keys are what they were.
 
+With `fairness_bootstrap` set, every ranking branch also keeps `data.positive_user`: per positive pair the row of its user in
+`rec.topk` over the whole evaluation (the batch's row plus the rows of the batches before), the unit the bootstrap resamples;
+without the key the collected keys are what they were.
+
 `full_sort_eval: fused` feeds `eval_batch_collect_fused` the model's factors instead of the matrix (same keys, same values).
 
 The three ranking branches differ in how they rank; each ends in `_finish_ranking` (the hit flags and the keys every branch adds).
@@ -55,6 +59,8 @@ class Collector:
         self.user_attrs = list(dict.fromkeys(self.utility + self.exposure))
         self.full = 'full' in (config['eval_args'] or {}).get('mode', 'full')
         self.meanrank = 'gauc' in [m.lower() for m in (config['metrics'] or [])]
+        self.positive_user = bool(config['fairness_bootstrap'])
+        self._rows = 0        # rows of `rec.topk` the batches before this one added (get_data_struct resets it)
         self._parts: Dict[str, List[torch.Tensor]] = {}
         self._data: Dict[str, object] = {}
         self._err = None      # device error word of the fused path's kernels (eval_batch_collect_fused)
@@ -134,7 +140,7 @@ class Collector:
             seg = torch.arange(U + 1, device=scores.device, dtype=torch.int64) * n_items
             self._meanrank(seg, None, scores.to(torch.float32).contiguous().view(-1), keys, n_items)
         self._finish_ranking(topk_idx, keys, scores[positive_u, positive_i], positive_i, interaction, positive_u, K, n_items, U,
-                             scores.device)
+                             scores.device, positive_u)
         self._add_user_attrs(interaction, scores.device)
 
     def eval_batch_collect_fused(self, factors, interaction, hist_indptr: torch.Tensor, hist_items: torch.Tensor,
@@ -175,7 +181,7 @@ class Collector:
                                                          hist_items=hist_items, **kw))
         cells = recommend_cells(X, W, positive_u, positive_i, self._err, user_bias=ub, hist_indptr=hist_indptr, hist_items=hist_items,
                                 **kw)
-        self._finish_ranking(topk_idx, keys, cells, positive_i, interaction, positive_u, K, n_items, U, dev)
+        self._finish_ranking(topk_idx, keys, cells, positive_i, interaction, positive_u, K, n_items, U, dev, positive_u)
         self._add_user_attrs(interaction, dev)
 
     def check_device_errors(self):
@@ -228,7 +234,8 @@ class Collector:
                 self._meanrank(seg, items, sc, pos_keys, n_items)
         else:
             topk_idx, lookup = self._rank_candidates_general(origin_scores, row_idx, items, pos_keys, n_items, U, K)
-        self._finish_ranking(topk_idx, pos_keys, lookup(positive_u, positive_i), positive_i, interaction, slice(P), K, n_items, U, dev)
+        self._finish_ranking(topk_idx, pos_keys, lookup(positive_u, positive_i), positive_i, interaction, slice(P), K, n_items, U, dev,
+                             positive_u)
         neg_items = items[P:2 * P]
         self._add('rec.negative_score', lookup(positive_u[:neg_items.numel()], neg_items))
         self._add('data.negative_i', neg_items)
@@ -306,10 +313,11 @@ class Collector:
         out[:, 2] = torch.bincount(r[pos], minlength=U)
         return out
 
-    def _finish_ranking(self, topk_idx, pos_keys, positive_score, positive_i, interaction, sst_rows, K, n_items, U, dev):
+    def _finish_ranking(self, topk_idx, pos_keys, positive_score, positive_i, interaction, sst_rows, K, n_items, U, dev, positive_u):
         """Where a ranking batch is finished, whichever branch ranked it: the hit flags of the lists against the SORTED positive keys
         row * n_items + item (fr_eval_hits), then `rec.topk`, `rec.items`, `rec.positive_score`, `data.positive_i` and `data.<sst>`
-        (rows `sst_rows` of the batch's columns: the positives' user rows, or the reference's [:P] in the candidates branch)."""
+        (rows `sst_rows` of the batch's columns: the positives' user rows, or the reference's [:P] in the candidates branch).
+        `fairness_bootstrap`: and `data.positive_user` = positive_u (the positives' rows in the batch) plus the rows before it."""
         rec = torch.empty((U, K + 1), dtype=torch.int32, device=dev)
         _C.call('eval_hits', topk_idx.data_ptr(), U, K, n_items, pos_keys.data_ptr(), pos_keys.numel(), rec.data_ptr())
         self._add('rec.topk', rec)
@@ -319,9 +327,13 @@ class Collector:
         for s in self.sst:
             if s in interaction:
                 self._add('data.' + s, interaction[s].to(dev)[sst_rows])
+        if self.positive_user:
+            self._add('data.positive_user', positive_u + self._rows)
+            self._rows += U
 
     def get_data_struct(self) -> Dict[str, torch.Tensor]:
         out = {k: torch.cat(v, dim=0) for k, v in self._parts.items()}
         out.update(self._data)
         self._parts = {}
+        self._rows = 0
         return out

@@ -25,6 +25,11 @@ users, '<m> ci_low | ci_high of <A>=<value>' and '<m> gap ci_low | ci_high of se
 gauc: topk_user_terms / gauc_user_terms once per evaluation, bootstrap_group_sums per attribute (csrc/bootstrap.hip:
 fr_bootstrap_group_sums, the U x B weights made in registers and never stored), bootstrap_intervals on the host.
 
+`fairness_bootstrap: B` (off by default) adds percentile intervals of the fairness metrics from B replicates of the same Poisson
+bootstrap over users, '<metric> ci_low | ci_high of sensitive attribute <A>': bootstrap_fairness (csrc/bootstrap_fair.hip:
+fr_bootstrap_fair_metrics walks the item-sorted members once for all replicates; no weight and no per-replicate table is stored),
+bootstrap_intervals on the host.  Attributes and intersections with at most NARROW_GROUPS groups.
+
 `eval_args.mode: labeled` is evaluation by value: 'auc', 'logloss', 'mae', 'rmse' of `rec.score` (what `predict` returned)
 against `data.label` (LABEL_FIELD), every row of the evaluation set (fr_value_metrics, fr_auc_sorted).  'gauc' is a ranking
 metric: it reads `rec.meanrank` (fr_eval_meanrank_segments) in the full / uniN / popN modes.
@@ -63,12 +68,18 @@ def _group_sums(perm: Optional[torch.Tensor], seg_start, K, group, value, wtrue,
     return stats
 
 
+def _item_sort(items: torch.Tensor):
+    """the members sorted by item, stably: (perm, seg_start int64 [K + 1], K); item k's members are perm[seg_start[k] .. seg_start[k + 1])"""
+    keys, perm = torch.sort(items, stable=True)
+    K, seg_start = item_segments(keys)
+    return perm, seg_start, K
+
+
 def _item_sums(items: Optional[torch.Tensor], group, value, wtrue, G):
     """stats [K, G, 3] over the distinct items (items = None: one segment), and K"""
     if items is None:
         return _group_sums(None, torch.tensor([0, value.numel()], dtype=torch.int64, device=value.device), 1, group, value, wtrue, G), 1
-    keys, perm = torch.sort(items, stable=True)
-    K, seg_start = item_segments(keys)
+    perm, seg_start, K = _item_sort(items)
     return _group_sums(perm, seg_start, K, group, value, wtrue, G), K
 
 
@@ -132,16 +143,7 @@ def fairness_metrics(pos_score, pos_i, sst: Dict[str, torch.Tensor], neg_score=N
         if n == 0 and value_type:
             if G != 2:
                 raise ValueError('sensitive attribute must be binary')
-            P = pos_score.numel()
-            if mode != 'full' and neg_i is not None:
-                # the j-th negative is attributed to the group of the j-th positive's user (metrics.py:957-960)
-                m = min(neg_i.numel(), P)
-                items = torch.cat([pos_i, neg_i[:m]])
-                value = torch.cat([pos_score, neg_score[:m].to(torch.float32)])
-                group = torch.cat([gidx, gidx[:m]])
-                wtrue = torch.cat([torch.ones(P, device=value.device), torch.zeros(m, device=value.device)])
-            else:
-                items, value, group, wtrue = pos_i, pos_score, gidx, torch.ones(P, device=pos_score.device)
+            items, group, value, wtrue, _ = value_type_rows(pos_score, pos_i, gidx, None, neg_score, neg_i, mode)
             st, K = _item_sums(items, group.contiguous(), value.contiguous(), wtrue.contiguous(), 2)
             v = _from_stats(st, K, 2)
             for q, label in enumerate(("Value", "Absolute", "Underestimation", "Overestimation")):
@@ -451,6 +453,66 @@ def bootstrap_group_sums(values: torch.Tensor, group_index: torch.Tensor, n_grou
     return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=2)), weight
 
 
+FAIR_STATS = ("value", "absolute", "under", "over", "differential")     # the rows of fr_bootstrap_fair_metrics' out_terms
+
+
+def value_type_rows(pos_score, pos_i, gidx, unit, neg_score=None, neg_i=None, mode="full"):
+    """the rows the value-type metrics of `fairness_metrics` are taken over: (items, group, value, wtrue, unit).  Outside the
+    `full` mode the first min(len(neg), P) negatives follow the P positives with wtrue 0; negative j carries the group and the
+    resampling unit of positive j (metrics.py:957-960).  unit = None (the point estimate): None."""
+    P = pos_score.numel()
+    ones = torch.ones(P, dtype=torch.float32, device=pos_score.device)
+    if mode == 'full' or neg_i is None:
+        return pos_i, gidx, pos_score, ones, unit
+    m = min(neg_i.numel(), P)
+    return (torch.cat([pos_i, neg_i[:m]]), torch.cat([gidx, gidx[:m]]), torch.cat([pos_score, neg_score[:m].to(torch.float32)]),
+            torch.cat([ones, torch.zeros(m, dtype=torch.float32, device=ones.device)]),
+            None if unit is None else torch.cat([unit, unit[:m]]))
+
+
+def bootstrap_fairness(items, group, value, wtrue, unit, n_groups: int, n_rep: int, seed: int, value_type=False,
+                       differential=True, sort=None):
+    """The fairness metrics of the rows (items, group, value, wtrue) -- what `fairness_metrics` forms -- in every one of n_rep
+    replicates of a Poisson bootstrap over users: member j occurs w(unit[j], b) times in replicate b, w the weights of
+    `bootstrap_group_sums` (fairrec_hip.h), unit[j] = the global row of the member's user in the evaluation.  -> {name: float64
+    [n_rep] on the host}: 'nonparity' (|difference| of the two weighted group means, the population std for more groups; NaN when
+    a group has weight 0), with value_type (two groups) 'value', 'absolute', 'under', 'over', with differential 'differential'
+    (means over the K_b items present in the replicate, alpha = 1 / K_b; NaN when K_b = 0), and 'items' = K_b (int64).
+    One library call (fr_bootstrap_fair_metrics): no weight and no per-replicate table is stored.  `sort`: what `_item_sort(items)`
+    returned, when the caller has it.  1 <= n_groups <= NARROW_GROUPS."""
+    G, B = int(n_groups), int(n_rep)
+    M = items.numel()
+    if not 1 <= G <= NARROW_GROUPS:
+        raise ValueError(f'bootstrap_fairness: {G} groups; the device path takes 1..{NARROW_GROUPS}')
+    if not 1 <= B <= _C.BOOTSTRAP_MAX_REP:
+        raise ValueError(f'bootstrap_fairness: {B} replicates; 1..{_C.BOOTSTRAP_MAX_REP}')
+    if value_type and G != 2:
+        raise ValueError('sensitive attribute must be binary')
+    if M < 1 or any(t.numel() != M for t in (group, value, unit)) or (wtrue is not None and wtrue.numel() != M):
+        raise ValueError(f'bootstrap_fairness: {M} items need as many groups, values, units (and wtrue), and at least one')
+    dev = value.device
+    perm, seg_start, K = sort if sort is not None else _item_sort(items)
+    group = group.to(torch.int32).contiguous()
+    value = value.to(torch.float32).contiguous()
+    wtrue = None if wtrue is None else wtrue.to(torch.float32).contiguous()
+    unit = unit.to(torch.int64).contiguous()
+    terms = torch.empty((5, B), dtype=torch.float64, device=dev)
+    n_items = torch.empty(B, dtype=torch.int64, device=dev)
+    gsum = torch.empty((G, B), dtype=torch.float64, device=dev)
+    gweight = torch.empty((G, B), dtype=torch.int64, device=dev)
+    want = (_C.FAIR_WANT_VALUE if value_type else 0) | (_C.FAIR_WANT_DF if differential else 0)
+    _C.call('bootstrap_fair_metrics', perm.data_ptr(), seg_start.data_ptr(), K, M, group.data_ptr(), value.data_ptr(), _C.ptr(wtrue),
+            unit.data_ptr(), G, B, int(seed) & (2 ** 64 - 1), want, terms.data_ptr(), n_items.data_ptr(), gsum.data_ptr(),
+            gweight.data_ptr(), ws=(M, K, G, B), device=dev)
+    terms, n_items = terms.cpu().numpy(), n_items.cpu().numpy()
+    means = _ratio(gsum.cpu().numpy(), gweight.cpu().numpy())                       # [G, B], NaN where a group has weight 0
+    res = {'items': n_items, 'nonparity': np.abs(means[0] - means[1]) if G == 2 else means.std(axis=0)}
+    for q, name in enumerate(FAIR_STATS):
+        if (value_type and q < 4) or (differential and q == 4):
+            res[name] = _ratio(terms[q], n_items)
+    return res
+
+
 def bootstrap_intervals(stat, level: float, what: str = ''):
     """Percentile intervals of bootstrap replicates.  stat: float64 [G, B] on the host, the statistic of group g in replicate b,
     NaN (or infinite) = unusable.  -> (low [G], high [G], gap_low, gap_high, usable [G], gap_usable): per group
@@ -542,18 +604,27 @@ class Evaluator:
         if self.bootstrap and self.mode == 'labeled':
             raise ValueError("group_bootstrap needs eval_args.mode full / uniN / popN, not 'labeled': the bootstrap resamples "
                              "users, and the rows of the labeled mode are interactions")
+        self.fair_bootstrap, self.fair_bootstrap_level = self._bootstrap_keys(
+            config['fairness_bootstrap'], config['fairness_bootstrap_level'], 'fairness_bootstrap')
+        if self.fair_bootstrap and self.mode == 'labeled':
+            raise ValueError("fairness_bootstrap needs eval_args.mode full / uniN / popN, not 'labeled': the bootstrap resamples "
+                             "users, and the rows of the labeled mode are interactions")
+        if self.fair_bootstrap and not self.FAIR & set(self.metrics):
+            raise ValueError('fairness_bootstrap needs a fairness metric among `metrics`: the intervals belong to '
+                             f'{sorted(self.FAIR)}')
         self.seed = int(config['seed']) if config['seed'] is not None else 0
 
     @staticmethod
-    def _bootstrap_keys(n_rep, level):
-        """`group_bootstrap` (None / 0: off, else an integer B in 2..65536) and `group_bootstrap_level` (strictly inside 0..1)"""
+    def _bootstrap_keys(n_rep, level, key='group_bootstrap'):
+        """`group_bootstrap` / `fairness_bootstrap` (`key`: the name the error messages use; None / 0: off, else an integer B in
+        2..65536) and its `<key>_level` (strictly inside 0..1)"""
         if n_rep is None or (not isinstance(n_rep, bool) and n_rep == 0):
             return 0, None
         if isinstance(n_rep, bool) or not isinstance(n_rep, int) or not 2 <= n_rep <= _C.BOOTSTRAP_MAX_REP:
-            raise ValueError(f'group_bootstrap must be None, 0 or an integer in 2..{_C.BOOTSTRAP_MAX_REP}, not {n_rep!r}')
+            raise ValueError(f'{key} must be None, 0 or an integer in 2..{_C.BOOTSTRAP_MAX_REP}, not {n_rep!r}')
         level = 0.95 if level is None else level
         if isinstance(level, bool) or not isinstance(level, (int, float)) or not 0.0 < level < 1.0:
-            raise ValueError(f'group_bootstrap_level must lie strictly between 0 and 1, not {level!r}')
+            raise ValueError(f'{key}_level must lie strictly between 0 and 1, not {level!r}')
         return int(n_rep), float(level)
 
     @staticmethod
@@ -595,14 +666,60 @@ class Evaluator:
                                     collected.get('rec.negative_score'), collected.get('data.negative_i'), self.mode,
                                     value_type=bool({"valueunfairness", "absoluteunfairness", "underunfairness",
                                                      "overunfairness"} & set(self.metrics)), **extra)
-            for k, v in fair.items():
-                if any(k.startswith(p) for m, p in self.FAIR_PREFIX.items() if m in self.metrics):
-                    res[k] = v
+            reported = [k for k in fair if any(k.startswith(p) for m, p in self.FAIR_PREFIX.items() if m in self.metrics)]
+            res.update({k: fair[k] for k in reported})
+            if self.fair_bootstrap:
+                res.update(self._fairness_intervals(collected, sst, extra.get('intersections'), reported))
         if self.utility:
             res.update(self._utility_by_group(collected))
         if self.exposure:
             res.update(self._exposure_by_group(collected))
         return {k: round(v, self.decimal_place) for k, v in res.items()}
+
+    # metric name -> (the head of its result keys, its statistic among what bootstrap_fairness returns)
+    FAIR_STAT = {"nonparityunfairness": ("NonParity Unfairness", "nonparity"), "valueunfairness": ("Value Unfairness", "value"),
+                 "absoluteunfairness": ("Absolute Unfairness", "absolute"), "underunfairness": ("Underestimation Unfairness", "under"),
+                 "overunfairness": ("Overestimation Unfairness", "over"), "differentialfairness": ("Differential Fairness", "differential")}
+
+    def _fairness_intervals(self, collected, sst, intersections, reported) -> Dict[str, float]:
+        """`fairness_bootstrap`: '<metric> ci_low | ci_high of sensitive attribute <A>' for every key of `reported` (the point
+        estimates, whose order the new keys follow): the percentile interval of the metric over the replicates of the bootstrap
+        over users.  One bootstrap_fairness call per attribute or intersection for NonParity and DifferentialFairness, one more
+        on the first attribute for the value-type rows; the positives are sorted by item once.  More than NARROW_GROUPS groups:
+        no interval keys and one warning."""
+        B, seed = self.fair_bootstrap, self.seed
+        pos_score = collected['rec.positive_score'].to(torch.float32).contiguous()
+        pos_i, unit = collected['data.positive_i'], collected['data.positive_user']
+        per_attr = [m for m in ("nonparityunfairness", "differentialfairness") if m in self.metrics]
+        value_type = [m for m in ("valueunfairness", "absoluteunfairness", "underunfairness", "overunfairness") if m in self.metrics]
+        sort = _item_sort(pos_i) if per_attr else None
+        stats = {}
+        for n, (name, index, G, _) in enumerate(attribute_groups(sst, intersections)):
+            if G > NARROW_GROUPS:
+                getLogger().warning('fairness_bootstrap: sensitive attribute %s has %d groups, more than the %d the bootstrap '
+                                    'takes; it gets no ci_low / ci_high keys', name, G, NARROW_GROUPS)
+                continue
+            gidx = index.to(torch.int32).contiguous()
+            found = {}
+            if per_attr:
+                found.update(bootstrap_fairness(pos_i, gidx, pos_score, None, unit, G, B, seed,
+                                                differential="differentialfairness" in self.metrics, sort=sort))
+            if n == 0 and value_type:
+                rows = value_type_rows(pos_score, pos_i, gidx, unit, collected.get('rec.negative_score'),
+                                       collected.get('data.negative_i'), self.mode)
+                found.update({k: v for k, v in bootstrap_fairness(*rows, 2, B, seed, value_type=True, differential=False).items()
+                              if k in ("value", "absolute", "under", "over")})
+            for m in per_attr + (value_type if n == 0 else []):
+                head, stat = self.FAIR_STAT[m]
+                stats[f'{head} of sensitive attribute {name}'] = found[stat]
+        res = {}
+        for key in reported:
+            if key in stats:
+                low, high, _, _, _, _ = bootstrap_intervals(stats[key][None, :], self.fair_bootstrap_level, key)
+                head, name = key.split(' of sensitive attribute ', 1)
+                res[f'{head} ci_low of sensitive attribute {name}'] = float(low[0])
+                res[f'{head} ci_high of sensitive attribute {name}'] = float(high[0])
+        return res
 
     def _utility_by_group(self, collected) -> Dict[str, float]:
         """`utility_by_group`: every requested top-k / gauc / value metric per group of each selected attribute, and of each
