@@ -152,19 +152,15 @@ class Collector:
         (k = K + 1, to see a tie at its end), a user whose list hangs on an exact tie gets its dense row after all and is
         ranked on the host as there, the positives' scores are single cells (fr_recommend_cells), and `rec.meanrank` counts
         the cells against them tile by tile (fr_recommend_meanrank)."""
-        from ..functional import recommend_cells, recommend_meanrank, recommend_topk
+        from ..functional import recommend_cells, recommend_kwargs, recommend_meanrank, recommend_topk
         from ..utils.case_study import DENSE_ROWS_BYTES, history_csr
-        X, W = factors['X'], factors['W']
-        ub = factors.get('user_bias')
-        kw = dict(item_bias=factors.get('item_bias'), bias0=factors.get('bias0', 0.0), epilogue=factors.get('epilogue', 0),
-                  scale=factors.get('scale', 1.0), mask_pad=True)
-        U, n_items, dev = X.shape[0], W.shape[0], X.device
+        kw = dict(recommend_kwargs(factors), mask_pad=True, hist_indptr=hist_indptr, hist_items=hist_items)
+        U, n_items, dev = kw['X'].shape[0], kw['W'].shape[0], kw['X'].device
         K = min(max(self.topk), n_items)
         positive_u, positive_i = positive_u.to(dev, torch.int64), positive_i.to(dev, torch.int64)
         if self._err is None:
             self._err = torch.zeros(1, dtype=torch.int32, device=dev)
-        vals, topk_idx = recommend_topk(X, W, min(K + 1, n_items), user_bias=ub, hist_indptr=hist_indptr, hist_items=hist_items,
-                                        **kw)
+        vals, topk_idx = recommend_topk(k=min(K + 1, n_items), **kw)
         topk_idx = topk_idx[:, :K].contiguous()
         # the rows `eval_batch_collect` finds: the K + 1 best values of a row are the same whoever selects them
         tied = (vals[:, 1:] == vals[:, :-1]).any(dim=1).nonzero().view(-1)
@@ -172,15 +168,13 @@ class Collector:
         for lo in range(0, tied.numel(), group):
             rows = tied[lo:lo + group]
             ip, hi = history_csr(hist_indptr, hist_items, rows, n_items)
-            dense = recommend_topk(X[rows], W, 1, user_bias=None if ub is None else ub.view(-1)[rows], hist_indptr=ip,
-                                   hist_items=hi, want_scores=True, **kw)[2]
+            dense = recommend_topk(k=1, mask_pad=True, hist_indptr=ip, hist_items=hi, want_scores=True,
+                                   **recommend_kwargs(factors, rows))[2]
             topk_idx[rows] = self._host_topk(dense, K).to(dev)
         keys = torch.sort(positive_u * n_items + positive_i).values
         if self.meanrank:
-            self._add('rec.meanrank', recommend_meanrank(X, W, keys, self._err, user_bias=ub, hist_indptr=hist_indptr,
-                                                         hist_items=hist_items, **kw))
-        cells = recommend_cells(X, W, positive_u, positive_i, self._err, user_bias=ub, hist_indptr=hist_indptr, hist_items=hist_items,
-                                **kw)
+            self._add('rec.meanrank', recommend_meanrank(pos_keys=keys, err_flag=self._err, **kw))
+        cells = recommend_cells(cell_user=positive_u, cell_item=positive_i, err_flag=self._err, **kw)
         self._finish_ranking(topk_idx, keys, cells, positive_i, interaction, positive_u, K, n_items, U, dev, positive_u)
         self._add_user_attrs(interaction, dev)
 

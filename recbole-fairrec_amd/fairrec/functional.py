@@ -583,6 +583,17 @@ def _rec_args(who, X, W, user_bias, item_bias, bias0, epilogue, scale, mask_pad,
     return a, (X, W, ub, ib, ip, hi)
 
 
+def recommend_kwargs(factors, rows=None):
+    """What a model's `full_sort_factors` dict says to recommend_topk / recommend_cells / recommend_meanrank, as their keyword
+    arguments: X and W, and the optional pieces with the defaults of a plain dot product.  `rows`: only these users, in this
+    order (X[rows], user_bias[rows])."""
+    X, ub = factors['X'], factors.get('user_bias')
+    if rows is not None:
+        X, ub = X[rows], None if ub is None else ub.view(-1)[rows]
+    return dict(X=X, W=factors['W'], user_bias=ub, item_bias=factors.get('item_bias'), bias0=factors.get('bias0', 0.0),
+                epilogue=factors.get('epilogue', 0), scale=factors.get('scale', 1.0))
+
+
 def recommend_topk(X, W, k, user_bias=None, item_bias=None, bias0=0.0, epilogue=0, scale=1.0, mask_pad=False,
                    hist_indptr=None, hist_items=None, want_scores=False, slices=0):
     """fr_recommend_topk: (values, indices[, scores]) of the k best items of every row of X against the item table W, score

@@ -29,13 +29,19 @@ class AbstractRecommender(nn.Module):
         raise NotImplementedError
 
     def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
-        """Optional hook of utils/case_study.py: a model whose score of (user, item) is
+        """Optional hook, asked first by fast_path.full_sort_plan (utils/case_study.py; the Trainer under `full_sort_eval:
+        fused`), read by functional.recommend_kwargs: a model whose score of (user, item) is
         epilogue(((X[u] . W[i] + user_bias[u]) + item_bias[i]) + bias0) returns those pieces -- a dict with X [users, D] (the
         users' final embeddings, already gathered / filtered), W [n_items, D] (the item table as it lies in memory) and,
         where it has them, user_bias [users], item_bias [n_items], bias0, epilogue (fr_recommend_topk: 0 none, 1 clamp to
         [0, scale] / scale, 2 sigmoid) and scale -- and is ranked without its dense score matrix.  None (the default): the
         model is scored through full_sort_predict / predict.  `users_per_batch`: how many users the full-sort evaluation
-        scores per `predict` call, for models whose user side depends on its batch."""
+        scores per `predict` call, for models whose user side depends on its batch (fast_path.filtered_users).  A model that
+        answers declines (None) by the rules of fairrec/model/fast_path.py: `single_device_engine`, and `overrides_any` with the
+        tuple of method names kept beside its hook.  Two more optional hooks have no default here: `full_sort_pair_mlp(interaction,
+        sst_list=None, users_per_batch=None)`, asked second by full_sort_plan (the pieces of fr_pair_mlp_scores, or None), and
+        `dyn_neg_select(interaction, cand, num, M)`, asked by TrainDataLoader._dynamic_negatives (the picked ids, or None for
+        `predict` + fr_dyn_neg_select); NFCF and PFCN_MLP answer both through the shared helpers of fairrec/model/layers.py."""
         return None
 
     def other_parameter(self):

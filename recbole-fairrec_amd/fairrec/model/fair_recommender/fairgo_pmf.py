@@ -26,6 +26,7 @@ from ...engine import GenericEngine
 from ...functional import CsrMatrix, GatherAndSpMMSel, Mse, RowDot, RowGather, SigmoidBce, SoftmaxCe, SplitRows, SpMM, SpMMSel
 from ...utils.enum_type import InputType
 from ..abstract_recommender import FairRecommender
+from ..fast_path import drops_out, overrides_any
 from ..layers import ACT_CODES, MLPLayers, _HipMLP, activation_layer
 
 
@@ -161,7 +162,7 @@ class FairGo_PMF(FairRecommender):
         mlp = self.filter_layer_dict[sst_list[0]]
         name = mlp.activation.lower() if isinstance(mlp.activation, str) else mlp.activation
         return (not mlp.use_bn and ACT_CODES[name] != 0 and mlp.forced_masks is None
-                and not (mlp.training and float(mlp.dropout) > 0.0))
+                and not drops_out(mlp))
 
     def _filtered_table(self, sst_list, grad_at_z=False):
         E = self.get_ego_embeddings()
@@ -470,10 +471,13 @@ class FairGo_PMF(FairRecommender):
             pred = torch.matmul(ua[user], ia.transpose(0, 1))
             return torch.clamp(pred.view(-1), min=0., max=float(self.max_rating)) / float(self.max_rating)
 
+    FULL_SORT_DECLINES = ('full_sort_predict',)
+
     def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
         """The pieces of full_sort_predict for fr_recommend_topk: the users' rows of the propagated table, its item rows (a
-        view: they lie behind the user rows), and the clamp to [0, max_rating] / max_rating as the kernel's epilogue."""
-        if type(self).full_sort_predict is not FairGo_PMF.full_sort_predict:
+        view: they lie behind the user rows), and the clamp to [0, max_rating] / max_rating as the kernel's epilogue.  None for a
+        subclass with a full_sort_predict of its own."""
+        if overrides_any(type(self), FairGo_PMF, FairGo_PMF.FULL_SORT_DECLINES):
             return None
         user = interaction[self.USER_ID].to(self.hip_engine().device)
         with torch.no_grad():

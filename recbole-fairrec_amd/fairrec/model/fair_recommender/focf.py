@@ -52,6 +52,7 @@ from ... import _C
 from ...optim import AdamHyper, FusedLazyAdam, LazyTable
 from ...utils.enum_type import InputType
 from ..abstract_recommender import FairRecommender
+from ..fast_path import flushed
 from ..init import xavier_normal_initialization
 
 
@@ -1064,10 +1065,9 @@ class FOCF(FairRecommender):
         clamp to [0, max_rating] / max_rating as the kernel's epilogue."""
         eng = self.hip_engine()
         eng.finish()
-        eng.I.flush(eng.hyper)
+        W = flushed(eng.I, eng.hyper)
         user = interaction[self.USER_ID].to(eng.device, torch.int64).contiguous()
-        return {'X': eng.U.gather(eng.hyper, user, eng.err_flag), 'W': self.item_embedding_layer.weight.data, 'epilogue': 1,
-                'scale': float(eng.max_rating)}
+        return {'X': eng.U.gather(eng.hyper, user, eng.err_flag), 'W': W, 'epilogue': 1, 'scale': float(eng.max_rating)}
 
     def state_dict(self, *args, **kwargs):
         if self._engine is not None:

@@ -17,8 +17,7 @@ from ... import _C
 from ...engine import GenericEngine
 from ...utils.enum_type import InputType
 from ..abstract_recommender import FairRecommender
-from ..layers import (MLPLayers, dyn_neg_pair_mlp_pieces, dynamic_neg_scorer_of, full_sort_pair_mlp_pieces,
-                      full_sort_scorer_of)
+from ..layers import MLPLayers, dyn_neg_pair_mlp_select, dynamic_neg_scorer_of, full_sort_pair_mlp, full_sort_scorer_of
 
 
 class _NfcfLoss(torch.autograd.Function):
@@ -289,36 +288,18 @@ class NFCF(FairRecommender):
 
     def full_sort_pair_mlp(self, interaction, sst_list=None, users_per_batch=None):
         """The pieces of predict() on every item for fr_pair_mlp_scores (`full_sort_scorer: split`), or None: the dense path
-        then serves the call (fairrec/model/layers.py: full_sort_pair_mlp_pieces)."""
-        if self.shard is not None:
-            return None
-        eng = self.hip_engine()
-        return full_sort_pair_mlp_pieces(self.full_sort_scorer, self.mlp_layers, eng,
-                                         lambda: eng.lookup("user_embedding.weight", interaction[self.USER_ID]),
-                                         "item_embedding.weight", self.n_items)
+        then serves the call (fairrec/model/layers.py: full_sort_pair_mlp).  No method of a subclass makes it decline."""
+        return full_sort_pair_mlp(self, self.mlp_layers, self.full_sort_scorer, "user_embedding.weight", "item_embedding.weight",
+                                  NFCF, (), interaction)
+
+    DYN_NEG_DECLINES = ('predict', 'forward', '_score_logits')
 
     def dyn_neg_select(self, interaction, cand, num, M):
-        """Dynamic negative sampling (TrainDataLoader._dynamic_negatives) with `dynamic_neg_scorer: split`: of the M
-        candidates of each negative slot the id the scorer rates highest, in one launch (fr_dyn_neg_mlp_select) -- the user rows
-        are looked up once and go through the user half of the first layer once, the candidates' rows are read in the kernel.
-        predict() is sigmoid(mlp_layers(cat(user row, item row))) and nothing else, which is what the kernel computes up to the
-        first layer's summation order; a model that drops out at this point (training mode), a subclass with a predict or
-        forward of its own, row-sharded tables and every scorer outside dyn_neg_pair_mlp_pieces answer None, and the loader goes
-        through predict().  None as well under the default `pairs`."""
-        cls, mlp = type(self), self.mlp_layers
-        if (self.dynamic_neg_scorer != 'split' or self.shard is not None or cls.predict is not NFCF.predict
-                or cls.forward is not NFCF.forward or cls._score_logits is not NFCF._score_logits
-                or (mlp.training and float(mlp.dropout) > 0.0)):
-            return None
-        from ...functional import dyn_neg_mlp_select
-        eng = self.hip_engine()
-        pieces = dyn_neg_pair_mlp_pieces(self.dynamic_neg_scorer, mlp, eng,
-                                         lambda: eng.lookup("user_embedding.weight", interaction[self.USER_ID]))
-        if pieces is None:
-            return None
-        with torch.no_grad():
-            return dyn_neg_mlp_select(pieces, eng._tables["item_embedding.weight"], eng._hyper("item_embedding.weight"), cand,
-                                      num, M, eng.err_flag)
+        """Dynamic negative sampling with `dynamic_neg_scorer: split`: the pick of fr_dyn_neg_mlp_select over this scorer, or
+        None -- the loader goes through predict() -- under the default `pairs`, for a subclass with one of DYN_NEG_DECLINES of
+        its own, and wherever fairrec/model/layers.py: dyn_neg_pair_mlp_select declines."""
+        return dyn_neg_pair_mlp_select(self, self.mlp_layers, self.dynamic_neg_scorer, "user_embedding.weight",
+                                       "item_embedding.weight", NFCF, NFCF.DYN_NEG_DECLINES, interaction, cand, num, M)
 
     def state_dict(self, *args, **kwargs):
         if self._engine is not None:

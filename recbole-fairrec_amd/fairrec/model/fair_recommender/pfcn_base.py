@@ -25,6 +25,7 @@ from ...engine import GenericEngine
 from ...functional import Bpr, BprBroadcastGlobal, BprBroadcastPacked, RowDot, RowDotPair, SigmoidBce, SoftmaxCe, SplitRows, SubScaled
 from ...utils.enum_type import InputType
 from ..abstract_recommender import FairRecommender
+from ..fast_path import config_choice, filtered_users, flushed, overrides_any, single_device_engine
 from ..layers import MLPLayers
 
 
@@ -43,10 +44,7 @@ class PFCNBase(FairRecommender):
             assert self.filter_mode in ('cm', 'sm', 'none')
         except AssertionError:
             raise AssertionError('filter_mode must be cm, sm or none')
-        stats = config['filter_eval_statistics']
-        self.filter_eval_statistics = 'batch' if stats is None else str(stats).lower()
-        if self.filter_eval_statistics not in ('batch', 'running'):
-            raise ValueError(f'filter_eval_statistics must be batch or running, not [{stats}]')
+        self.filter_eval_statistics = config_choice(config, 'filter_eval_statistics', ('batch', 'running'), 'batch')
         self.filter_num, self.sst_dict = self._get_filter_info()
         self.sst_size = self._get_sst_size(dataset.get_user_feature())
         if self.filter_mode != 'none':
@@ -298,6 +296,8 @@ class PFCNBase(FairRecommender):
     def _predict_score(self, ue, ie):
         return RowDot.apply(ue, ie).unsqueeze(-1)
 
+    DYN_NEG_DECLINES = ('_predict_score', '_item_tower', '_user_tower', 'predict')
+
     def dyn_neg_select(self, interaction, cand, num, M):
         """Dynamic negative sampling (TrainDataLoader._dynamic_negatives) for a dot-product model on one device: of the M
         candidates of each negative slot the id `predict` scores highest, in one launch (fr_dyn_neg_dot_select) -- the
@@ -309,15 +309,10 @@ class PFCNBase(FairRecommender):
             # `sst_list=None`), so the reference's dynamic branch stops there too
             raise NotImplementedError(f'dynamic negative sampling with filter_mode [{self.filter_mode}]: predict() is called '
                                       'without sst_list, which the filtered PFCN models need')
-        cls = type(self)
-        if (self.shard is not None or cls._predict_score is not PFCNBase._predict_score
-                or cls._item_tower is not PFCNBase._item_tower or cls._user_tower is not PFCNBase._user_tower
-                or cls.predict is not PFCNBase.predict):
+        eng = None if overrides_any(type(self), PFCNBase, PFCNBase.DYN_NEG_DECLINES) else single_device_engine(self)
+        if eng is None:
             return None
         from ...functional import dyn_neg_dot_select
-        eng = self.hip_engine()
-        if type(eng) is not GenericEngine:      # row-sharded / replicated engines: the generic path
-            return None
         user = interaction[self.USER_ID]
         with torch.no_grad():
             ue = eng.lookup(self._utab, user)
@@ -329,35 +324,25 @@ class PFCNBase(FairRecommender):
             return dyn_neg_dot_select(eng._tables[self._itab], eng._hyper(self._itab), ue, cand, num, M, eng.err_flag,
                                       item_bias=ib, user_bias=ub, global_bias=gb)
 
+    FULL_SORT_DECLINES = DYN_NEG_DECLINES + ('_score',)
+
     def full_sort_factors(self, interaction, sst_list=None, users_per_batch=None):
-        """The pieces of predict() for fr_recommend_topk (PFCN_PMF / PFCN_BiasedMF; a model with a scorer or towers of its own
-        answers None): the filtered user embeddings, the flushed item table, the biases, and the sigmoid as the kernel's
+        """The pieces of predict() for fr_recommend_topk (PFCN_PMF / PFCN_BiasedMF; a model with one of FULL_SORT_DECLINES of
+        its own -- a scorer, towers -- or without a single-device engine answers None): the filtered user embeddings, the flushed item table, the biases, and the sigmoid as the kernel's
         epilogue.  The filters' BatchNorm layers normalise by the statistics of the batch they are given, so the users go
         through them `users_per_batch` at a time -- the users of one predict() batch of the full-sort evaluation, whose
         statistics over the repeated rows are those of the rows themselves.  (`filter_eval_statistics: running`, model in
         eval mode: a row's filtered embedding does not depend on its group, and any `users_per_batch` gives the same bits.)"""
-        cls = type(self)
-        if (self.shard is not None or cls._predict_score is not PFCNBase._predict_score or cls._score is not PFCNBase._score
-                or cls._item_tower is not PFCNBase._item_tower or cls._user_tower is not PFCNBase._user_tower
-                or cls.predict is not PFCNBase.predict):
-            return None
-        eng = self.hip_engine()
-        if type(eng) is not GenericEngine:      # row-sharded / replicated engines: the generic path
+        eng = None if overrides_any(type(self), PFCNBase, PFCNBase.FULL_SORT_DECLINES) else single_device_engine(self)
+        if eng is None:
             return None
         user = interaction[self.USER_ID]
         with torch.no_grad():
-            ue = eng.lookup(self._utab, user)
-            if self.filter_mode != 'none':
-                per = int(users_per_batch) if users_per_batch else ue.shape[0]
-                ue = torch.cat([self._filter(ue[lo:lo + per], sst_list) for lo in range(0, ue.shape[0], per)]) \
-                    if ue.shape[0] else ue
-            it = eng._tables[self._itab]
-            it.flush(eng._hyper(self._itab))
-            out = {'X': ue, 'W': it.weight, 'epilogue': 2}
+            ue = filtered_users(self, eng.lookup(self._utab, user), sst_list, users_per_batch)
+            out = {'X': ue, 'W': flushed(eng._tables[self._itab], eng._hyper(self._itab)), 'epilogue': 2}
             if self.biased:
-                ib = eng._tables["item_bias.weight"]
-                ib.flush(eng._hyper("item_bias.weight"))
-                out.update(user_bias=eng.lookup("user_bias.weight", user).view(-1), item_bias=ib.weight.view(-1),
+                ib = flushed(eng._tables["item_bias.weight"], eng._hyper("item_bias.weight"))
+                out.update(user_bias=eng.lookup("user_bias.weight", user).view(-1), item_bias=ib.view(-1),
                            bias0=float(self.global_bias))
             return out
 

@@ -6,8 +6,8 @@ cosine_similarity * 10 in training, sigmoid(cosine) in predict; filters and disc
 normalised once per user and once per item -- `full_sort_factors` -- on the fused score-and-select kernels."""
 import torch
 
-from ...engine import GenericEngine
 from ...functional import RowDot
+from ..fast_path import config_choice, filtered_users, flushed, single_device_engine
 from ..layers import MLPLayers
 from .pfcn_base import PFCNBase
 
@@ -19,11 +19,7 @@ FUSED_MAX_DIM = 256             # the widest rows the fused ranking kernels (and
 def dmf_full_sort_scorer_of(config) -> str:
     """The config key `full_sort_scorer` of PFCN_DMF: `pairs` (default: `predict` on every (user, item) pair, the reference)
     or `towers` (each tower once per row, unit rows, the cosine as the fused ranking kernels' dot product)."""
-    value = config['full_sort_scorer']
-    name = 'pairs' if value is None else str(value).lower()
-    if name not in ('pairs', 'towers'):
-        raise ValueError(f'full_sort_scorer of PFCN_DMF must be pairs or towers, not [{value}]')
-    return name
+    return config_choice(config, 'full_sort_scorer', ('pairs', 'towers'), 'pairs', of=' of PFCN_DMF')
 
 
 class PFCN_DMF(PFCNBase):
@@ -81,26 +77,20 @@ class PFCN_DMF(PFCNBase):
         None -- the dense path then serves the call -- with `pairs`, on the row-sharded and replicated engines, for rows wider
         than 256, and for a model in training mode whose towers drop out."""
         from ...functional import rows_l2_normalize
-        if self.full_sort_scorer != 'towers' or self.shard is not None or self.embedding_size > FUSED_MAX_DIM:
+        if (self.full_sort_scorer != 'towers' or self.embedding_size > FUSED_MAX_DIM
+                or (self.training and float(self.mlp_dropout) > 0.0)):
             return None
-        if self.training and float(self.mlp_dropout) > 0.0:
-            return None
-        eng = self.hip_engine()
-        if type(eng) is not GenericEngine:      # row-sharded / replicated engines: the generic path
+        eng = single_device_engine(self)
+        if eng is None:
             return None
         user = interaction[self.USER_ID]
         with torch.no_grad():
             if user.numel() == 0:       # an empty request: empty factors on the user side
                 ue = torch.empty((0, self.embedding_size), dtype=torch.float32, device=eng.device)
             else:
-                ue = self._user_tower(eng.lookup(self._utab, user))
-                if self.filter_mode != 'none':
-                    per = int(users_per_batch) if users_per_batch else ue.shape[0]
-                    ue = torch.cat([self._filter(ue[lo:lo + per], sst_list) for lo in range(0, ue.shape[0], per)])
+                ue = filtered_users(self, self._user_tower(eng.lookup(self._utab, user)), sst_list, users_per_batch)
                 ue = rows_l2_normalize(ue, eps=COSINE_EPS, out=ue)
-            it = eng._tables[self._itab]
-            it.flush(eng._hyper(self._itab))
-            rows = it.weight
+            rows = flushed(eng._tables[self._itab], eng._hyper(self._itab))
             W = torch.empty((rows.shape[0], self.embedding_size), dtype=torch.float32, device=rows.device)
             for lo in range(0, rows.shape[0], ITEM_TOWER_ROWS):
                 rows_l2_normalize(self._item_tower(rows[lo:lo + ITEM_TOWER_ROWS]), eps=COSINE_EPS, out=W[lo:lo + ITEM_TOWER_ROWS])

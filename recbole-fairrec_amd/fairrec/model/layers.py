@@ -15,6 +15,7 @@ import torch.nn as nn
 from torch.nn.init import normal_
 
 from .. import _C
+from .fast_path import config_choice, drops_out, filtered_users, flushed, overrides_any, single_device_engine
 
 ACT_CODES = {None: 0, "none": 0, "relu": 1, "leakyrelu": 2, "sigmoid": 3, "tanh": 4}
 
@@ -468,7 +469,7 @@ class MLPLayers(nn.Module):
             return mlp_infer(self, x.to(torch.float32))
         if self.use_bn:
             params = [t for lin, bn in zip(lins, bns) for t in (lin.weight, lin.bias, bn.weight, bn.bias)]
-            if passes != 1 and (self.training and float(self.dropout) > 0.0):
+            if passes != 1 and drops_out(self):
                 raise ValueError("passes > 1 needs a module without dropout (two evaluations would differ)")
             # (num_batches_tracked moves by `passes` in each layer's fold launch, fr_bn_fwd_ex: no launch of its own;
             # FAIRREC_BN_COUNT_SEPARATE=1: one multi-tensor add per forward instead, for A/B runs)
@@ -520,48 +521,50 @@ class MLPLayers(nn.Module):
 def full_sort_scorer_of(config) -> str:
     """The config key `full_sort_scorer` of the MLP-scored models (NFCF, PFCN_MLP): `pairs` (default: `predict` on every
     (user, item) pair, the reference) or `split` (first layer split, the rest per pair in one kernel: fr_pair_mlp_scores)."""
-    value = config['full_sort_scorer']
-    name = 'pairs' if value is None else str(value).lower()
-    if name not in ('pairs', 'split'):
-        raise ValueError(f'full_sort_scorer must be pairs or split, not [{value}]')
-    return name
-
-
-def full_sort_pair_mlp_pieces(scorer, mlp, engine, user_rows, item_table_name, n_items):
-    """What a model's `full_sort_pair_mlp` hook answers: the pieces of fr_pair_mlp_scores for the scorer `mlp` over
-    cat(user_rows[u], item table row i), or None -- the dense path then serves the call -- when the key is `pairs`, the
-    scorer has BatchNorm, an activation other than ReLU, recorded dropout masks or a shape outside fr_pair_mlp_supported, or
-    the engine is not the single-device GenericEngine.  `user_rows`: a callable, so that nothing is looked up for a None."""
-    from ..engine import GenericEngine
-    from ..functional import pair_mlp_pieces, pair_mlp_supported
-    if scorer != 'split' or type(engine) is not GenericEngine or not pair_mlp_supported(mlp):
-        return None
-    with torch.no_grad():
-        table = engine._tables[item_table_name]
-        table.flush(engine._hyper(item_table_name))
-        return pair_mlp_pieces(mlp, user_rows(), table.weight[:n_items])
+    return config_choice(config, 'full_sort_scorer', ('pairs', 'split'), 'pairs')
 
 
 def dynamic_neg_scorer_of(config) -> str:
     """The config key `dynamic_neg_scorer` of the MLP-scored models (NFCF, PFCN_MLP): how dynamic negative sampling rates its
     candidates -- `pairs` (default: `predict` on the repeated interaction, the reference) or `split` (first layer split, the
     rest per candidate and the pick in one kernel: fr_dyn_neg_mlp_select)."""
-    value = config['dynamic_neg_scorer']
-    name = 'pairs' if value is None else str(value).lower()
-    if name not in ('pairs', 'split'):
-        raise ValueError(f'dynamic_neg_scorer must be pairs or split, not [{value}]')
-    return name
+    return config_choice(config, 'dynamic_neg_scorer', ('pairs', 'split'), 'pairs')
 
 
-def dyn_neg_pair_mlp_pieces(scorer, mlp, engine, user_rows):
-    """What a model's `dyn_neg_select` hook hands to fr_dyn_neg_mlp_select for the scorer `mlp` over cat(user_rows[i], item
-    table row): P over the batch rows and the layer list, or None -- the loader then goes through `predict` -- when the key is
-    `pairs`, the scorer has BatchNorm, an activation other than ReLU, recorded dropout masks or a shape outside
-    fr_pair_mlp_supported, or the engine is not the single-device GenericEngine.  `user_rows`: a callable, so that nothing is
-    looked up for a None."""
-    from ..engine import GenericEngine
-    from ..functional import dyn_neg_mlp_pieces, pair_mlp_supported
-    if scorer != 'split' or type(engine) is not GenericEngine or not pair_mlp_supported(mlp):
+def _split_scorer_engine(model, mlp, scorer, base, names):
+    """The engine on which the split pair-MLP kernels serve the scorer `mlp` of `model`, or None -- the dense path then serves
+    the call -- when the key is `pairs`, a subclass replaces one of `base`'s methods `names`, the tables do not lie on one device,
+    or the scorer has BatchNorm, an activation other than ReLU, recorded dropout masks or a shape outside fr_pair_mlp_supported."""
+    from ..functional import pair_mlp_supported
+    if scorer != 'split' or overrides_any(type(model), base, names):
+        return None
+    eng = single_device_engine(model)
+    return eng if eng is not None and pair_mlp_supported(mlp) else None
+
+
+def full_sort_pair_mlp(model, mlp, scorer, user_table, item_table, base, names, interaction, sst_list=None, users_per_batch=None):
+    """What the `full_sort_pair_mlp` hook of NFCF and PFCN_MLP answers: the pieces of fr_pair_mlp_scores for the scorer `mlp`
+    over cat(filtered user row, row of the flushed item table), or None where `_split_scorer_engine` has no engine for the call."""
+    from ..functional import pair_mlp_pieces
+    eng = _split_scorer_engine(model, mlp, scorer, base, names)
+    if eng is None:
         return None
     with torch.no_grad():
-        return dyn_neg_mlp_pieces(mlp, user_rows())
+        items = flushed(eng._tables[item_table], eng._hyper(item_table))[:model.n_items]
+        users = filtered_users(model, eng.lookup(user_table, interaction[model.USER_ID]), sst_list, users_per_batch)
+        return pair_mlp_pieces(mlp, users, items)
+
+
+def dyn_neg_pair_mlp_select(model, mlp, scorer, user_table, item_table, base, names, interaction, cand, num, M):
+    """What the `dyn_neg_select` hook of NFCF and PFCN_MLP answers (TrainDataLoader._dynamic_negatives): of the M candidates of
+    each negative slot the id the scorer `mlp` rates highest, in one launch (fr_dyn_neg_mlp_select) -- the user rows are
+    looked up once and go through the user half of the first layer once, the candidates' rows are read in the kernel: predict()
+    up to the first layer's summation order where predict() is sigmoid(mlp(cat(user row, item row))) and nothing else.  None --
+    the loader goes through predict() -- for a scorer that drops out now and where `_split_scorer_engine` has no engine."""
+    from ..functional import dyn_neg_mlp_pieces, dyn_neg_mlp_select
+    eng = None if drops_out(mlp) else _split_scorer_engine(model, mlp, scorer, base, names)
+    if eng is None:
+        return None
+    with torch.no_grad():
+        pieces = dyn_neg_mlp_pieces(mlp, eng.lookup(user_table, interaction[model.USER_ID]))
+        return dyn_neg_mlp_select(pieces, eng._tables[item_table], eng._hyper(item_table), cand, num, M, eng.err_flag)

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _C
+from ..model.fast_path import config_choice, full_sort_plan, with_subset
 from ..optim import FUSED_LAZY, FusedLazyAdam
 from ..sampler import host_numpy_stream
 from ..utils import calculate_valid_score, dict2str, early_stopping, ensure_dir, get_local_time
@@ -32,10 +33,7 @@ def full_sort_eval_of(config) -> str:
     the key: the [users, n_items] score matrix and torch.topk) or `fused` (a model that answers `full_sort_factors` is ranked
     and counted in the scoring kernel, eval_batch_collect_fused; any other model takes the matrix path).  `fused` selects
     max(topk) + 1 items per user to see a tie at the end of the list, so max(topk) is at most FR_TOPK_MAX - 1."""
-    value = config['full_sort_eval']
-    value = 'matrix' if value is None else value
-    if value not in ('matrix', 'fused'):
-        raise ValueError(f'full_sort_eval must be matrix or fused, not [{value}]')
+    value = config_choice(config, 'full_sort_eval', ('matrix', 'fused'), 'matrix', lower=False)     # (`Fused` is no value)
     if value == 'fused':
         from .._C import FR_TOPK_MAX
         topk = config['topk'] or [10]
@@ -58,6 +56,8 @@ class AbstractTrainer:
 
 
 class Trainer(AbstractTrainer):
+    full_sort_eval = 'matrix'       # (a trainer built without __init__ evaluates as the default does)
+
     def __init__(self, config, model):
         super().__init__(config, model)
         self.logger = getLogger()
@@ -406,19 +406,13 @@ class Trainer(AbstractTrainer):
         """[users, n_items] scores of a batch of users: `model.full_sort_predict`, or -- as the reference does when a
         model has none (trainer.py:425-433) -- `predict` on every (user, item) pair, in chunks (shared with utils/case_study.py).
         A model whose `full_sort_pair_mlp` hook answers (`full_sort_scorer: split`) is scored by fr_pair_mlp_scores instead."""
-        from ..utils.case_study import dense_full_sort_scores, split_full_sort_scores, users_per_batch
-        scores = split_full_sort_scores(self.model, interaction, users_per_batch(self.config, n_items), sst_list)
-        if scores is not None:
-            return scores
-        return dense_full_sort_scores(self.model, interaction, n_items, users_per_batch(self.config, n_items),
-                                      self.config['ITEM_ID_FIELD'], self.device, sst_list)
-
-    def _full_sort_factors(self, interaction, n_items, sst_list=None):
-        """What the model's `full_sort_factors` hook answers for a batch of users (as case_study asks it), or None: a model
-        without the hook, or one that declines (a scorer of its own, a multi-GPU engine)."""
-        from ..utils.case_study import users_per_batch
-        hook = getattr(self.model, 'full_sort_factors', None)
-        return hook(interaction, sst_list, users_per_batch=users_per_batch(self.config, n_items)) if hook is not None else None
+        from ..functional import pair_mlp_scores
+        from ..utils.case_study import dense_full_sort_scores, users_per_batch
+        per = users_per_batch(self.config, n_items)
+        kind, pieces = full_sort_plan(self.model, interaction, sst_list, per, ask=('pair_mlp',))
+        if kind == 'pair_mlp':
+            return pair_mlp_scores(pieces)
+        return dense_full_sort_scores(self.model, interaction, n_items, per, self.config['ITEM_ID_FIELD'], self.device, sst_list)
 
     def _ranking_evaluate(self, eval_data, sst_lists=(None,)):
         """One result over everything collected: every batch scored once per entry of `sst_lists` (None = no filter
@@ -433,20 +427,21 @@ class Trainer(AbstractTrainer):
             per = int(self.config['eval_batch_size'] or 4096)
             for interaction, row_idx, positive_u, positive_i in eval_data:
                 for sst_list in sst_lists:
-                    extra = () if sst_list is None else (sst_list,)
-                    scores = torch.cat([self.model.predict(interaction[lo:lo + per], *extra).view(-1)
+                    scores = torch.cat([with_subset(self.model.predict, interaction[lo:lo + per], sst_list).view(-1)
                                         for lo in range(0, len(interaction), per)])
                     collector.eval_batch_collect_candidates(scores, row_idx, interaction, positive_u, positive_i, n_items)
             return OrderedDict(evaluator.evaluate(collector.get_data_struct()))
-        fused = getattr(self, 'full_sort_eval', 'matrix') == 'fused'
+        from ..utils.case_study import history_csr, users_per_batch
+        fused = self.full_sort_eval == 'fused'      # only then is a model asked for its factors: `matrix` scores every model densely
         for user_df, (hist_u, hist_i), positive_u, positive_i in eval_data:
             user_df = user_df.to(self.device)
             csr = None
             for sst_list in sst_lists:
-                factors = self._full_sort_factors(user_df, n_items, sst_list) if fused else None
+                factors = None
+                if fused:
+                    factors = full_sort_plan(self.model, user_df, sst_list, users_per_batch(self.config, n_items), ask=('factors',))[1]
                 if factors is not None:                                # `full_sort_eval: fused`: no [users, n_items] matrix
                     if csr is None:
-                        from ..utils.case_study import history_csr
                         csr = history_csr(eval_data.hist_indptr, eval_data.hist_items, user_df[eval_data.uid_field], n_items)
                     collector.eval_batch_collect_fused(factors, user_df, csr[0], csr[1], positive_u, positive_i)
                     continue
@@ -468,8 +463,7 @@ class Trainer(AbstractTrainer):
         for interaction in eval_data:
             interaction = interaction.to(self.device)
             for sst_list in sst_lists:
-                extra = () if sst_list is None else (sst_list,)
-                collector.eval_batch_collect_labeled(self.model.predict(interaction, *extra), interaction)
+                collector.eval_batch_collect_labeled(with_subset(self.model.predict, interaction, sst_list), interaction)
         return OrderedDict(evaluator.evaluate(collector.get_data_struct()))
 
     def _load_for_eval(self, load_best_model, model_file):

@@ -1,7 +1,9 @@
 """recbole.utils.case_study: what a trained model recommends.
 
 `full_sort_scores` / `full_sort_topk` (reference case_study.py:20-91) for a list of users, on the device, plus the optional
-attribute subset the filtered models take.  A dot-product model answers `full_sort_factors` and is ranked by
+attribute subset the filtered models take.  Which of three paths serves a call is decided in one place,
+model/fast_path.full_sort_plan, which the Trainer's full-sort evaluation asks as well.  A dot-product model answers
+`full_sort_factors` and is ranked by
 fr_recommend_topk, which never stores the [users, n_items] matrix; a model whose MLP scorer over cat(user, item) answers
 `full_sort_pair_mlp` (NFCF, PFCN_MLP with `full_sort_scorer: split`) is scored by fr_pair_mlp_scores -- the first layer
 split into a user half and an item half, the rest per pair in one kernel -- and ranked by fr_topk_rows; every other model
@@ -18,16 +20,16 @@ import torch
 
 from .. import _C
 from ..data.interaction import Interaction
+from ..model.fast_path import full_sort_plan, with_subset
 
 
 def dense_full_sort_scores(model, interaction, n_items, users_per_batch, iid_field, device, sst_list=None):
     """[users, n_items] scores of a batch of users: `model.full_sort_predict`, or -- as the reference does when a model has
     none (trainer.py:425-433) -- `predict` on every (user, item) pair, `users_per_batch` users at a time."""
     from ..model.abstract_recommender import AbstractRecommender
-    extra = () if sst_list is None else (sst_list,)
     if type(model).full_sort_predict is not AbstractRecommender.full_sort_predict:
         try:
-            return model.full_sort_predict(interaction, *extra).view(-1, n_items)
+            return with_subset(model.full_sort_predict, interaction, sst_list).view(-1, n_items)
         except NotImplementedError:
             pass
     U = len(interaction)
@@ -37,19 +39,8 @@ def dense_full_sort_scores(model, interaction, n_items, users_per_batch, iid_fie
     for lo in range(0, U, per):
         part = interaction[lo:lo + per].repeat_interleave(n_items)
         part.update(type(part)({iid_field: items.repeat(min(per, U - lo))}))
-        out[lo:lo + per] = model.predict(part, *extra).view(-1, n_items)
+        out[lo:lo + per] = with_subset(model.predict, part, sst_list).view(-1, n_items)
     return out
-
-
-def split_full_sort_scores(model, interaction, users_per_batch, sst_list=None):
-    """The [users, n_items] scores of `model.full_sort_pair_mlp`'s pieces, unmasked, or None when the model has no such hook
-    or the hook declines (the dense path then serves the call)."""
-    hook = getattr(model, 'full_sort_pair_mlp', None)
-    pieces = hook(interaction, sst_list, users_per_batch=users_per_batch) if hook is not None else None
-    if pieces is None:
-        return None
-    from ..functional import pair_mlp_scores
-    return pair_mlp_scores(pieces)
 
 
 def users_per_batch(config, n_items):
@@ -95,14 +86,6 @@ class _Request:
         self.iid_field = dataset.iid_field
         self.model = model
 
-    def factors(self, sst_list):
-        hook = getattr(self.model, 'full_sort_factors', None)
-        return hook(self.interaction, sst_list, users_per_batch=self.per) if hook is not None else None
-
-    def pair_mlp(self, sst_list):
-        hook = getattr(self.model, 'full_sort_pair_mlp', None)
-        return hook(self.interaction, sst_list, users_per_batch=self.per) if hook is not None else None
-
     def split(self, pieces, lo, hi, out=None):
         """Rows lo..hi of the split scorer's masked matrix (fr_pair_mlp_scores)."""
         from ..functional import pair_mlp_scores
@@ -123,10 +106,9 @@ class _Request:
         return scores
 
     def fused(self, f, k, want_scores):
-        from ..functional import recommend_topk
-        return recommend_topk(f['X'], f['W'], k, user_bias=f.get('user_bias'), item_bias=f.get('item_bias'),
-                              bias0=f.get('bias0', 0.0), epilogue=f.get('epilogue', 0), scale=f.get('scale', 1.0),
-                              mask_pad=True, hist_indptr=self.indptr, hist_items=self.items, want_scores=want_scores)
+        from ..functional import recommend_kwargs, recommend_topk
+        return recommend_topk(k=k, mask_pad=True, hist_indptr=self.indptr, hist_items=self.items, want_scores=want_scores,
+                              **recommend_kwargs(f))
 
 
 class _EvalMode:
@@ -152,14 +134,13 @@ def full_sort_scores(uid_series, model, test_data, device=None, sst_list=None):
     user, its item and the parameters alone)."""
     req = _Request(uid_series, model, test_data, device)
     with _EvalMode(model):
-        f = req.factors(sst_list)
-        if f is not None:
+        kind, answer = full_sort_plan(model, req.interaction, sst_list, req.per)
+        if kind == 'factors':
             if req.uids.numel() == 0:
                 return torch.empty((0, req.n_items), dtype=torch.float32, device=req.device)
-            return req.fused(f, 1, True)[2]
-        pieces = req.pair_mlp(sst_list)
-        if pieces is not None:
-            return req.split(pieces, 0, req.uids.numel())
+            return req.fused(answer, 1, True)[2]
+        if kind == 'pair_mlp':
+            return req.split(answer, 0, req.uids.numel())
         return req.dense(0, req.uids.numel(), sst_list)
 
 
@@ -175,12 +156,11 @@ def full_sort_topk(uid_series, model, test_data, k, device=None, sst_list=None):
         raise ValueError(f'full_sort_topk: k = {k} not in 1..{req.n_items}')
     from ..functional import topk_rows
     with _EvalMode(model):
-        f = req.factors(sst_list)
-        if f is not None:
-            return req.fused(f, k, False)
+        kind, pieces = full_sort_plan(model, req.interaction, sst_list, req.per)
+        if kind == 'factors':
+            return req.fused(pieces, k, False)
         U = req.uids.numel()
-        pieces = req.pair_mlp(sst_list)
-        if pieces is not None:      # (the users' halves are formed already: any grouping gives the same bits)
+        if kind == 'pair_mlp':      # (the users' halves are formed already: any grouping gives the same bits)
             group = max(DENSE_ROWS_BYTES // (4 * req.n_items), 1)
             buf = torch.empty((min(group, U), req.n_items), dtype=torch.float32, device=req.device)
         else:
@@ -188,7 +168,7 @@ def full_sort_topk(uid_series, model, test_data, k, device=None, sst_list=None):
         vals, idxs = [], []
         for lo in range(0, U, group):
             hi = min(lo + group, U)
-            v, i = topk_rows(req.split(pieces, lo, hi, buf[:hi - lo]) if pieces is not None else req.dense(lo, hi, sst_list), k)
+            v, i = topk_rows(req.split(pieces, lo, hi, buf[:hi - lo]) if kind == 'pair_mlp' else req.dense(lo, hi, sst_list), k)
             vals.append(v)
             idxs.append(i)
         if not vals:
